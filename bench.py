@@ -16,7 +16,15 @@ the secondary key `synthetic_nms_tensor`.
 Multi-GPU: inference does not exchange data -> N independent replicas, one process per GPU,
 "weak" scaling; the only collective is the timing barrier / max-reduce.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` and `cpu_baseline`.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the contract fields (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  Everything else the benchmark measures -- the sequential and synthetic-NMS
+figures, leg split, per-kernel roofline, vendor-GEMM comparison, clocks / sustained leg, `cpu_baseline`, the appended train leg, and in
+--mode train the gradient-exchange leg and the kernel families -- runs only with --full, after the timed region, and adds its keys to
+the same line.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32, rank 0): the detections, a seeded
+sample of the prediction tensor (inference) or the loss and a seeded sample of the updated weights (--mode train).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -76,6 +84,49 @@ def per_kernel_times(plan, reps=5, forms=None):
             a[2] += e0.elapsed_time(e1) * 1e-3
             a[3] += 1
     return acc
+
+
+DUMP_BYTES_CAP = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy in float32 (at most DUMP_BYTES_CAP in all)"""
+    import numpy as np
+
+    arrs = {k: v.detach().float().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_BYTES_CAP, f"--dump-outputs: {total} bytes > {DUMP_BYTES_CAP}"
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(d / f"{k}.npy", a)
+
+
+def seeded_rows(n, k, seed=0):
+    """a fixed, sorted sample of k of n row indices (all n when k >= n)"""
+    if k >= n:
+        return torch.arange(n)
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def infer_outputs(pred, dets, rows_cap=2048, pred_bytes_cap=48 << 20):
+    """what a caller of the inference step receives, for --dump-outputs: the detections of every image as one (n, 7) array
+    [image, x1, y1, x2, y2, conf, cls] and a seeded row sample of the decoded prediction tensor (the whole tensor is 274 MB at batch 32)"""
+    bs, n_rows, no = pred.shape
+    k = max(1, min(rows_cap, pred_bytes_cap // (4 * bs * no)))
+    rows = seeded_rows(n_rows, k)
+    det = torch.cat([torch.cat((torch.full((d.shape[0], 1), float(i)), d.detach().float().cpu()), 1) for i, d in enumerate(dets)])
+    return {"detections": det, "predictions_sample": pred[:, rows.to(pred.device)], "predictions_sample_rows": rows}
+
+
+def train_outputs(model, loss, per_param=1024):
+    """what a caller of the train step receives, for --dump-outputs: the loss and a seeded sample of every parameter after the step
+    (per_param elements of each, in named_parameters order)"""
+    parts = []
+    for i, (_, p) in enumerate(model.named_parameters()):
+        flat = p.detach().reshape(-1)
+        parts.append(flat[seeded_rows(flat.numel(), per_param, seed=i).to(flat.device)].float().cpu())
+    return {"loss": loss.detach().reshape(1), "weights_sample": torch.cat(parts)}
 
 
 def host_threads(cap=32):
@@ -150,7 +201,7 @@ def train_flops_per_image(model, hw):
     return 3.0 * total - (first or 0.0)
 
 
-def run_train(args, rank, world, dev, parallel, yo, batch, steps, warmup):
+def run_train(args, rank, world, dev, parallel, yo, batch, steps, warmup, dump_dir=None):
     """Data-parallel training step (BASELINE configs[2] shape per GPU): forward (batch-stat BN) + ComputeLoss + backward with
     the gradient all-reduce overlapped (parallel.GradBuckets; RCCL over xGMI) + the fused optimizer step.  Weak scaling.
     Returns the result record (all ranks run it; rank 0 reports)."""
@@ -194,13 +245,15 @@ def run_train(args, rank, world, dev, parallel, yo, batch, steps, warmup):
     parallel.barrier()
     dt = parallel.max_over_ranks(time.perf_counter() - t0, dev)
     group = parallel.describe(dev)   # (collective: every rank calls it) who took part, as the communicator sees it
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, train_outputs(model, loss))
     flops_img = train_flops_per_image(model, hw)
     tflops = flops_img * bs * steps / dt / 1e12   # per GPU
     # N = 1: what the gradient exchange costs the step when it runs beside the backward -- the same bucket / side-stream / event machinery as
     # N ranks on a ONE-rank RCCL communicator (the collective itself moves no bytes over xGMI at one rank: this prices the plumbing and shows
     # the side stream does not stall the compute stream; the wire time of N = 8 is modelled in DESIGN.md section 7)
     exchange = None
-    if world == 1 and not os.environ.get("Y3_NO_EXCHANGE_LEG"):
+    if args.full and world == 1 and not os.environ.get("Y3_NO_EXCHANGE_LEG"):
         try:
             parallel.init(force=True)
             model.grad_sync = parallel.GradBuckets(force=True)
@@ -218,36 +271,37 @@ def run_train(args, rank, world, dev, parallel, yo, batch, steps, warmup):
             exchange = {"error": f"{type(e).__name__}: {e}"[:300]}
         finally:
             model.grad_sync = None
-    # kernel families of ONE more step, measured here: HIP events around every C-ABI call of the step on the stream it runs on (_lib.CallTimer), after the timed steps
+    # --full: kernel families of ONE more step, measured here: HIP events around every C-ABI call of the step on the stream it runs on (_lib.CallTimer), after the timed steps
     groups, timed_step_ms = None, None
     from yolov3_amd import _lib as y3lib
 
     side_streams = []
-    try:   # (every rank runs the extra step -- it contains the gradient collectives -- rank 0's record is the one reported)
-        # the instrumented step runs on ONE stream: with the filter gradients on their side stream (the default since round 6) two full-chip kernels are time-sliced and
-        # every call's event pair would measure the other stream's kernels too (the families then sum to more than the step)
-        from yolov3_amd.engine import plan_cache
+    if args.full:
+        try:   # (every rank runs the extra step -- it contains the gradient collectives -- rank 0's record is the one reported)
+            # the instrumented step runs on ONE stream: with the filter gradients on their side stream (the default since round 6) two full-chip kernels are time-sliced and
+            # every call's event pair would measure the other stream's kernels too (the families then sum to more than the step)
+            from yolov3_amd.engine import plan_cache
 
-        for key, pl in plan_cache(model).plans.items():
-            if key[0] == "train" and getattr(pl, "wgrad_stream", None) is not None:
-                side_streams.append((pl, pl.wgrad_stream))
-                pl.wgrad_stream = None
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        with y3lib.CallTimer() as ct:
-            step()
-        e1.record()
-        by_fn = ct.by_function()
-        timed_step_ms = round(e0.elapsed_time(e1), 3)
-        groups = train_call_families(by_fn)
-        lib_ms = sum(g["ms_per_step"] for g in groups.values())
-        groups["outside the library (torch glue, gaps)"] = {"ms_per_step": round(timed_step_ms - lib_ms, 3), "calls_per_step": 0}
-    except Exception as e:  # noqa: BLE001
-        groups = {"error": f"{type(e).__name__}: {e}"[:300]}
-    finally:
-        for pl, st_ in side_streams:
-            pl.wgrad_stream = st_
+            for key, pl in plan_cache(model).plans.items():
+                if key[0] == "train" and getattr(pl, "wgrad_stream", None) is not None:
+                    side_streams.append((pl, pl.wgrad_stream))
+                    pl.wgrad_stream = None
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            with y3lib.CallTimer() as ct:
+                step()
+            e1.record()
+            by_fn = ct.by_function()
+            timed_step_ms = round(e0.elapsed_time(e1), 3)
+            groups = train_call_families(by_fn)
+            lib_ms = sum(g["ms_per_step"] for g in groups.values())
+            groups["outside the library (torch glue, gaps)"] = {"ms_per_step": round(timed_step_ms - lib_ms, 3), "calls_per_step": 0}
+        except Exception as e:  # noqa: BLE001
+            groups = {"error": f"{type(e).__name__}: {e}"[:300]}
+        finally:
+            for pl, st_ in side_streams:
+                pl.wgrad_stream = st_
     parallel.barrier()
     rec = {
         "metric": "images/sec (640x640) train step", "value": round(world * bs * steps / dt, 2), "unit": "images/sec", "n_gpus": world,
@@ -269,7 +323,7 @@ def run_train(args, rank, world, dev, parallel, yo, batch, steps, warmup):
 
 
 def train_main(args, rank, local_rank, world, dev, parallel, yo, print_record):
-    rec = run_train(args, rank, world, dev, parallel, yo, args.batch, args.steps, args.warmup)
+    rec = run_train(args, rank, world, dev, parallel, yo, args.batch, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if rank == 0:
         print_record(rec)
     parallel.finalize()
@@ -425,18 +479,22 @@ def main():
     ap.add_argument("--model", default="yolov3")
     ap.add_argument("--nc", type=int, default=80, help="classes (365 = the Objects365 head of BASELINE configs[4])")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-layers", action="store_true", help="print the per-launch table (rank 0)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every other measurement (see the module docstring); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--profile-layers", action="store_true", help="--full: print the per-launch table (rank 0)")
     ap.add_argument("--no-overlap", action="store_true", help="sequential forward -> NMS per step (no second stream)")
     ap.add_argument("--mode", default="infer", choices=["infer", "train"], help="train = BASELINE configs[2] per-GPU shape (data-parallel train step)")
-    ap.add_argument("--no-clocks", action="store_true", help="skip the rocm-smi clock / power sampling leg (after the timed region)")
-    ap.add_argument("--no-train", action="store_true", help="infer mode: skip the appended train-step leg (BASELINE metric part ii, batch 64, after the timed inference region)")
+    ap.add_argument("--no-clocks", action="store_true", help="--full: skip the rocm-smi clock / power sampling leg (after the timed region)")
+    ap.add_argument("--no-train", action="store_true", help="--full, infer mode: skip the appended train-step leg (BASELINE metric part ii, batch 64, after the timed inference region)")
     ap.add_argument("--train-batch", type=int, default=64)
     ap.add_argument("--train-steps", type=int, default=6)
     ap.add_argument("--train-timeout", type=float, default=240.0, help="N > 1: seconds the appended train leg may take before the inference line is printed without it")
     ap.add_argument("--dist-backend", default=None, choices=["nccl", "gloo"],
                     help="process-group backend (default nccl = RCCL; gloo: plumbing smoke with several ranks on fewer GPUs, tools/gpu_dist_smoke.sh)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` on its own (no torch.distributed.run around it): become the launcher -- one rank per GPU on this node, rendezvous on
     # 127.0.0.1 (the reference's train.py:672-683 is launched the same way).  The ranks' stdout is ours: rank 0's single JSON line passes through.
@@ -481,7 +539,7 @@ def main():
     x = torch.rand(bs, 3, hw, hw, generator=torch.Generator().manual_seed(rank)).to(dev).to(dtype)
     calib = calibrate_detect_head(model, x)   # the head's own output becomes the NMS load of SURVEY 8(d); before every timed region
     n_rows = sum(3 * (hw // s) ** 2 for s in (8, 16, 32)) if args.model != "yolov3-tiny" else sum(3 * (hw // s) ** 2 for s in (16, 32))
-    pred_synth = yo.synth_predictions(bs=bs, n_rows=n_rows, nc=args.nc, seed=2 + rank, img=hw).to(dev).to(dtype)
+    pred_synth = yo.synth_predictions(bs=bs, n_rows=n_rows, nc=args.nc, seed=2 + rank, img=hw).to(dev).to(dtype) if args.full else None   # --full legs only
     nms_kw = dict(conf_thres=0.001, iou_thres=0.6, multi_label=True, max_det=300)
 
     def step(synthetic=False):
@@ -533,8 +591,32 @@ def main():
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, dev)
     group = parallel.describe(dev)   # (collective: every rank calls it) who took part, as the communicator sees it
+    if args.dump_outputs and rank == 0:   # the last timed step's results, before anything else runs on the device
+        dump_outputs(args.dump_outputs, infer_outputs(pred, dets))
 
     if rank == 0:
+        out = {
+            "metric": "images/sec (640x640) inference+NMS",
+            "value": round(world * bs * args.steps / dt, 2),
+            "unit": "images/sec",
+            "n_gpus": world,
+            "process_group": group,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f16" if dtype == torch.float16 else "bf16",
+            "data": "synthetic (seeded uniform images; random-init weights with conditioned BN stats; Detect head calibrated to the NMS load of SURVEY 8d; NMS runs on the model's own output)",
+            "config": {
+                "workload": f"{args.model} inference {hw}x{hw} batch={bs}/GPU {args.dtype} nc={args.nc} + NMS(conf 0.001, iou 0.6, multi_label, max_det 300)" + (" [BASELINE configs[1]]" if (args.model, hw, bs, args.dtype, args.nc) == ("yolov3", 640, 32, "fp16", 80) else ""),
+                "global_batch": world * bs,
+                "parallelism": f"replicas x{world} (no data-path collective)",
+                "schedule": "sequential forward -> NMS(pred) per batch" if args.no_overlap else "NMS of batch i's predictions on a second HIP stream beside the forward of batch i+1 (every batch completes inside the timed region)",
+            },
+        }
+    if rank == 0 and args.full:
         # ---- leg split + per-kernel roofline (outside the timed region) ----
         def timed(fn, n=5):
             torch.cuda.synchronize()
@@ -660,7 +742,6 @@ def main():
             except Exception as e:  # noqa: BLE001
                 roofline["vendor_gemm_same_shape"] = {"error": f"{type(e).__name__}: {e}"[:200]}
         cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()   # rank 0 at N = 1 only
-        value = world * bs * args.steps / dt
         roofline["whole_step_frac"] = round(total_conv_flops / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS, 4)   # conv FLOPs of one step / wall time of one step / 2.5 PF
         clk = None if args.no_clocks else clocks_under_load(lambda: model(x))
         roofline["clocks_under_load"] = clk
@@ -676,26 +757,7 @@ def main():
             peak_at_clk = MFMA_PEAK_TFLOPS * clk["sclk_mhz_median"] / 2400.0
             roofline["peak_at_sustained_clock"] = round(peak_at_clk, 1)
             roofline["frac_of_peak_at_sustained_clock"] = round(fl / sec / 1e12 / peak_at_clk, 4)
-        out = {
-            "metric": "images/sec (640x640) inference+NMS",
-            "value": round(value, 2),
-            "unit": "images/sec",
-            "n_gpus": world,
-            "process_group": group,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f16" if dtype == torch.float16 else "bf16",
-            "data": "synthetic (seeded uniform images; random-init weights with conditioned BN stats; Detect head calibrated to the NMS load of SURVEY 8d; NMS runs on the model's own output)",
-            "config": {
-                "workload": f"{args.model} inference {hw}x{hw} batch={bs}/GPU {args.dtype} nc={args.nc} + NMS(conf 0.001, iou 0.6, multi_label, max_det 300)" + (" [BASELINE configs[1]]" if (args.model, hw, bs, args.dtype, args.nc) == ("yolov3", 640, 32, "fp16", 80) else ""),
-                "global_batch": world * bs,
-                "parallelism": f"replicas x{world} (no data-path collective)",
-                "schedule": "sequential forward -> NMS(pred) per batch" if args.no_overlap else "NMS of batch i's predictions on a second HIP stream beside the forward of batch i+1 (every batch completes inside the timed region)",
-            },
+        out.update({
             "sustained_images_per_sec": sustained["images_per_sec"] if sustained else None,
             "sustained": sustained,
             "sequential_images_per_sec_per_gpu": seq,
@@ -706,14 +768,14 @@ def main():
             "synthetic_nms_tensor": {"images_per_sec": synth_rate, "note": "same two-stream schedule, NMS leg on the seeded synthetic (bs, 25200, 85) tensor instead of the forward's output (rounds 1-4's headline form)"},
             "roofline": roofline,
             "cpu_baseline": cpu,
-        }
+        })
         try:   # the UNMODIFIED reference timed where it can run (the build container; /root/reference does not exist on the GPU box): committed record
             ref = json.load(open(ROOT / "profiles" / "r03_cpu_reference.json"))
             out["cpu_reference_recorded"] = {"kind": ref["kind"], "host": ref["host"], "inference": ref["inference"], "train_step": ref["train_step"],
                                              "source": "profiles/r03_cpu_reference.json (tools/cpu_reference.py, not measured in this run)"}
         except (OSError, ValueError, KeyError):
             pass
-    # BASELINE metric part (ii): the train step, measured in the same run AFTER the timed inference region.  At N > 1 it is the
+    # --full, BASELINE metric part (ii): the train step, measured in the same run AFTER the timed inference region.  At N > 1 it is the
     # data-parallel step of BASELINE configs[2] (batch 64 per GPU, RCCL gradient all-reduce overlapped with the backward; `value` = images/s
     # of the whole job), so the driver's N = 1, 2, 4, 8 runs carry the training scaling curve next to the inference replicas.  The
     # inference line must survive whatever happens in that leg: an exception is recorded in `train`, and a watchdog prints the line
@@ -725,7 +787,8 @@ def main():
     def emit(train):
         if rank == 0 and not state["printed"]:
             state["printed"] = True
-            out["train"] = train
+            if args.full:
+                out["train"] = train
             print_record(out)
 
     def on_timeout():
@@ -733,7 +796,7 @@ def main():
         os._exit(0)
 
     train, wd = None, None
-    if not args.no_train:
+    if args.full and not args.no_train:
         if world > 1:
             wd = threading.Timer(args.train_timeout, on_timeout)
             wd.daemon = True

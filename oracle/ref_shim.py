@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import contextlib
 import logging
+import os
 import sys
 import types
 from pathlib import Path
@@ -26,7 +27,11 @@ REFERENCE_ROOT = Path("/root/reference")
 
 
 def available() -> bool:
-    return (REFERENCE_ROOT / "models" / "yolo.py").exists()
+    """the reference tree is there and readable (a tree this user may not read counts as absent)"""
+    try:
+        return os.access(REFERENCE_ROOT / "models" / "yolo.py", os.R_OK)
+    except OSError:
+        return False
 
 
 class _Anything:

@@ -342,11 +342,109 @@ def gen_tta_goldens(ns):
     torch.save(out, OUT / "tta.pt")
 
 
+def _sparse(t: torch.Tensor) -> dict:
+    """a mostly-zero gradient as (shape, flat indices of its non-zeros, their values): the class / box channels are zero away from the matched cells"""
+    flat = t.reshape(-1)
+    idx = flat.nonzero().reshape(-1)
+    return {"shape": tuple(t.shape), "idx": idx.to(torch.int32), "val": flat[idx].clone()}
+
+
+def gen_cases_goldens(ns):
+    """The reference's outputs on the seeded cases of tests/test_oracle_vs_reference_live.py (wider than the files above: 120 val
+    matches, 60 letterbox geometries, 4 NMS regimes, 8 loss heads / hyp variants, 2 x 3 autobalance calls).  Inputs are regenerated from
+    the same seeds by the test; their checksums are stored."""
+    import importlib
+    import types
+
+    import utils.general as ref_general  # type: ignore
+    from utils.general import scale_boxes  # type: ignore
+
+    ref_val = importlib.import_module("val")
+    ref_general.time = types.SimpleNamespace(time=lambda: 0.0)   # the reference's NMS time limit (utils/general.py:675,746-748) must not cut a batch short
+    out = {"process_batch": [], "scale_boxes": [], "nms": [], "loss": [], "autobalance": []}
+
+    iouv = torch.linspace(0.5, 0.95, 10)
+    for seed in range(120):
+        det, lab = yo.synth_val_case(seed + 1000, n_lab=1 + seed % 29, n_det=20 + seed, nc=1 + seed % 6, dup=(seed % 3) / 2)
+        out["process_batch"].append({"det_sum": checksum(det), "lab_sum": checksum(lab), "want": ref_val.process_batch(det.clone(), lab.clone(), iouv)})
+
+    g = torch.Generator().manual_seed(0)
+    for i in range(60):
+        h0, w0 = int(torch.randint(120, 1400, (1,), generator=g)), int(torch.randint(120, 1400, (1,), generator=g))
+        s1 = (int(torch.randint(5, 21, (1,), generator=g)) * 32, int(torch.randint(5, 21, (1,), generator=g)) * 32)
+        boxes = yo.synth_scale_case(s1, seed=20 + i, n=64)
+        rp = None
+        if i % 2:
+            r = min(s1[0] / h0, s1[1] / w0)
+            rp = ((r, r), ((s1[1] - round(w0 * r)) / 2, (s1[0] - round(h0 * r)) / 2))
+        out["scale_boxes"].append({"s1": s1, "s0": (h0, w0), "ratio_pad": rp, "boxes_sum": checksum(boxes), "want": scale_boxes(s1, boxes.clone()[:, :4], (h0, w0), rp)})
+
+    for gk, nk in NMS_CASES:
+        pred = yo.synth_predictions(**gk)
+        out["nms"].append({"gen": gk, "nms": nk, "pred_sum": checksum(pred), "want": [d.clone() for d in ns.non_max_suppression(pred.clone(), **nk)]})
+
+    variants = [dict(), dict(fl_gamma=1.5), dict(label_smoothing=0.1, cls_pw=0.8, obj_pw=1.3)]
+    for i, (name, nc, hw, bs) in enumerate(LOSS_HEADS * 2):
+        layers, save, anchors, nc_v = yo.parse_cfg(yaml.safe_load(open(CFG / f"{name}.yaml")), 3, nc)
+        strides = yo.model_strides(layers)
+        sd = yo.seeded_state_dict(layers, nc_v, anchors, strides, seed=40 + i)
+        m = ns.DetectionModel(str(CFG / f"{name}.yaml"), ch=3, nc=nc)
+        m.load_state_dict(sd, strict=True)
+        hyp = dict(HYP, **variants[i % len(variants)])
+        nl = len(strides)
+        hyp["box"] *= 3 / nl
+        hyp["cls"] *= nc / 80 * 3 / nl
+        hyp["obj"] *= (hw / 640) ** 2 * 3 / nl
+        m.hyp = hyp
+        crit = ns.ComputeLoss(m)
+        crit.sort_obj_iou = sort_iou = i >= 4
+        shapes = [(bs, 3, hw // int(s), hw // int(s), nc + 5) for s in strides]
+        tg = yo.synth_targets(bs, nc, seed=70 + i)
+        if sort_iou:
+            tg = torch.cat((tg, tg[: max(1, tg.shape[0] // 3)] * torch.tensor([1, 1, 1, 1, 0.8, 1.25])))
+        p_ref = [t.requires_grad_(True) for t in yo.synth_raw_predictions(shapes, seed=50 + i)]
+        loss_ref, items_ref = crit(p_ref, tg)
+        loss_ref.backward()
+        out["loss"].append({"head": (name, nc, hw, bs), "hyp": hyp, "sort_obj_iou": sort_iou, "anchors": m.model[-1].anchors.clone(), "tg_sum": checksum(tg),
+                            "p_sum": sum(checksum(t.detach()) for t in p_ref), "loss": loss_ref.detach().clone(), "items": items_ref.detach().clone(),
+                            "grads": [_sparse(t.grad) for t in p_ref]})
+
+    for name, nc, hw, bs in LOSS_HEADS[:2]:
+        layers, save, anchors, nc_v = yo.parse_cfg(yaml.safe_load(open(CFG / f"{name}.yaml")), 3, nc)
+        strides = yo.model_strides(layers)
+        sd = yo.seeded_state_dict(layers, nc_v, anchors, strides, seed=7)
+        m = ns.DetectionModel(str(CFG / f"{name}.yaml"), ch=3, nc=nc)
+        m.load_state_dict(sd, strict=True)
+        m.hyp = dict(HYP)
+        crit = ns.ComputeLoss(m, autobalance=True)
+        balance0 = [float(b) for b in crit.balance]
+        shapes = [(bs, 3, hw // int(s), hw // int(s), nc + 5) for s in strides]
+        calls = []
+        for step in range(3):
+            tg = yo.synth_targets(bs, nc, seed=90 + step)
+            p = yo.synth_raw_predictions(shapes, seed=60 + step)
+            loss_ref, _ = crit([t.clone() for t in p], tg)
+            calls.append({"loss": loss_ref.detach().clone(), "balance": [float(b) for b in crit.balance]})
+        out["autobalance"].append({"head": (name, nc, hw, bs), "ssi": crit.ssi, "balance0": balance0,
+                                   "anchors": m.model[-1].anchors.clone(), "calls": calls})
+    torch.save(out, OUT / "reference_cases.pt")
+    print("reference_cases.pt", (OUT / "reference_cases.pt").stat().st_size)
+
+
+NMS_CASES = [
+    (dict(bs=2, n_rows=1800, nc=80, seed=101), dict(conf_thres=0.001, iou_thres=0.6, multi_label=True, max_det=300)),
+    (dict(bs=2, n_rows=1800, nc=80, seed=102), dict(conf_thres=0.25, iou_thres=0.45)),
+    (dict(bs=1, n_rows=1500, nc=20, seed=103, hits=0.1), dict(conf_thres=0.05, iou_thres=0.5, agnostic=True)),
+    (dict(bs=1, n_rows=1500, nc=8, seed=104, n_gt=30), dict(conf_thres=0.1, iou_thres=0.45, classes=[1, 4])),
+]
+LOSS_HEADS = [("yolov3", 80, 96, 2), ("yolov3-tiny", 20, 128, 3), ("yolov3", 5, 64, 4), ("yolov3-tiny", 80, 96, 2)]
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.set_num_threads(8)
     ns = ref_shim.load()
-    which = set(sys.argv[1:]) or {"model", "decode", "nms", "loss", "val_edge", "big", "ckpt", "metrics", "tta"}  # python make_golden.py [model decode nms loss val_edge big ckpt metrics tta]
+    which = set(sys.argv[1:]) or {"model", "decode", "nms", "loss", "val_edge", "big", "ckpt", "metrics", "tta", "cases"}  # python make_golden.py [model decode nms loss val_edge big ckpt metrics tta cases]
     if "model" in which:
         gen_model_goldens(ns)
     if "decode" in which:
@@ -365,4 +463,6 @@ if __name__ == "__main__":
         gen_ckpt_fixture(ns)
     if "tta" in which:
         gen_tta_goldens(ns)
+    if "cases" in which:
+        gen_cases_goldens(ns)
     print("golden files:", [(p.name, p.stat().st_size) for p in OUT.glob("*.pt")])

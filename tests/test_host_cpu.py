@@ -210,24 +210,17 @@ def test_gradient_buckets_reject_unknown_exchange():
 
 
 def test_reference_checkpoint_unpickles_into_hip_modules(tmp_path):
-    """a ``.pt`` written by the UNMODIFIED reference (pickled models.yolo.DetectionModel, as train.py:470-488 does)
-    loads through yolov3_amd.compat into MI355X-backed modules with identical parameters.  Needs /root/reference."""
-    from oracle import ref_shim
-
-    if not ref_shim.available():
-        pytest.skip("reference tree not present on this box")
-    ckpt = tmp_path / "ref_tiny.pt"
+    """a ``.pt`` written by the UNMODIFIED reference (pickled models.yolo.DetectionModel, as train.py:470-488 does: the committed
+    tests/golden/ref_tiny_w025_fp16.pt, make_golden.py ckpt) loads through yolov3_amd.compat into MI355X-backed modules with identical
+    parameters (the pickled tensors, read by a plain unpickle in another process)."""
+    ckpt = ROOT / "tests" / "golden" / "ref_tiny_w025_fp16.pt"
     writer = f"""
 import sys, torch
 sys.path.insert(0, {str(ROOT)!r})
-from oracle import ref_shim
-ns = ref_shim.load()
-m = ns.DetectionModel({str(ROOT / 'yolov3_amd' / 'cfg' / 'yolov3-tiny.yaml')!r}, ch=3, nc=80)
-for mod in m.modules():
-    if isinstance(mod, torch.nn.BatchNorm2d):
-        mod.running_mean.normal_(0, 0.1); mod.running_var.uniform_(0.5, 1.5)
-torch.save({{"epoch": 3, "model": m.half(), "ema": None, "optimizer": None}}, {str(ckpt)!r})
-torch.save(m.float().state_dict(), {str(tmp_path / 'sd.pt')!r})
+from yolov3_amd import compat
+assert compat.install_aliases() is True
+m = torch.load({str(ckpt)!r}, map_location="cpu", weights_only=False)["model"]
+torch.save({{k: v.clone() for k, v in m.state_dict().items()}}, {str(tmp_path / 'sd.pt')!r})
 """
     subprocess.check_call([sys.executable, "-c", writer], cwd=tmp_path)
     reader = f"""

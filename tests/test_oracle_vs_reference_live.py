@@ -1,31 +1,31 @@
-"""Where the reference tree is present (the build container), run the UNMODIFIED reference side by side with the oracle on
-fresh seeded inputs -- a wider pin than the committed golden files (which only hold a handful of cases).  Skipped on the GPU
-box (/root/reference does not exist there).  CPU only."""
-import importlib
-
+"""The oracle against the UNMODIFIED reference on more seeded cases than tests/test_oracle_golden.py holds -- a wider pin: 120 val
+matches, 60 letterbox geometries, 4 NMS regimes, 8 loss heads / hyp variants, 2 x 3 autobalance calls.  The reference's outputs on these
+cases are recorded in tests/golden/reference_cases.pt (tests/golden/make_golden.py cases); the inputs are regenerated here from the same
+seeds and checked against the recorded checksums.  CPU only."""
 import pytest
 import torch
+import yaml
+from pathlib import Path
 
-from oracle import ref_shim, yolo_oracle as yo
+from oracle import yolo_oracle as yo
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="/root/reference not present")
+CFG = Path(__file__).resolve().parents[1] / "yolov3_amd" / "cfg"
+
+
+def checksum(t):
+    return float(t.double().abs().sum())
+
+
+def dense(g):
+    """a gradient recorded as (shape, flat indices of its non-zeros, their values)"""
+    t = torch.zeros(g["shape"], dtype=g["val"].dtype).reshape(-1)
+    t[g["idx"].long()] = g["val"]
+    return t.reshape(g["shape"])
 
 
 @pytest.fixture(scope="module")
-def ref():
-    ns = ref_shim.load()
-    ns.val = importlib.import_module("val")
-    from utils.general import scale_boxes  # type: ignore
-
-    ns.scale_boxes = scale_boxes
-    # the reference's NMS drops the remaining images of a batch when its wall clock says it is slow (utils/general.py:675,746-748): on a cold or
-    # loaded host that made this comparison fail at random.  The side-by-side run sees a frozen clock; the reference's files are untouched.
-    import types
-
-    import utils.general as ref_general  # type: ignore
-
-    ref_general.time = types.SimpleNamespace(time=lambda: 0.0)
-    return ns
+def ref(golden_dir):
+    return torch.load(golden_dir / "reference_cases.pt")
 
 
 def test_process_batch_oracle_equals_reference_on_many_cases(ref):
@@ -33,9 +33,11 @@ def test_process_batch_oracle_equals_reference_on_many_cases(ref):
     detections, 1-6 classes, three duplicate regimes (several detections per label)."""
     iouv = torch.linspace(0.5, 0.95, 10)
     checked = 0
-    for seed in range(120):
+    assert len(ref["process_batch"]) == 120
+    for seed, rec in enumerate(ref["process_batch"]):
         det, lab = yo.synth_val_case(seed + 1000, n_lab=1 + seed % 29, n_det=20 + seed, nc=1 + seed % 6, dup=(seed % 3) / 2)
-        want = ref.val.process_batch(det.clone(), lab.clone(), iouv)
+        assert checksum(det) == rec["det_sum"] and checksum(lab) == rec["lab_sum"], f"input drift, seed {seed}"
+        want = rec["want"]
         got = yo.process_batch(det, lab, iouv)
         assert torch.equal(got, want), f"seed {seed}"
         checked += int(want.sum())
@@ -46,7 +48,8 @@ def test_scale_boxes_oracle_equals_reference_on_many_shapes(ref):
     """utils.general.scale_boxes (reference :613-626) == oracle.scale_boxes, bit-exact, over letterbox geometries derived the way
     val.py / detect.py derive them (ratio_pad None and the dataloader's (ratio, pad) form)."""
     g = torch.Generator().manual_seed(0)
-    for i in range(60):
+    assert len(ref["scale_boxes"]) == 60
+    for i, rec in enumerate(ref["scale_boxes"]):
         h0, w0 = int(torch.randint(120, 1400, (1,), generator=g)), int(torch.randint(120, 1400, (1,), generator=g))
         s1 = (int(torch.randint(5, 21, (1,), generator=g)) * 32, int(torch.randint(5, 21, (1,), generator=g)) * 32)
         boxes = yo.synth_scale_case(s1, seed=20 + i, n=64)
@@ -54,7 +57,8 @@ def test_scale_boxes_oracle_equals_reference_on_many_shapes(ref):
         if i % 2:
             r = min(s1[0] / h0, s1[1] / w0)
             rp = ((r, r), ((s1[1] - round(w0 * r)) / 2, (s1[0] - round(h0 * r)) / 2))
-        want = ref.scale_boxes(s1, boxes.clone()[:, :4], (h0, w0), rp)
+        assert (s1, (h0, w0), rp) == (tuple(rec["s1"]), tuple(rec["s0"]), rec["ratio_pad"]) and checksum(boxes) == rec["boxes_sum"], f"input drift, case {i}"
+        want = rec["want"]
         got = yo.scale_boxes(s1, boxes.clone()[:, :4], (h0, w0), rp)
         assert torch.equal(got, want), (i, s1, (h0, w0), rp)
 
@@ -68,9 +72,12 @@ def test_nms_oracle_equals_reference_on_fresh_seeds(ref):
         (dict(bs=1, n_rows=1500, nc=20, seed=103, hits=0.1), dict(conf_thres=0.05, iou_thres=0.5, agnostic=True)),
         (dict(bs=1, n_rows=1500, nc=8, seed=104, n_gt=30), dict(conf_thres=0.1, iou_thres=0.45, classes=[1, 4])),
     ]
-    for gk, nk in cases:
+    assert len(ref["nms"]) == len(cases)
+    for (gk, nk), rec in zip(cases, ref["nms"]):
+        assert (gk, nk) == (rec["gen"], rec["nms"])
         pred = yo.synth_predictions(**gk)
-        want = ref.non_max_suppression(pred.clone(), **nk)
+        assert checksum(pred) == rec["pred_sum"], f"input drift, {gk}"
+        want = rec["want"]
         got = yo.non_max_suppression(pred, **nk)
         assert len(got) == len(want)
         for a, b in zip(got, want):
@@ -80,69 +87,59 @@ def test_nms_oracle_equals_reference_on_fresh_seeds(ref):
 def test_compute_loss_oracle_equals_reference_on_fresh_targets(ref):
     """ComputeLoss (reference utils/loss.py:98-244) == oracle.compute_loss -- value, items and d loss / d predictions -- on target
     sets the golden file does not hold: 8 seeds, focal / label-smoothing / pos_weight variants, yolov3 and yolov3-tiny heads, the last four with sort_obj_iou and duplicated cells."""
-    import yaml
-    from pathlib import Path
-
-    cfg = Path(__file__).resolve().parents[1] / "yolov3_amd" / "cfg"
     variants = [dict(), dict(fl_gamma=1.5), dict(label_smoothing=0.1, cls_pw=0.8, obj_pw=1.3)]
-    for i, (name, nc, hw, bs) in enumerate([("yolov3", 80, 96, 2), ("yolov3-tiny", 20, 128, 3), ("yolov3", 5, 64, 4), ("yolov3-tiny", 80, 96, 2)] * 2):
-        d = yaml.safe_load(open(cfg / f"{name}.yaml"))
+    heads = [("yolov3", 80, 96, 2), ("yolov3-tiny", 20, 128, 3), ("yolov3", 5, 64, 4), ("yolov3-tiny", 80, 96, 2)] * 2
+    assert len(ref["loss"]) == len(heads)
+    for i, ((name, nc, hw, bs), rec) in enumerate(zip(heads, ref["loss"])):
+        assert tuple(rec["head"]) == (name, nc, hw, bs)
+        d = yaml.safe_load(open(CFG / f"{name}.yaml"))
         layers, save, anchors, nc_v = yo.parse_cfg(d, 3, nc)
         strides = yo.model_strides(layers)
-        sd = yo.seeded_state_dict(layers, nc_v, anchors, strides, seed=40 + i)
-        m = ref.DetectionModel(str(cfg / f"{name}.yaml"), ch=3, nc=nc)
-        m.load_state_dict(sd, strict=True)
         hyp = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=4.0, fl_gamma=0.0, label_smoothing=0.0)
         hyp.update(variants[i % len(variants)])
         nl = len(strides)
         hyp["box"] *= 3 / nl
         hyp["cls"] *= nc / 80 * 3 / nl
         hyp["obj"] *= (hw / 640) ** 2 * 3 / nl
-        m.hyp = hyp
-        crit = ref.ComputeLoss(m)
-        crit.sort_obj_iou = sort_iou = i >= 4   # the second pass over the four heads: ComputeLoss.sort_obj_iou (utils/loss.py:101,156-158)
+        assert hyp == rec["hyp"], i
+        sort_iou = i >= 4   # the second pass over the four heads: ComputeLoss.sort_obj_iou (utils/loss.py:101,156-158)
+        assert sort_iou == rec["sort_obj_iou"]
         shapes = [(bs, 3, hw // int(s), hw // int(s), nc + 5) for s in strides]
         tg = yo.synth_targets(bs, nc, seed=70 + i)
         if sort_iou:   # duplicate cells with different boxes, so that the order of the writes matters
             tg = torch.cat((tg, tg[: max(1, tg.shape[0] // 3)] * torch.tensor([1, 1, 1, 1, 0.8, 1.25])))
-        p_ref = [t.requires_grad_(True) for t in yo.synth_raw_predictions(shapes, seed=50 + i)]
-        loss_ref, items_ref = crit(p_ref, tg)
-        loss_ref.backward()
+        assert checksum(tg) == rec["tg_sum"], f"input drift, head {i}"
         p = [t.requires_grad_(True) for t in yo.synth_raw_predictions(shapes, seed=50 + i)]
-        loss, items, _ = yo.compute_loss(p, tg, m.model[-1].anchors.clone(), hyp, nc, sort_obj_iou=sort_iou)
+        assert sum(checksum(t.detach()) for t in p) == rec["p_sum"], f"input drift, head {i}"
+        loss, items, _ = yo.compute_loss(p, tg, rec["anchors"].clone(), hyp, nc, sort_obj_iou=sort_iou)
         loss.backward()
-        torch.testing.assert_close(loss, loss_ref.detach(), rtol=1e-6, atol=1e-6)
-        torch.testing.assert_close(items, items_ref, rtol=1e-6, atol=1e-6)
-        for a, b in zip(p, p_ref):
-            torch.testing.assert_close(a.grad, b.grad, rtol=1e-5, atol=1e-8)
+        torch.testing.assert_close(loss, rec["loss"], rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(items, rec["items"], rtol=1e-6, atol=1e-6)
+        assert len(p) == len(rec["grads"])
+        for a, b in zip(p, rec["grads"]):
+            torch.testing.assert_close(a.grad, dense(b), rtol=1e-5, atol=1e-8)
 
 
 def test_autobalance_oracle_equals_reference_over_consecutive_calls(ref):
     """ComputeLoss(autobalance=True) (reference utils/loss.py:121, :171-175): the per-level objectness weights after three consecutive calls,
     and every call's loss, from the unmodified reference and from oracle.compute_loss(balance=..., autobalance_ssi=...)."""
-    import yaml
-    from pathlib import Path
-
-    cfg = Path(__file__).resolve().parents[1] / "yolov3_amd" / "cfg"
-    for name, nc, hw, bs in [("yolov3", 80, 96, 2), ("yolov3-tiny", 20, 128, 3)]:
-        d = yaml.safe_load(open(cfg / f"{name}.yaml"))
+    heads = [("yolov3", 80, 96, 2), ("yolov3-tiny", 20, 128, 3)]
+    assert len(ref["autobalance"]) == len(heads)
+    for (name, nc, hw, bs), rec in zip(heads, ref["autobalance"]):
+        assert tuple(rec["head"]) == (name, nc, hw, bs)
+        d = yaml.safe_load(open(CFG / f"{name}.yaml"))
         layers, save, anchors, nc_v = yo.parse_cfg(d, 3, nc)
         strides = yo.model_strides(layers)
-        sd = yo.seeded_state_dict(layers, nc_v, anchors, strides, seed=7)
-        m = ref.DetectionModel(str(cfg / f"{name}.yaml"), ch=3, nc=nc)
-        m.load_state_dict(sd, strict=True)
         hyp = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=4.0, fl_gamma=0.0, label_smoothing=0.0)
-        m.hyp = hyp
-        crit = ref.ComputeLoss(m, autobalance=True)
         ssi = [int(s) for s in strides].index(16)
-        assert crit.ssi == ssi
-        balance = list(crit.balance)
+        assert rec["ssi"] == ssi
+        balance = list(rec["balance0"])
         shapes = [(bs, 3, hw // int(s), hw // int(s), nc + 5) for s in strides]
-        for step in range(3):
+        assert len(rec["calls"]) == 3
+        for step, call in enumerate(rec["calls"]):
             tg = yo.synth_targets(bs, nc, seed=90 + step)
             p = yo.synth_raw_predictions(shapes, seed=60 + step)
-            loss_ref, _ = crit([t.clone() for t in p], tg)
-            loss, _, _ = yo.compute_loss(p, tg, m.model[-1].anchors.clone(), hyp, nc, balance=balance, autobalance_ssi=ssi)
-            torch.testing.assert_close(loss, loss_ref.detach(), rtol=1e-6, atol=1e-6)
-            torch.testing.assert_close(torch.tensor(balance), torch.tensor([float(b) for b in crit.balance]), rtol=1e-6, atol=1e-7)
+            loss, _, _ = yo.compute_loss(p, tg, rec["anchors"].clone(), hyp, nc, balance=balance, autobalance_ssi=ssi)
+            torch.testing.assert_close(loss, call["loss"], rtol=1e-6, atol=1e-6)
+            torch.testing.assert_close(torch.tensor(balance), torch.tensor(call["balance"]), rtol=1e-6, atol=1e-7)
         assert abs(balance[ssi] - 1.0) < 1e-9 and balance != [4.0, 1.0, 0.4][: len(balance)]
