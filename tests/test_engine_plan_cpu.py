@@ -103,26 +103,44 @@ def test_fuse_matches_unfused_plan_weights(monkeypatch):
             torch.testing.assert_close(a["w"].folded[1], b["w"].folded[1], rtol=1e-6, atol=1e-6)
 
 
-def test_stem_pair_eligibility(monkeypatch):
+def test_stem_pair_eligibility_on_graph(monkeypatch):
     """Layers 0 + 1 are fused only for the Conv(<=4, 32, 3, 1) -> Conv(32, 64, 3, 2) opening of yolov3 / yolov3-spp with layer 0
     consumed by layer 1 alone; yolov3-tiny (Conv(3, 16) + MaxPool) keeps the stem kernel; Y3_STEM_PAIR=0 switches it off."""
     from yolov3_amd import DetectionModel
     from yolov3_amd import engine as e
 
     def eligible(name):
-        m = DetectionModel(f"{name}.yaml").eval()
-        layers = list(m.model)
-        src = [e._sources(i, l.f) for i, l in enumerate(layers)]
-        consumers = {i: [] for i in range(-1, len(layers))}
-        for i, s in enumerate(src):
-            for j in s:
-                consumers[j].append(i)
-        return e._stem_pair_eligible(layers, src, consumers, {}, {})
+        return e._stem_pair_eligible(e.Graph(DetectionModel(f"{name}.yaml").eval(), 64, 64), {}, {})
 
     monkeypatch.delenv("Y3_STEM_PAIR", raising=False)
     assert eligible("yolov3") and eligible("yolov3-spp") and not eligible("yolov3-tiny")
     monkeypatch.setenv("Y3_STEM_PAIR", "0")
     assert not eligible("yolov3")
+
+
+def test_graph_description_of_yolov3_640():
+    """engine.Graph, the analysis both planners build their buffers from, for yolov3 at 640 x 640: channels (-1 = the image, padded to 8),
+    sizes, the two zero-copy Concats, no ZeroPad2d; yolov3-tiny's ZeroPad2d folds into the MaxPool2d behind it"""
+    g = engine.Graph(DetectionModel("yolov3.yaml").eval(), 640, 640)
+    assert g.ch == {-1: 8, 0: 32, 1: 64, 2: 64, 3: 128, 4: 128, 5: 256, 6: 256, 7: 512, 8: 512, 9: 1024, 10: 1024, 11: 1024, 12: 512, 13: 1024, 14: 512,
+                    15: 1024, 16: 256, 17: 256, 18: 768, 19: 512, 20: 512, 21: 256, 22: 512, 23: 128, 24: 128, 25: 384, 26: 256, 27: 256}
+    assert g.hw == [(640, 640), (320, 320), (320, 320), (160, 160), (160, 160), (80, 80), (80, 80), (40, 40), (40, 40)] + [(20, 20)] * 8 + [(40, 40)] * 7 + [(80, 80)] * 5
+    assert g.concat == {18: [(17, 0, 256, True), (8, 256, 512, True)], 25: [(24, 0, 128, True), (6, 128, 256, True)]}
+    assert g.pad == {} and g.src[28] == [27, 22, 15] and g.consumers[-1] == [0] and g.consumers[14] == [15, 16]
+    assert engine.Graph(DetectionModel("yolov3-tiny.yaml").eval(), 96, 128).pad == {11: (12, 1, 1)}
+
+
+def test_zeropad_not_in_front_of_a_maxpool_is_refused():
+    """A ZeroPad2d is folded into the MaxPool2d behind it; one that feeds anything else is refused by both planners, not dropped"""
+    from yolov3_amd.train_engine import TrainPlan, TrainSlot
+
+    d = yaml.safe_load(open(CFG / "yolov3-tiny.yaml"))
+    d["backbone"][12] = [-1, 1, "Conv", [512, 1, 1]]
+    cpu = torch.device("cpu")
+    with pytest.raises(NotImplementedError, match="ZeroPad2d is only supported directly in front of a MaxPool2d"):
+        engine.compile_model(DetectionModel(d).eval(), 1, 64, 64, torch.float32, cpu)
+    with pytest.raises(NotImplementedError, match="ZeroPad2d is only supported directly in front of a MaxPool2d"):
+        TrainPlan.build(DetectionModel(d).train(), 1, 64, 64, torch.float16, cpu, TrainSlot(torch.float16, cpu))
 
 
 def test_bneck_pair_eligibility(monkeypatch):

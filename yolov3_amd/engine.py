@@ -32,7 +32,7 @@ from ._lib import Y3ConvDesc, Y3Tensor
 from .common import SPP, Bottleneck, Concat, Conv, MaxPool2d, Upsample, ZeroPad2d
 
 
-# ------------------------------------------------------------------------------------------- shape bookkeeping
+# ------------------------------------------------------------------------------------------- shape bookkeeping, graph analysis
 def _conv_hw(hw, k, s):
     p = k // 2
     return tuple((v + 2 * p - k) // s + 1 for v in hw)
@@ -74,6 +74,58 @@ def _out_channels(m):
     if isinstance(mm, SPP):
         return mm.cv2.conv.out_channels
     return None
+
+
+class Graph:
+    """What the inference and the training planner both read off `model.model` for an (h, w) input: no buffers, no device.
+
+    * ``src[i]``: the layers layer i reads (-1 = the image); ``consumers[j]``: the layers that read j (``consumers[-1]``: the image's);
+    * ``hw[i]`` (graph_hw) and ``ch[i]``: output size and channels of every layer but Detect; ``ch[-1]`` is the image's, padded to 8;
+    * ``concat[i]``: the sources of Concat i as (j, channel offset, channels, zero_copy).  A zero-copy source is written straight into its
+      slice of the Concat's buffer; the others (the image, a tensor an earlier Concat already holds, a slice not aligned to 8 channels) are copied;
+    * ``pad[i]``: ZeroPad2d i -> (the MaxPool2d it feeds, right, bottom): the pad is folded into the pool launch."""
+
+    def __init__(self, model, h, w):
+        from .yolo import Detect
+
+        self.layers = list(model.model)
+        self.src = [_sources(i, m.f) for i, m in enumerate(self.layers)]
+        self.consumers = {i: [] for i in range(-1, len(self.layers))}
+        for i, s in enumerate(self.src):
+            for j in s:
+                self.consumers[j].append(i)
+        self.hw = graph_hw(model, h, w)
+        self.ch = {-1: _pad8(model.yaml.get("ch", 3))}
+        self.concat, self.pad = {}, {}
+        claimed = set()   # layers whose output already lives in a Concat's buffer (first claim wins, in layer order)
+        for i, m in enumerate(self.layers):
+            k, src = self.kind(i), self.src[i]
+            if isinstance(k, Detect):
+                continue
+            oc = _out_channels(m)
+            if oc is None:   # Concat: the sum of its sources; Upsample / MaxPool2d / ZeroPad2d: the width of their input
+                oc = sum(self.ch[j] for j in src) if isinstance(k, Concat) else self.ch[src[0]]
+            self.ch[i] = oc
+            if isinstance(k, Concat):
+                claimed.add(i)
+                self.concat[i], off = [], 0
+                for j in src:
+                    c = self.ch[j]
+                    zero_copy = not (j in claimed or j < 0 or c % 8 or off % 8)
+                    if zero_copy:
+                        claimed.add(j)
+                    self.concat[i].append((j, off, c, zero_copy))
+                    off += c
+            elif isinstance(k, ZeroPad2d):
+                cons = self.consumers[i]
+                if len(cons) != 1 or not isinstance(self.kind(cons[0]), MaxPool2d):
+                    raise NotImplementedError("ZeroPad2d is only supported directly in front of a MaxPool2d (yolov3-tiny)")
+                self.pad[i] = (cons[0], k.padding[1], k.padding[3])
+
+    def kind(self, i):
+        """the module of layer i (the first of an nn.Sequential of repeats)"""
+        m = self.layers[i]
+        return m[0] if isinstance(m, nn.Sequential) else m
 
 
 # ------------------------------------------------------------------------------------------- symbolic buffers
@@ -433,26 +485,28 @@ def _bneck_pair_eligible(m, x, dtype) -> bool:
             and isinstance(m.cv1.act, (nn.SiLU, nn.Identity)) and isinstance(m.cv2.act, (nn.SiLU, nn.Identity)))
 
 
-def _stem_eligible(m, dtype, srcs, input_consumers) -> bool:
+def _stem_eligible(g: Graph, dtype) -> bool:
     """Layer 0 = Conv(ch <= 4, <= 64 filters, 3, 1) fed by the image alone: csrc/stem.hip computes it straight from the
     caller's NCHW tensor (no NHWC copy of the image).  Y3_STEM=0 restores ingest + generic conv (A/B runs)."""
     import os
 
-    c = m.conv
-    return (os.environ.get("Y3_STEM", "1") != "0" and dtype in (torch.float16, torch.bfloat16) and list(srcs) == [-1] and list(input_consumers) == [0]
+    if not isinstance(g.layers[0], Conv):
+        return False
+    c = g.layers[0].conv
+    return (os.environ.get("Y3_STEM", "1") != "0" and dtype in (torch.float16, torch.bfloat16) and g.src[0] == [-1] and g.consumers[-1] == [0]
             and c.in_channels <= 4 and c.out_channels <= 64 and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1)
             and c.dilation == (1, 1) and c.groups == 1)
 
 
-def _stem_pair_eligible(layers, src, consumers, placed, fused_ups) -> bool:
+def _stem_pair_eligible(g: Graph, placed, fused_ups) -> bool:
     """Layers 0 and 1 = Conv(<=4, 32, 3, 1) -> Conv(32, 64, 3, 2), layer 0 consumed by layer 1 alone: csrc/stem.hip computes both
     with layer 0's output kept in LDS.  Y3_STEM_PAIR=0 restores stem + generic conv (A/B runs)."""
     import os
 
-    if os.environ.get("Y3_STEM_PAIR", "1") == "0" or len(layers) < 2:
+    if os.environ.get("Y3_STEM_PAIR", "1") == "0" or len(g.layers) < 2:
         return False
-    m0, m1 = layers[0], layers[1]
-    if not (isinstance(m0, Conv) and isinstance(m1, Conv)) or list(src[1]) != [0] or list(consumers[0]) != [1] or 0 in placed or 1 in fused_ups or 0 in fused_ups:
+    m0, m1 = g.layers[0], g.layers[1]
+    if not (isinstance(m0, Conv) and isinstance(m1, Conv)) or g.src[1] != [0] or g.consumers[0] != [1] or 0 in placed or 1 in fused_ups or 0 in fused_ups:
         return False
     c0, c1 = m0.conv, m1.conv
     return (c0.out_channels == 32 and c1.in_channels == 32 and c1.out_channels == 64 and c1.kernel_size == (3, 3) and c1.stride == (2, 2) and c1.padding == (1, 1)
@@ -464,81 +518,35 @@ def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
 
     plan = Plan(device, dtype, n, h, w)
     comp = _Compiler(plan, dtype, training=model.training, wcache=wcache)
-    layers = list(model.model)
-    nl = len(layers)
-    hw = graph_hw(model, h, w)
-    src = [_sources(i, m.f) for i, m in enumerate(layers)]
-    consumers = {i: [] for i in range(-1, nl)}
-    for i, s in enumerate(src):
-        for j in s:
-            consumers[j].append(i)
+    g = Graph(model, h, w)
+    layers = g.layers
 
-    def kind(m):
-        return m[0] if isinstance(m, nn.Sequential) else m
-
-    ch = {}
-    cin0 = _pad8(model.yaml.get("ch", 3))
-    for i, m in enumerate(layers):
-        k = kind(m)
-        oc = _out_channels(m)
-        if oc is None:
-            if isinstance(k, Concat):
-                oc = sum(ch[j] for j in src[i])
-            elif isinstance(k, Detect):
-                oc = 0
-            else:
-                oc = ch[src[i][0]] if src[i][0] >= 0 else cin0
-        ch[i] = oc
-
-    # ---- placement: where each layer's output lives (Concat destinations claim their sources) ----
+    # ---- placement: where each layer's output lives (Concat destinations hold their zero-copy sources) ----
     placed: dict[int, SView] = {}
-    extra_copy = []  # (src layer, destination view) when a tensor feeds a second Concat
-    for i, m in enumerate(layers):
-        if isinstance(kind(m), Concat):
-            ctot = ch[i]
-            cbuf = placed.get(i) or plan.new_view(n, hw[i][0], hw[i][1], ctot, f"L{i}.concat")
-            placed[i] = cbuf
-            off = 0
-            for j in src[i]:
-                sl = cbuf.slice(off, ch[j])
-                if j in placed or j < 0 or (ch[j] % 8) or (off % 8):
-                    extra_copy.append((j, i, sl))
-                else:
-                    placed[j] = sl
-                off += ch[j]
+    for i, srcs in g.concat.items():
+        placed[i] = plan.new_view(n, g.hw[i][0], g.hw[i][1], g.ch[i], f"L{i}.concat")
+        for j, off, c, zero_copy in srcs:
+            if zero_copy:
+                placed[j] = placed[i].slice(off, c)
 
     # Upsample fed by a single-consumer Conv: the conv scatters straight into the upsample's home
     fused_ups = {}
-    for i, m in enumerate(layers):
-        if isinstance(kind(m), Upsample):
-            j = src[i][0]
-            if j >= 0 and isinstance(layers[j], Conv) and consumers[j] == [i] and j not in placed:
+    for i in range(len(layers)):
+        if isinstance(g.kind(i), Upsample):
+            j = g.src[i][0]
+            if j >= 0 and isinstance(layers[j], Conv) and g.consumers[j] == [i] and j not in placed:
                 fused_ups[j] = i
-    # ZeroPad2d consumed only by a MaxPool2d: folded into the pool launch
-    fused_pad = {}
-    for i, m in enumerate(layers):
-        if isinstance(kind(m), ZeroPad2d):
-            cons = consumers[i]
-            if len(cons) == 1 and isinstance(kind(layers[cons[0]]), MaxPool2d) and i not in placed:
-                fused_pad[i] = cons[0]
-            else:
-                raise NotImplementedError("ZeroPad2d is only supported directly in front of a MaxPool2d (yolov3-tiny)")
 
-    def home(i):
-        if i not in placed:
-            placed[i] = plan.new_view(n, hw[i][0], hw[i][1], ch[i], f"L{i}")
-        return placed[i]
-
-    x_in = plan.new_view(n, h, w, cin0, "input")
+    x_in = plan.new_view(n, h, w, g.ch[-1], "input")
     x_in.buf.pinned = True
     plan.input_view = x_in
     out = {-1: x_in}
 
     pair = None   # layer-0 weights while layers 0 + 1 are emitted as one stem_pair launch
-    pair_ok = not model.training and _stem_pair_eligible(layers, src, consumers, placed, fused_ups)   # before home() claims a buffer for layer 0
+    pair_ok = not model.training and _stem_pair_eligible(g, placed, fused_ups)   # before layer 0's own buffer enters `placed`
     for i, m in enumerate(layers):
-        k = kind(m)
-        ins = [out[j] for j in src[i]]
+        k = g.kind(i)
+        ins = [out[j] for j in g.src[i]]
         lab = f"L{i}"
         if isinstance(k, Detect):
             heads = []
@@ -552,40 +560,33 @@ def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
             plan.detect = (k, heads)
             continue
         if isinstance(k, Concat):
-            for (j, ci, sl) in extra_copy:
-                if ci == i:
+            for j, off, c, zero_copy in g.concat[i]:
+                if not zero_copy:
+                    sl = placed[i].slice(off, c)
                     plan.add("copy", [out[j]], [sl], x=out[j], y=sl, label=f"{lab}.copy{j}")
             out[i] = placed[i]
-            continue
-        if isinstance(k, Upsample):
-            j = src[i][0]
-            if j in fused_ups:
-                out[i] = home(i)  # already written by the producing conv
-            else:
-                y = home(i)
-                plan.add("upsample", [ins[0]], [y], x=ins[0], y=y, label=lab)
-                out[i] = y
             continue
         if isinstance(k, ZeroPad2d):
             out[i] = ins[0]  # folded into the following pool
             continue
-        if isinstance(k, MaxPool2d):
-            j = src[i][0]
-            zr = zb = 0
-            if j in fused_pad:
-                zr, zb = kind(layers[j]).padding[1], kind(layers[j]).padding[3]
-            y = home(i)
+        if isinstance(k, Upsample) and g.src[i][0] in fused_ups:
+            continue   # out[i] was written by the producing conv
+        d = fused_ups.get(i, i)   # (a conv fused with its upsample writes the upsample's output)
+        if d not in placed:
+            placed[d] = plan.new_view(n, g.hw[d][0], g.hw[d][1], g.ch[d], f"L{d}")
+        y = placed[d]
+        if i in fused_ups:
+            comp.conv_unit(k, ins[0], y=y, ups=True, label=lab, cin_pad=ins[0].c)
+            out[i], out[d] = None, y
+        elif isinstance(k, Upsample):
+            plan.add("upsample", [ins[0]], [y], x=ins[0], y=y, label=lab)
+            out[i] = y
+        elif isinstance(k, MaxPool2d):
+            j = g.src[i][0]
+            zr, zb = g.pad[j][1:] if j in g.pad else (0, 0)
             plan.add("maxpool", [ins[0]], [y], x=ins[0], y=y, k=k.kernel_size, s=k.stride, p=k.padding, zr=zr, zb=zb, label=lab)
             out[i] = y
-            continue
-        # conv-type layers
-        if i in fused_ups:
-            dst = home(fused_ups[i])
-            comp.conv_unit(k, ins[0], y=dst, ups=True, label=lab, cin_pad=ins[0].c)
-            out[i] = None
-            continue
-        y = home(i)
-        if isinstance(m, nn.Sequential):
+        elif isinstance(m, nn.Sequential):
             x = ins[0]
             for r, sub in enumerate(m):
                 last = r == len(m) - 1
@@ -596,7 +597,7 @@ def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
             w1 = make_conv_weights(k.conv, getattr(k, "bn", None), isinstance(k.act, nn.SiLU), dtype, cin_pad=32, cache=wcache)
             plan.add("stem_pair", [], [y], w0=w0, w1=w1, y=y, cin=w0.cin, h=h, w=w, label="L0+L1")
             out[i] = y
-        elif isinstance(k, Conv) and i == 0 and _stem_eligible(k, dtype, src[0], consumers[-1]):
+        elif i == 0 and _stem_eligible(g, dtype):
             skey = ("stem", id(k.conv), id(getattr(k, "bn", None)), dtype)
             wts = wcache.get(skey) if wcache is not None else None
             if wts is None:

@@ -24,7 +24,7 @@ from torch import nn
 from . import _lib, ops
 from ._lib import Y3Tensor, check
 from .common import SPP, Bottleneck, Concat, Conv, MaxPool2d, Upsample, ZeroPad2d
-from .engine import _pad8, _sources, graph_hw
+from .engine import Graph, _pad8, _stem_eligible
 from .ops import View
 
 
@@ -162,6 +162,22 @@ class ConvUnit(_Unit):
             "y3_bn_finalize_devcount",
         )
 
+    def _stats_from_rows(self, buf, n_rows):
+        """BatchNorm statistics from the `n_rows` per-block (sum, sum of squares) rows in `buf`: summed and exchanged across a SyncBatchNorm group, else finalized here"""
+        L, st = _lib.lib(), ops.stream_ptr()
+        sync = self.sync_group()
+        if sync:
+            check(L.y3_bn_sum_rows(buf.data_ptr(), n_rows, self.cout, self.sums.data_ptr(), st), "y3_bn_sum_rows")
+            self._sync_forward_stats(sync)
+            return
+        bn = self.m.bn
+        check(
+            L.y3_bn_finalize_rows(buf.data_ptr(), n_rows, self.count, self.cout, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
+                                  float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
+                                  self.mean.data_ptr(), self.invstd.data_ptr(), st),
+            "y3_bn_finalize_rows",
+        )
+
     def generic_dgrad(self) -> bool:
         """the data gradient runs as ONE launch of the forward conv kernels on the flipped bank (not the stride-2 parity classes)"""
         return self.need_dx and not (self.s == 2 and self.k == 3 and self.plan.dtype != torch.float32)
@@ -188,7 +204,6 @@ class ConvUnit(_Unit):
         dcode = ops.dtype_code(self.plan.dtype)
         ut = self.u.y3()
         stats_in_epilogue = False
-        sync = self.sync_group()
         if self.use_stem and self.plan.x_nchw is not None:
             # layer 0 straight from the caller's NCHW image (csrc/stem.hip); the NHWC copy is still made for the filter gradient
             filt = ops.pack_filter_stem(m.conv.weight, self.cout, self.plan.dtype)
@@ -199,16 +214,7 @@ class ConvUnit(_Unit):
                 recompute = self.stem_recompute()
                 self.stem_filt = filt if recompute else None   # the backward multiplies with the same bank
                 n_rows = ops.stem_conv_stats_only(xi, filt, self.u, buf, rows) if recompute else ops.stem_conv_stats(xi, filt, self.zero_bias, self.u, buf, rows)
-                if sync:
-                    check(L.y3_bn_sum_rows(buf.data_ptr(), n_rows, self.cout, self.sums.data_ptr(), st), "y3_bn_sum_rows")
-                    self._sync_forward_stats(sync)
-                else:
-                    check(
-                        L.y3_bn_finalize_rows(buf.data_ptr(), n_rows, self.count, self.cout, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
-                                              float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
-                                              self.mean.data_ptr(), self.invstd.data_ptr(), st),
-                        "y3_bn_finalize_rows",
-                    )
+                self._stats_from_rows(buf, n_rows)
                 stats_in_epilogue = True
             else:
                 ops.stem_conv(self.plan.x_nchw, filt, self.zero_bias, self.u, act=False)
@@ -225,12 +231,7 @@ class ConvUnit(_Unit):
                 buf = self.plan.stat_buffer(self.bnin_rows * 2 * self.cout)
                 n_rows = ops.conv1x1_bnin_stats(pr.u, pr.scale, pr.shift, pr.act, pr.res.view if pr.res is not None else None, pr.y.view, filt, self.zero_bias, self.u, buf,
                                                 self.bnin_rows)
-                check(
-                    L.y3_bn_finalize_rows(buf.data_ptr(), n_rows, self.count, self.cout, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
-                                          float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
-                                          self.mean.data_ptr(), self.invstd.data_ptr(), st),
-                    "y3_bn_finalize_rows",
-                )
+                self._stats_from_rows(buf, n_rows)   # (_pair_bn_consumers pairs no SyncBatchNorm layer)
                 stats_in_epilogue = True
             elif self.plan.epilogue_stats:
                 # BatchNorm statistics taken in the conv epilogue (per-tile rows of sum / sum of squares): no separate pass over u
@@ -239,29 +240,22 @@ class ConvUnit(_Unit):
                     self.stat_rows = ops.conv2d_stats_rows(self.x.view, self.u, self.k, self.s, workspace=ws)
                 buf = self.plan.stat_buffer(self.stat_rows * 2 * self.cout)
                 n_rows = ops.conv2d_stats(self.x.view, filt, self.zero_bias, self.u, self.k, self.s, buf, self.stat_rows, workspace=ws)
-                if sync:
-                    check(L.y3_bn_sum_rows(buf.data_ptr(), n_rows, self.cout, self.sums.data_ptr(), st), "y3_bn_sum_rows")
-                    self._sync_forward_stats(sync)
-                else:
-                    check(
-                        L.y3_bn_finalize_rows(buf.data_ptr(), n_rows, self.count, self.cout, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps),
-                                              float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
-                                              self.mean.data_ptr(), self.invstd.data_ptr(), st),
-                        "y3_bn_finalize_rows",
-                    )
+                self._stats_from_rows(buf, n_rows)
                 stats_in_epilogue = True
             else:
                 ops.conv2d(self.x.view, filt, self.zero_bias, self.u, self.k, self.s, act=False, workspace=self.plan.conv_ws)
-        if not stats_in_epilogue and sync:
-            check(L.y3_bn_stats(C.byref(ut), dcode, self.sums.data_ptr(), st), "y3_bn_stats")
-            self._sync_forward_stats(sync)
-        elif not stats_in_epilogue:
-            check(
-                L.y3_bn_stats_finalize(C.byref(ut), dcode, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), float(bn.momentum),
-                                       bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(), self.mean.data_ptr(),
-                                       self.invstd.data_ptr(), st),
-                "y3_bn_stats_finalize",
-            )
+        if not stats_in_epilogue:
+            sync = self.sync_group()
+            if sync:
+                check(L.y3_bn_stats(C.byref(ut), dcode, self.sums.data_ptr(), st), "y3_bn_stats")
+                self._sync_forward_stats(sync)
+            else:
+                check(
+                    L.y3_bn_stats_finalize(C.byref(ut), dcode, self.sums.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), float(bn.momentum),
+                                           bn.running_mean.data_ptr(), bn.running_var.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(), self.mean.data_ptr(),
+                                           self.invstd.data_ptr(), st),
+                    "y3_bn_stats_finalize",
+                )
         if self.act_in_consumer:
             return   # y = act(scale u + shift) (+ shortcut) is computed and stored by the 1x1 consumer's launch (the next unit)
         if self.stem_filt is not None:
@@ -544,62 +538,29 @@ class TrainPlan:
         self.units: list[_Unit] = []
         self.heads: list[HeadUnit] = []
         self.acts: list[Act] = []
-        layers = list(model.model)
-        hw = graph_hw(model, h, w)
-        src = [_sources(i, m.f) for i, m in enumerate(layers)]
-
-        def kind(m):
-            return m[0] if isinstance(m, nn.Sequential) else m
-
-        def out_ch(i, m):
-            k = m[-1] if isinstance(m, nn.Sequential) else m
-            if isinstance(k, Conv):
-                return k.conv.out_channels
-            if isinstance(k, Bottleneck):
-                return k.cv2.conv.out_channels
-            if isinstance(k, Concat):
-                return sum(ch[j] for j in src[i])
-            if isinstance(k, SPP):
-                return k.cv2.conv.out_channels
-            return ch[src[i][0]]
-
-        ch = {}
-        for i, m in enumerate(layers):
-            if not isinstance(kind(m), Detect):
-                ch[i] = out_ch(i, m)
+        g = Graph(model, h, w)
         self._max_c = max(_pad8(mod.out_channels) for mod in model.modules() if isinstance(mod, nn.Conv2d))
 
-        def new_act(i_hw, c):
-            a = Act(self.alloc_view(n, i_hw[0], i_hw[1], c))
+        def new_act(i, c):   # a tensor of layer i's size
+            a = Act(self.alloc_view(n, g.hw[i][0], g.hw[i][1], c))
             self.acts.append(a)
             return a
 
         # placement: Concat sources live in slices of the Concat buffer (zero-copy, forward and backward)
         placed: dict[int, Act] = {}
-        for i, m in enumerate(layers):
-            if isinstance(kind(m), Concat):
-                cat = new_act(hw[i], ch[i])
-                placed[i] = cat
-                off = 0
-                for j in src[i]:
-                    if j in placed or (ch[j] % 8) or (off % 8):
-                        raise NotImplementedError("a tensor feeding two Concats / unaligned Concat offsets is not supported in training")
-                    placed[j] = cat.slice(off, ch[j])
-                    self.acts.append(placed[j])
-                    off += ch[j]
+        for i, srcs in g.concat.items():
+            placed[i] = new_act(i, g.ch[i])
+            for j, off, c, zero_copy in srcs:
+                if not zero_copy:
+                    raise NotImplementedError("a tensor feeding two Concats / unaligned Concat offsets is not supported in training")
+                placed[j] = placed[i].slice(off, c)
+                self.acts.append(placed[j])
 
-        def home(i):
-            if i not in placed:
-                placed[i] = new_act(hw[i], ch[i])
-            return placed[i]
-
-        cin0 = _pad8(model.yaml.get("ch", 3))
-        self.x_in = Act(self.alloc_view(n, h, w, cin0))
+        self.x_in = Act(self.alloc_view(n, h, w, g.ch[-1]))
         out: dict[int, Act] = {-1: self.x_in}
-        pad_of = {}
-        for i, m in enumerate(layers):
-            k = kind(m)
-            ins = [out[j] for j in src[i]]
+        for i, m in enumerate(g.layers):
+            k = g.kind(i)
+            ins = [out[j] for j in g.src[i]]
             if isinstance(k, Detect):
                 self.det = k
                 for lvl, a in enumerate(ins):
@@ -608,38 +569,38 @@ class TrainPlan:
             if isinstance(k, Concat):
                 out[i] = placed[i]
             elif isinstance(k, Upsample):
-                out[i] = home(i)
+                out[i] = placed.get(i) or new_act(i, g.ch[i])
                 self.units.append(UpsampleUnit(self, ins[0], out[i]))
             elif isinstance(k, ZeroPad2d):
-                pad_of[i] = (k.padding[1], k.padding[3])
-                out[i] = ins[0]
+                out[i] = ins[0]   # folded into the following pool
             elif isinstance(k, MaxPool2d):
-                zr, zb = pad_of.get(src[i][0], (0, 0))
-                out[i] = home(i)
+                j = g.src[i][0]
+                zr, zb = g.pad[j][1:] if j in g.pad else (0, 0)
+                out[i] = placed.get(i) or new_act(i, g.ch[i])
                 self.units.append(MaxPoolUnit(self, ins[0], out[i], k.kernel_size, k.stride, k.padding, zr, zb))
             elif isinstance(m, nn.Sequential) or isinstance(k, Bottleneck):
                 subs = list(m) if isinstance(m, nn.Sequential) else [k]
                 x = ins[0]
                 for r, sub in enumerate(subs):
                     last = r == len(subs) - 1
-                    t = new_act(hw[i], sub.cv1.conv.out_channels)
+                    t = new_act(i, sub.cv1.conv.out_channels)
                     self.units.append(ConvUnit(self, sub.cv1, x, t, None, True, f"L{i}.{r}.cv1"))
-                    y = home(i) if last else new_act(hw[i], sub.cv2.conv.out_channels)
+                    y = (placed.get(i) if last else None) or new_act(i, sub.cv2.conv.out_channels)
                     self.units.append(ConvUnit(self, sub.cv2, t, y, x if sub.add else None, True, f"L{i}.{r}.cv2"))
                     x = y
                 out[i] = x
             elif isinstance(k, SPP):
                 c_ = k.cv1.conv.out_channels
-                cat = new_act(hw[i], 4 * c_)
+                cat = new_act(i, 4 * c_)
                 s0, s3 = cat.slice(0, c_), cat.slice(c_, 3 * c_)
                 self.acts += [s0, s3]
                 self.units.append(ConvUnit(self, k.cv1, ins[0], s0, None, True, f"L{i}.cv1"))
                 self.units.append(SPPPoolUnit(self, s0, s3))
-                out[i] = home(i)
+                out[i] = placed.get(i) or new_act(i, g.ch[i])
                 self.units.append(ConvUnit(self, k.cv2, cat, out[i], None, True, f"L{i}.cv2"))
             elif isinstance(k, Conv):
-                out[i] = home(i)
-                self.units.append(ConvUnit(self, k, ins[0], out[i], None, need_dx=src[i][0] >= 0, label=f"L{i}"))
+                out[i] = placed.get(i) or new_act(i, g.ch[i])
+                self.units.append(ConvUnit(self, k, ins[0], out[i], None, need_dx=g.src[i][0] >= 0, label=f"L{i}"))
             else:
                 raise NotImplementedError(type(k).__name__)
         self._pair_bn_consumers()
@@ -659,10 +620,8 @@ class TrainPlan:
         # Y3_BN_EPILOGUE=0: statistics by a separate reduction pass over u (A/B runs); fp32 plans always take that path
         self.epilogue_stats = dtype in (torch.float16, torch.bfloat16) and os.environ.get("Y3_BN_EPILOGUE", "1") != "0"
 
-        u0 = self.units[0] if self.units else None
-        if (isinstance(u0, ConvUnit) and u0.x is self.x_in and u0.k == 3 and u0.s == 1 and u0.ci_real <= 4 and u0.cout <= 64 and u0.cout % 8 == 0
-                and dtype in (torch.float16, torch.bfloat16) and os.environ.get("Y3_STEM", "1") != "0"):
-            u0.use_stem = True
+        if _stem_eligible(g, dtype):
+            self.units[0].use_stem = True   # (layer 0 is a Conv: its unit is the first)
         self._bn_counters = [u.m.bn.num_batches_tracked for u in self.units if isinstance(u, ConvUnit) and u.m.bn.num_batches_tracked is not None]
         # scratch of the persistent conv kernel (forward + data-gradient launches of the 3x3 layers with >= 256 channels); one per plan:
         # every conv launch of the plan runs on the compute stream
