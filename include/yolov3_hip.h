@@ -241,6 +241,38 @@ int y3_match_detections(const float* dets, int64_t img_stride, int32_t row_strid
                         int32_t max_det, const float* labels, const int32_t* label_offsets, const float* iouv, int32_t niou,
                         uint8_t* correct, void* stream);
 
+/* Statistics of a validation run, device-resident (csrc/val_stats.hip): reference val.py:386-428 after process_batch, utils/metrics.py:22-178.
+ * Nothing here allocates or synchronises.  Rows of a run are three dense arrays: conf fp32, class int32, and the hits of the niou <= 16 IoU thresholds
+ * as one bit mask (bit t = threshold t).
+ * append: the valid rows of one batch (image i owns counts[i] rows, or max_det with counts == NULL) behind dst_offset, in image order.  conf / cls
+ *   point at the first row's confidence / class; row r of image i lies at [i img_stride + r elem_stride] (the batched NMS output: rows + 4, rows + 5,
+ *   6 max_det, 6; flat vectors: 0, 1 with bs = 1).  correct is the contiguous (bs, max_det, niou) result of the matching step.
+ * count_labels: nt[class] += 1 for n label classes at cls[i stride] (classes outside [0, nc) are skipped).
+ * compute: ap_per_class + compute_ap for the n rows held.  Order (class ascending, confidence descending, arrival ascending -- the last key is the
+ *   documented tie rule), fp64 curves in the reference's operation order, then the summary.  conf_grid / recall_grid are DEVICE copies of
+ *   np.linspace(0, 1, 1000) / np.linspace(0, 1, 101).  out (DEVICE doubles, at least out_elems(nc, niou)): out[0] classes with labels, out[1] the chosen
+ *   confidence index, out[2] 1 if any row has a hit, out[3] the labels counted; then one row of niou + 6 per class with labels, ascending:
+ *   [class, tp, fp, p, r, f1, ap[0 .. niou)].  workspace: 256-byte aligned, workspace_bytes(n, nc).
+ * confusion_matrix: ConfusionMatrix.process_batch for a batch, one block per image, same inputs as the matching step (labels (nl, label_stride >= 5)
+ *   [cls, x1, y1, x2, y2] grouped by image through label_offsets); adds into the DEVICE (nc + 1, nc + 1) int64 matrix[predicted][true].  Images without
+ *   labels add nothing; dets == NULL with max_det 0 is the `detections=None` form (label_stride >= 1: classes alone).
+ * labels_to_native: collate-format targets (nl, 6) [image, class, x, y, w, h] normalised, grouped by image -> (nl, 5) [class, x1, y1, x2, y2] in native
+ *   pixels (val.py:371,401-403; params as scale_boxes: per image {gain, pad_x, pad_y, w0, h0}) and the bs + 1 label offsets. */
+int y3_val_stats_append(const float* conf, const float* cls, int64_t img_stride, int32_t elem_stride, const int32_t* counts, int32_t bs,
+                        int32_t max_det, const uint8_t* correct, int32_t niou, float* dst_conf, int32_t* dst_cls, uint16_t* dst_mask,
+                        int64_t dst_offset, int64_t capacity, void* stream);
+int y3_val_stats_count_labels(const float* cls, int32_t stride, int64_t n, int32_t* nt, int32_t nc, void* stream);
+size_t y3_val_stats_out_elems(int32_t nc, int32_t niou);
+size_t y3_val_stats_workspace_bytes(int64_t n, int32_t nc);
+int y3_val_stats_compute(const float* conf, const int32_t* cls, const uint16_t* mask, int64_t n, const int32_t* nt, int32_t nc, int32_t niou,
+                         double eps, const double* conf_grid, const double* recall_grid, double* out, size_t out_elems, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int y3_confusion_matrix(const float* dets, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_det,
+                        const float* labels, int32_t label_stride, const int32_t* label_offsets, int32_t nc, float conf_thres, float iou_thres,
+                        int64_t* matrix, void* stream);
+int y3_labels_to_native(const float* targets, int32_t nl, int32_t bs, float width, float height, const float* params, float* labels_out,
+                        int32_t* offsets_out, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -414,6 +414,69 @@ def match_detections_raw(dets: torch.Tensor, img_stride: int, row_stride: int, c
     return correct
 
 
+def val_stats_append(conf: torch.Tensor, cls: torch.Tensor, img_stride: int, elem_stride: int, counts: torch.Tensor | None, bs: int, max_det: int, correct: torch.Tensor,
+                     dst_conf: torch.Tensor, dst_cls: torch.Tensor, dst_mask: torch.Tensor, dst_offset: int):
+    """rows of one batch behind `dst_offset` of the run's dense buffers (y3_val_stats_append); conf / cls are fp32 views whose data_ptr is the first row's element"""
+    require_gpu(conf, "ValStats")
+    require_gpu(correct, "ValStats")
+    if conf.dtype != torch.float32 or cls.dtype != torch.float32 or correct.dtype not in (torch.uint8, torch.bool) or not correct.is_contiguous():
+        raise TypeError("val_stats_append expects fp32 confidences / classes and a contiguous uint8 / bool (rows, T) hit matrix")
+    check(_lib.lib().y3_val_stats_append(conf.data_ptr(), cls.data_ptr(), int(img_stride), int(elem_stride), counts.data_ptr() if counts is not None else None, int(bs), int(max_det),
+                                         correct.data_ptr(), int(correct.shape[-1]), dst_conf.data_ptr(), dst_cls.data_ptr(), dst_mask.data_ptr(), int(dst_offset),
+                                         int(dst_conf.numel()), stream_ptr()), "y3_val_stats_append")
+
+
+def val_stats_count_labels(cls: torch.Tensor, stride: int, n: int, nt: torch.Tensor):
+    if n:
+        require_gpu(cls, "ValStats")
+    check(_lib.lib().y3_val_stats_count_labels(cls.data_ptr() if n else None, int(stride), int(n), nt.data_ptr(), int(nt.numel()), stream_ptr()), "y3_val_stats_count_labels")
+
+
+_val_stats_cache: dict = {}
+
+
+def val_stats_compute(conf: torch.Tensor, cls: torch.Tensor, mask: torch.Tensor, n: int, nt: torch.Tensor, niou: int, eps: float) -> torch.Tensor:
+    """ap_per_class for the first n rows of the run's buffers (y3_val_stats_compute) -> the DEVICE result block (fp64), see include/yolov3_hip.h"""
+    require_gpu(nt, "ValStats")
+    import numpy as np
+
+    dev, nc, L = nt.device, int(nt.numel()), _lib.lib()
+    grids = _val_stats_cache.get(("grids", dev.index))
+    if grids is None:   # np.linspace's own values: the sample points of the reference
+        grids = _val_stats_cache[("grids", dev.index)] = (torch.from_numpy(np.linspace(0.0, 1.0, 1000)).to(dev), torch.from_numpy(np.linspace(0.0, 1.0, 101)).to(dev))
+    need = int(L.y3_val_stats_workspace_bytes(int(n), nc))
+    if need == 0:
+        check(-1, "y3_val_stats_workspace_bytes")
+    ws = _val_stats_cache.get(("ws", dev.index))
+    if ws is None or ws.numel() < need:
+        ws = _val_stats_cache[("ws", dev.index)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(int(L.y3_val_stats_out_elems(nc, int(niou))), dtype=torch.float64, device=dev)
+    check(L.y3_val_stats_compute(conf.data_ptr() if n else None, cls.data_ptr() if n else None, mask.data_ptr() if n else None, int(n), nt.data_ptr(), nc, int(niou), float(eps),
+                                 grids[0].data_ptr(), grids[1].data_ptr(), out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_val_stats_compute")
+    return out
+
+
+def confusion_matrix_raw(dets: torch.Tensor | None, img_stride: int, row_stride: int, counts: torch.Tensor | None, bs: int, max_det: int, labels: torch.Tensor, label_stride: int,
+                         offsets: torch.Tensor, nc: int, conf: float, iou_thres: float, matrix: torch.Tensor):
+    require_gpu(matrix, "ConfusionMatrix")
+    check(_lib.lib().y3_confusion_matrix(dets.data_ptr() if dets is not None else None, int(img_stride), int(row_stride), counts.data_ptr() if counts is not None else None, int(bs),
+                                         int(max_det), labels.data_ptr() if labels.numel() else None, int(label_stride), offsets.data_ptr(), int(nc), float(conf), float(iou_thres),
+                                         matrix.data_ptr(), stream_ptr()), "y3_confusion_matrix")
+
+
+def labels_to_native(targets: torch.Tensor, bs: int, width: int, height: int, params: torch.Tensor):
+    """collate-format targets (nl, 6) on the device -> (labels (nl, 5) native pixels, offsets (bs + 1) int32), y3_labels_to_native"""
+    require_gpu(targets, "labels_to_native")
+    if targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[1] != 6 or not targets.is_contiguous():
+        raise TypeError("labels_to_native expects contiguous fp32 (nl, 6) targets [image, class, x, y, w, h]")
+    nl = targets.shape[0]
+    out = torch.empty(nl, 5, dtype=torch.float32, device=targets.device)
+    offs = torch.empty(bs + 1, dtype=torch.int32, device=targets.device)
+    check(_lib.lib().y3_labels_to_native(targets.data_ptr() if nl else None, nl, int(bs), float(width), float(height), params.data_ptr(), out.data_ptr() if nl else None,
+                                         offs.data_ptr(), stream_ptr()), "y3_labels_to_native")
+    return out, offs
+
+
 def scale_img(img: torch.Tensor, ratio: float = 1.0, same_shape: bool = False, gs: int = 32, flip_lr: bool = False) -> torch.Tensor:
     """upstream scale_img (the resize + pad of reference models/yolo.py:246), fused with the left-right mirror of the same line: (n, c, h, w) ->
     (n, c, ceil(h ratio / gs) gs, ceil(w ratio / gs) gs).  ratio 1.0 without a mirror returns `img` itself, like upstream."""

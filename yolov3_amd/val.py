@@ -1,7 +1,8 @@
 """Host-side mirror of the metric-matching step of reference val.py: ``process_batch`` (:147-188) with the reference
 signature, and a batched form that consumes the batched NMS output without a per-image Python loop or device->host
-copies.  The matching runs in csrc/val_edge.hip; AP accumulation (``ap_per_class``) stays NumPy in the
-reference: yolov3_amd/metrics.py is its host mirror."""
+copies.  The matching runs in csrc/val_edge.hip.  ``run_batches`` is the loop of val.py:351-428 itself: forward, batched
+NMS, box / label scaling, matching and the statistics of the run (``metrics.ValStats``, ``metrics.ConfusionMatrix``: csrc/val_stats.hip) all stay on the
+device; per batch the host reads the NMS counts and nothing else, and one small block at the end."""
 from __future__ import annotations
 
 import torch
@@ -76,3 +77,63 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
         pending = (pred, ev)
     if pending is not None:
         yield finish(pending)
+
+
+def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False):
+    """The validation loop of reference val.py:351-428 over ``(im, targets, shapes)`` triples in the reference dataloader's format: im (bs, 3, h, w)
+    (uint8 is scaled by 1 / 255 like val.py:358-359), targets (nl, 6) [image, class, x, y, w, h] normalised and grouped by image, shapes[i] =
+    ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))).  The post-processing of batch i (NMS, scale_boxes, labels to native space, process_batch, the
+    statistics and optionally the confusion matrix) runs on a second HIP stream while the forward of batch i + 1 fills the CUs, as in `detect_batches`;
+    its only device->host copy is the NMS counts.  Returns ((mp, mr, map50, map), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
+    from . import ops
+    from .general import _gain_pad, non_max_suppression_batched
+    from .metrics import ConfusionMatrix, ValStats
+
+    cur = torch.cuda.current_stream()
+    dev = cur.device
+    side = torch.cuda.Stream(device=dev)
+    iouv = torch.linspace(0.5, 0.95, 10, device=dev)
+    stats = ValStats(nc, iouv, dev)
+    cm = ConfusionMatrix(nc) if confusion else None
+    dtype = next(model.parameters()).dtype
+    pending = None
+
+    def finish(p):
+        pred, ev, targets, shapes, hw = p
+        bs = pred.shape[0]
+        with torch.cuda.stream(side):
+            side.wait_event(ev)
+            rows, counts, counts_list = non_max_suppression_batched(pred, conf_thres, iou_thres, None, single_cls, True, max_det)
+            if single_cls:
+                rows[:, :, 5] = 0
+            tab = []
+            for i in range(bs):
+                gain, px, py = _gain_pad(hw, shapes[i][0], shapes[i][1])
+                tab.append([gain, px, py, float(shapes[i][0][1]), float(shapes[i][0][0])])
+            params = torch.tensor(tab, dtype=torch.float32).to(dev, non_blocking=True)
+            ops.scale_boxes_raw(rows, rows.stride(0), rows.stride(1), counts, bs, rows.shape[1], params)
+            labels, offs = ops.labels_to_native(targets, bs, hw[1], hw[0], params)
+            correct = process_batch_batched(rows, counts, labels, offs, iouv)
+            stats.update(rows, counts, counts_list, correct, labels, offs)
+            if cm is not None:
+                cm.process_batch_batched(rows, counts, labels, offs)
+        cur.wait_stream(side)
+
+    for im, targets, shapes in batches:
+        im = im.to(dev, non_blocking=True)
+        if im.dtype == torch.uint8:
+            im = im.to(dtype) / 255
+        elif im.dtype != dtype:
+            im = im.to(dtype)
+        targets = targets.to(dev, torch.float32, non_blocking=True).contiguous()
+        out = model(im)
+        pred = out[0] if isinstance(out, (list, tuple)) else out
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        if pending is not None:
+            finish(pending)
+        pending = (pred, ev, targets, shapes, tuple(im.shape[2:]))
+    if pending is not None:
+        finish(pending)
+    res = stats.results()
+    return (res, stats.maps(nc), stats, cm) if confusion else (res, stats.maps(nc), stats)
