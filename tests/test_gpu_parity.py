@@ -51,10 +51,46 @@ def conv_ws(dev):
     return _WS[dev]
 
 
+def bits(t):
+    """the tensor's storage as integers: bit-for-bit comparisons that also hold for NaN"""
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def wide_view(ops, n, h, w, c, dtype, dev, pads, fill):
+    """(buffer view, channel slice): `c` channels placed behind pads[0] and in front of pads[1] channels of `fill` in a (n, h, w, pads[0] + c + pads[1]) buffer -- the
+    pitch > c, offset data pointer views a layer inside a Concat buffer hands its neighbours.  pads None: the plain pitch == c tensor (buffer is slice)."""
+    if pads is None:
+        v = ops.View.alloc(n, h, w, c, dtype, dev)
+        v.buf.fill_(fill)
+        return v, v
+    left, right = pads
+    esz = torch.empty(0, dtype=dtype).element_size()
+    assert (left * esz) % 16 == 0 and (left + c + right) % 8 == 0, "the ABI wants 16-byte aligned slice starts and pitches of whole 8-element groups"
+    big = ops.View.alloc(n, h, w, left + c + right, dtype, dev)
+    big.buf.fill_(fill)
+    return big, big.slice(left, c)
+
+
+def assert_outside_unchanged(big, before, written, what):
+    """every channel of the buffer `big` outside the (first channel, channels) ranges in `written` holds the bits of the snapshot `before` (canary / poison / input intact)"""
+    now, was = bits(big.as_nhwc()), bits(before.view(big.n, big.h, big.w, big.pitch))
+    keep = torch.ones(big.pitch, dtype=torch.bool, device=now.device)
+    for c0, c in written:
+        keep[c0 : c0 + c] = False
+    assert torch.equal(now[..., keep], was[..., keep]), f"{what}: the launch changed memory outside its channel slice"
+
+
 def run_conv(dev, dtype, n, h, w, cin, cout, k, s, act=True, residual=False, ups=False, sliced=False, algo=0, seed=0, cin_real=None, cout_real=None, ws=False, expect=None,
-             repeat=1, check_ws=True):
+             repeat=1, check_ws=True, views=None):
     """Returns (hip output NCHW fp32 cpu, reference NCHW fp32 cpu computed from the SAME rounded operands).  ws: call through
-    y3_conv2d_fwd_ws; expect: assert the kernel variant the dispatcher picks (so a tolerance is tied to the kernel that ran)."""
+    y3_conv2d_fwd_ws; expect: assert the kernel variant the dispatcher picks (so a tolerance is tied to the kernel that ran).
+    views (default: every tensor with pitch == c, as before): dict of (left, right) channel pads for "x", "res" and "y" -- the tensor becomes a channel slice of a wider
+    buffer; "res_in_y": True puts the residual and the output into ONE buffer as different slices (pads "res" left of the residual, pads "y" around the output).  Everything
+    outside the input slices is NaN before the launch, everything outside the output slice a canary; afterwards the output must be finite and every buffer bit-unchanged
+    outside the output slice.  run_conv.variant: the variant the last launch took."""
+    if views is not None:
+        assert not sliced
+        return _run_conv_views(dev, dtype, n, h, w, cin, cout, k, s, act, residual, ups, algo, seed, cin_real, cout_real, ws, expect, repeat, check_ws, views)
     _lib, ops = _ops()
     g = torch.Generator().manual_seed(seed)
     cin_real = cin_real or cin
@@ -111,6 +147,81 @@ def run_conv(dev, dtype, n, h, w, cin, cout, k, s, act=True, residual=False, ups
     if sliced:
         full = big.as_nhwc().float().cpu()
         assert torch.all(full[..., :16] == 7.0) and torch.all(full[..., 16 + cout :] == 7.0), "conv wrote outside its channel slice"
+    run_conv.variant = ops.last_conv_variant()
+    return out, ref
+
+
+def _run_conv_views(dev, dtype, n, h, w, cin, cout, k, s, act, residual, ups, algo, seed, cin_real, cout_real, ws, expect, repeat, check_ws, views):
+    """run_conv on channel-sliced views: the same operands (same seed, same draw order) and the same reference as the pitch == c path"""
+    _lib, ops = _ops()
+    g = torch.Generator().manual_seed(seed)
+    cin_real = cin_real or cin
+    cout_real = cout_real or cout
+    x = torch.randn(n, cin_real, h, w, generator=g)
+    wt = torch.randn(cout_real, cin_real, k, k, generator=g) / math.sqrt(cin_real * k * k)
+    b = torch.randn(cout_real, generator=g) * 0.5
+    xq, wq = x.to(dtype).float(), wt.to(dtype).float()
+    ho, wo = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
+    res = torch.randn(n, cout_real, ho, wo, generator=g).to(dtype).float() if residual else None
+    ref = F.conv2d(xq, wq, b, stride=s, padding=k // 2)
+    if act:
+        ref = F.silu(ref)
+    if residual:
+        ref = ref + res
+    if ups:
+        ref = F.interpolate(ref, scale_factor=2.0, mode="nearest")
+    nan = float("nan")
+    up = 2 if ups else 1
+
+    def put(t_nchw, view, c_real):   # NCHW fp32 host values -> the view's channels (pad channels behind c_real: zeros, like y3_nchw_to_nhwc writes them)
+        dst = view.as_nhwc()
+        dst.zero_()
+        dst[..., :c_real] = t_nchw.permute(0, 2, 3, 1).to(dev).to(dtype)
+
+    xbig, xv = wide_view(ops, n, h, w, cin, dtype, dev, views.get("x"), nan)
+    put(x, xv, cin_real)
+    rbig = rv = None
+    if residual and views.get("res_in_y"):
+        rl, (yl, yr) = views["res"][0], views["y"]
+        ybig, _ = wide_view(ops, n, ho, wo, cout, dtype, dev, (rl, yl + cout + yr), nan)   # [rl | residual | yl | output | yr]
+        rv, yv = ybig.slice(rl, cout), ybig.slice(rl + cout + yl, cout)
+        put(res, rv, cout_real)
+        y_written = [(yv.coff, cout)]
+    else:
+        ybig, yv = wide_view(ops, n, ho * up, wo * up, cout, dtype, dev, views.get("y"), 7.0)
+        y_written = [(yv.coff, cout)]
+        if residual:
+            rbig, rv = wide_view(ops, n, ho, wo, cout, dtype, dev, views.get("res"), nan)
+            put(res, rv, cout_real)
+    filt = ops.pack_filter(wt.to(dev), cout, cin, dtype)
+    bias = torch.zeros(cout, device=dev)
+    bias[:cout_real] = b.to(dev)
+    wsp = conv_ws(dev) if ws else None
+    got = ops.conv_variant(xv, yv, k, s, residual, ups, algo, workspace_bytes=wsp.numel() if ws else 0)
+    if expect is not None:
+        assert got == expect, f"dispatcher picked {got}, the test is written for {expect}"
+    snap = {name: big.buf.clone() for name, big in (("x", xbig), ("res", rbig), ("y", ybig)) if big is not None}
+    first = None
+    for r in range(repeat):
+        if r:
+            yv.as_nhwc().fill_(-3.0)
+        ops.conv2d(xv, filt, bias, yv, k, s, act, rv, ups, algo, workspace=wsp)
+        torch.cuda.synchronize()
+        assert ops.last_conv_variant() == got, (ops.last_conv_variant(), got)
+        cur = yv.as_nhwc().clone()
+        if first is None:
+            first = cur
+        else:
+            assert torch.equal(first, cur), f"launch {r} differs from launch 0 (non-deterministic or stale workspace state)"
+    run_conv.variant = got
+    if ws and check_ws:
+        assert int(wsp[:8192].view(torch.int32).abs().sum()) == 0, "the conv wrote into the head of its workspace"
+    assert torch.isfinite(first.float()).all(), f"{got}: the output is not finite -- the kernel read poisoned memory outside its input slices (or left pixels unwritten)"
+    assert_outside_unchanged(xbig, snap["x"], [], f"{got} input")
+    if rbig is not None:
+        assert_outside_unchanged(rbig, snap["res"], [], f"{got} residual")
+    assert_outside_unchanged(ybig, snap["y"], y_written, f"{got} output")
+    out = first.float().cpu().permute(0, 3, 1, 2)[:, :cout_real]
     return out, ref
 
 

@@ -340,12 +340,14 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const T* __restri
 
 // ------------------------------------------------------------------------------------------------------------------
 // Filter gradient, direct form: one thread per dW[co][ci][kh][kw] (OIHW fp32, the layout of nn.Conv2d.weight.grad),
-// serial over the pixels of a slice, slices combined with atomicAdd.  Exact-order-free fp32; used for the fp32 parity
-// path and as the cross-check of the MFMA kernel.
+// serial over the pixels of a slice.  One slice stores dW itself; several slices store fp32 partials [slice][element] into
+// the caller's workspace and wgrad_direct_reduce_kernel adds them in slice order -- no atomics: like every other reduction
+// of the library the result does not change from launch to launch (atomicAdd combined the slices until a sliced-view test
+// compared two launches bit for bit).  Used for the fp32 parity path and as the cross-check of the MFMA kernel.
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_direct_kernel(const T* __restrict__ x, int N, int H, int W, int Cin, int xpitch, const T* __restrict__ du, int Ho,
                                                              int Wo, int Cout, int dpitch, int ks, int stride, int pad, int cin_real, int cout_real,
-                                                             float* __restrict__ dw, int mslices) {
+                                                             float* __restrict__ dw, int mslices, float* __restrict__ part) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)cout_real * cin_real * ks * ks;
     if (idx >= total) return;
@@ -367,7 +369,25 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(const T* __restrict__
         if ((unsigned)hi >= (unsigned)H || (unsigned)wi >= (unsigned)W) continue;
         acc = fmaf(to_f32<T>(du[m * dpitch + co]), to_f32<T>(x[((long long)(n * H + hi) * W + wi) * xpitch + ci]), acc);
     }
-    atomicAdd(&dw[idx], acc);
+    if (part) part[(long long)blockIdx.y * total + idx] = acc;
+    else dw[idx] = acc;
+}
+
+__global__ __launch_bounds__(256) void wgrad_direct_reduce_kernel(const float* __restrict__ part, long long total, int mslices, float* __restrict__ dw) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    float a = 0.0f;
+    for (int s = 0; s < mslices; ++s) a += part[(long long)s * total + idx];
+    dw[idx] = a;
+}
+
+// pixel slices of the direct filter-gradient kernel: enough to fill the machine when the filter is small
+static long long wgrad_direct_slices(long long total, long long M) {
+    long long want = (256LL * 8 * 256 + total - 1) / total;
+    if (want > M / 64) want = M / 64;
+    if (want < 1) want = 1;
+    if (want > 4096) want = 4096;
+    return want;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2219,9 +2239,14 @@ extern "C" int y3_conv2d_wgrad_plan(const y3_conv_desc* d, const y3_tensor* x, i
 }
 
 extern "C" size_t y3_conv2d_wgrad_workspace_bytes(const y3_conv_desc* d, const y3_tensor* x) {
-    if (!d || !x || d->dtype == Y3_F32) return 256;
+    if (!d || !x) return 256;
     const int pad = d->ksize / 2;
     const int Ho = (x->h + 2 * pad - d->ksize) / d->stride + 1, Wo = (x->w + 2 * pad - d->ksize) / d->stride + 1;
+    // the direct kernel's partials (fp32 always; f16 / bf16 when it is forced or an operand passes the reach of a buffer descriptor): real sizes <= padded sizes
+    const long long total_d = (long long)d->cout * d->cin * d->ksize * d->ksize;
+    const long long slices_d = total_d > 0 ? wgrad_direct_slices(total_d, (long long)x->n * Ho * Wo) : 1;
+    const size_t need_d = slices_d > 1 ? (size_t)slices_d * total_d * sizeof(float) : 256;
+    if (d->dtype == Y3_F32) return need_d;
     int n_ct, n_nt, tsh;
     long long slices, per;
     wgrad_geometry(d, (long long)x->n * Ho * Wo, n_ct, n_nt, slices, per, tsh);
@@ -2230,7 +2255,7 @@ extern "C" size_t y3_conv2d_wgrad_workspace_bytes(const y3_conv_desc* d, const y
     if (strip_plan(d, x->n, x->h, x->w, d->cout, d->cin, false, sp) && sp.ws_bytes > need) need = sp.ws_bytes;
     PatchPlan pp;
     if (patch_plan(d, x->n, x->h, x->w, pp) && pp.ws_bytes > need) need = pp.ws_bytes;
-    return need;
+    return need > need_d ? need : need_d;
 }
 
 extern "C" int y3_conv2d_wgrad(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* du, int32_t cout_real, int32_t cin_real, float* dw_oihw, float* dbias,
@@ -2319,16 +2344,18 @@ extern "C" int y3_conv2d_wgrad(const y3_conv_desc* d, const y3_tensor* x, const 
                                cout_real, dw_oihw, tsh);
         Y3_CHECK_LAUNCH();
     } else {
-        Y3_HIP(hipMemsetAsync(dw_oihw, 0, (size_t)total * sizeof(float), st));
-        // enough pixel slices to fill the machine when the filter is small
-        long long want = (256LL * 8 * 256 + total - 1) / total;
-        if (want > M / 64) want = M / 64;
-        if (want < 1) want = 1;
-        if (want > 4096) want = 4096;
+        long long want = wgrad_direct_slices(total, M);
+        // without room for the partials (a caller that did not size its workspace with y3_conv2d_wgrad_workspace_bytes): one slice, still deterministic
+        if (want > 1 && (!workspace || workspace_bytes < (size_t)want * total * sizeof(float) || (((uintptr_t)workspace) & 3))) want = 1;
+        float* part = want > 1 ? (float*)workspace : nullptr;
         const dim3 grid(nblk(total), (unsigned)want);
         Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((wgrad_direct_kernel<T>), grid, dim3(256), 0, st, (const T*)x->data, x->n, x->h, x->w, d->cin, x->pitch,
-                                                   (const T*)du->data, Ho, Wo, d->cout, du->pitch, d->ksize, d->stride, pad, cin_real, cout_real, dw_oihw, (int)want));
+                                                   (const T*)du->data, Ho, Wo, d->cout, du->pitch, d->ksize, d->stride, pad, cin_real, cout_real, dw_oihw, (int)want, part));
         Y3_CHECK_LAUNCH();
+        if (part) {
+            hipLaunchKernelGGL(wgrad_direct_reduce_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float*)part, total, (int)want, dw_oihw);
+            Y3_CHECK_LAUNCH();
+        }
     }
     if (dbias) {
         // bias gradient = per-channel sum of du.  The filter-gradient workspace is idle again (stream order): it holds the
@@ -2337,7 +2364,8 @@ extern "C" int y3_conv2d_wgrad(const y3_conv_desc* d, const y3_tensor* x, const 
         const int esz = esize(d->dtype);
         unsigned grid = 0;
         const size_t row_bytes = (size_t)2 * d->cout * sizeof(double);
-        if (vec_ok(du, esz) && d->cout / (16 / esz) <= 256 && workspace && workspace_bytes >= 3 * row_bytes && (((uintptr_t)workspace) & 7) == 0) {
+        // (fp32 keeps the one-block-per-channel sum it always ran: its workspace held 256 bytes until the direct kernel's partials moved into it)
+        if (d->dtype != Y3_F32 && vec_ok(du, esz) && d->cout / (16 / esz) <= 256 && workspace && workspace_bytes >= 3 * row_bytes && (((uintptr_t)workspace) & 7) == 0) {
             if (reduce_geometry(d->cout, esz, M, grid)) return -1;
             const size_t fit = workspace_bytes / row_bytes - 1;
             if (grid > fit) grid = (unsigned)fit;
