@@ -346,7 +346,6 @@ def test_conv1x1_bn_in_consumer_matches_separate_passes(dev, tune, dtype, name, 
     bits (same arithmetic on the same operands, same K order), every pixel and channel.  (Knob conv_1x1s = 2: the dispatcher leaves launches below 8192 pixels to the
     separate passes since round 6 -- most cases here are smaller.)"""
     _lib, ops = _ops()
-    import ctypes as C
 
     tune("conv_1x1s", 2)
     n, h, w, cin, cout = shape
@@ -366,10 +365,7 @@ def test_conv1x1_bn_in_consumer_matches_separate_passes(dev, tune, dtype, name, 
     act = _lib.Y3_ACT_SILU if silu else _lib.Y3_ACT_NONE
     # the two launches
     y_ref = ops.View.alloc(n, h, w, cin, dtype, dev)
-    ut, yt = u_in.y3(), y_ref.y3()
-    rt = res.y3() if res is not None else None
-    _lib.check(_lib.lib().y3_bn_act_fwd(C.byref(ut), scale.data_ptr(), shift.data_ptr(), C.byref(rt) if rt is not None else None, C.byref(yt), ops.dtype_code(dtype), act,
-                                        ops.stream_ptr()), "y3_bn_act_fwd")
+    ops.bn_act_fwd(u_in, ops.BnVecs(scale, shift), act, y_ref, res)
     o_ref = ops.View.alloc(n, h, w, cout, dtype, dev)
     rows_ref = ops.conv2d_stats_rows(y_ref, o_ref, 1, 1)
     buf_ref = torch.full((rows_ref * 2 * cout,), float("nan"), device=dev)
@@ -1906,13 +1902,11 @@ def test_conv_epilogue_bn_statistics(dev, tune, dtype, name, shape):
     assert (tot[:, 0] - ref0).abs().max().item() <= 1e-5 * u.abs().sum(0).max().item(), "sum"
     assert (tot[:, 1] - ref1).abs().max().item() <= 1e-5 * ref1.max().item(), "sum of squares"
     # finalize from the rows == BatchNorm2d(eps 1e-3, momentum 0.03) batch statistics of the stored tensor
-    sums = ops.bn_scratch(cout, dev)
     gamma, beta = torch.rand(cout, device=dev) + 0.5, torch.randn(cout, device=dev)
     rm, rv = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
-    scale, shift, mean, invstd = (torch.empty(cout, device=dev) for _ in range(4))
+    scale, shift, mean, invstd, sums = v = ops.BnVecs.alloc(cout, dev)
     cnt = n * ho * wo
-    _lib.check(_lib.lib().y3_bn_finalize_rows(buf.data_ptr(), rows, cnt, cout, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.03, rm.data_ptr(), rv.data_ptr(),
-                                              scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ops.stream_ptr()), "y3_bn_finalize_rows")
+    ops.bn_finalize_rows(buf, rows, cnt, cout, ops.bn_affine(gamma, beta, 1e-3, 0.03, rm, rv), v)
     torch.cuda.synchronize()
     mu, var = u.mean(0), u.var(0, unbiased=False)
     torch.testing.assert_close(mean.double().cpu(), mu, rtol=1e-4, atol=1e-5)
@@ -2382,9 +2376,7 @@ def test_stem_layer0_by_recomputation_matches_the_stored_path(dev, dtype, shape)
     y3_bn_act_fwd on the stored u).  Backward: dW / dgamma / dbeta against the stored-u kernels (another order of the fp64 partial sums: 1e-6 level) and against
     fp32 autograd of conv -> affine -> SiLU on the same rounded operands."""
     _lib, ops = _ops()
-    import ctypes as C
 
-    L = _lib.lib()
     n, h, w = shape
     g = torch.Generator().manual_seed(17)
     x = torch.rand(n, 3, h, w, generator=g)
@@ -2404,8 +2396,7 @@ def test_stem_layer0_by_recomputation_matches_the_stored_path(dev, dtype, shape)
     scale = (gamma * invstd).contiguous()
     shift = (beta - mean * gamma * invstd).contiguous()
     y_ref = ops.View.alloc(n, h, w, 32, dtype, dev)
-    ut, yt = u.y3(), y_ref.y3()
-    _lib.check(L.y3_bn_act_fwd(C.byref(ut), scale.data_ptr(), shift.data_ptr(), None, C.byref(yt), ops.dtype_code(dtype), _lib.Y3_ACT_SILU, ops.stream_ptr()), "y3_bn_act_fwd")
+    ops.bn_act_fwd(u, ops.BnVecs(scale, shift), _lib.Y3_ACT_SILU, y_ref)
     # recomputation
     r_new = torch.zeros(rows_cap * 64, device=dev)
     like = ops.View(torch.empty(0, dtype=dtype, device=dev), n, h, w, 32, 32, 0)
@@ -2497,9 +2488,7 @@ def test_maxpool_backward_indexed_form(dev, dtype, n, h, w, c, k, s, p, zr, zb):
     """y3_maxpool2d_bwd_ws (round 6: first-maximum index per window + k^2 look-ups per element) against the gather form y3_maxpool2d_bwd it replaces in the training plans --
     the same bits, write and accumulate, with ties in the input (half the values are repeated) -- and against torch's max_pool2d autograd on tie-free inputs."""
     _lib, ops = _ops()
-    import ctypes as C
 
-    L = _lib.lib()
     g = torch.Generator().manual_seed(23)
     ho, wo = (h + zb + 2 * p - k) // s + 1, (w + zr + 2 * p - k) // s + 1
     for ties in (True, False):
@@ -2518,8 +2507,7 @@ def test_maxpool_backward_indexed_form(dev, dtype, n, h, w, c, k, s, p, zr, zb):
             dx.buf.fill_(float("nan"))
             for acc in (False, True):
                 if form == "gather":
-                    a, b, d = xv.y3(), gv.y3(), dx.y3()
-                    _lib.check(L.y3_maxpool2d_bwd(C.byref(a), C.byref(b), C.byref(d), ops.dtype_code(dtype), k, s, p, zr, zb, int(acc), ops.stream_ptr()), "y3_maxpool2d_bwd")
+                    ops.maxpool2d_bwd_gather(xv, gv, dx, k, s, p, zr, zb, accumulate=acc)
                 else:
                     ops.maxpool2d_bwd(xv, gv, dx, k, s, p, zr, zb, accumulate=acc)
             torch.cuda.synchronize()
@@ -2574,7 +2562,6 @@ def test_stem_bn_bwd_wgrad_matches_unfused_backward(dev, dtype, shape, sdt, div,
     """y3_stem_bn_bwd_wgrad (layer 0 backward: BatchNorm + SiLU backward and the filter gradient in one pass, du never stored) against the
     path it replaces -- y3_bn_act_bwd (du stored in T) + y3_conv2d_wgrad on the NHWC image: dgamma / dbeta bit-identical (same reduction),
     dW equal up to fp32 summation order (both multiply the SAME T-rounded du and image values); and against torch autograd in fp32."""
-    import ctypes as C
 
     _lib, ops = _ops()
     n, cin, h, w = shape
@@ -2604,9 +2591,7 @@ def test_stem_bn_bwd_wgrad_matches_unfused_backward(dev, dtype, shape, sdt, div,
     sums = ops.bn_scratch(cout, dev)
     duv = ops.View.alloc(n, h, w, cout, dtype, dev)
     dg0, db0 = torch.empty(cout, device=dev), torch.empty(cout, device=dev)
-    ut, gt, dt_ = uv.y3(), gv.y3(), duv.y3()
-    _lib.check(_lib.lib().y3_bn_act_bwd(C.byref(ut), C.byref(gt), scale.data_ptr(), shift.data_ptr(), mean_d.data_ptr(), invstd_d.data_ptr(), ops.dtype_code(dtype), a,
-                                        sums.data_ptr(), C.byref(dt_), dg0.data_ptr(), db0.data_ptr(), ops.stream_ptr()), "y3_bn_act_bwd")
+    ops.bn_act_bwd(uv, gv, ops.BnVecs(scale, shift, mean_d, invstd_d, sums), a, duv, dg0, db0)
     xin = ops.View.alloc(n, h, w, 8, dtype, dev)
     ops.nchw_to_nhwc(xd, xin, div)
     dw0, _ = ops.conv2d_wgrad(xin, duv, 3, 1, cout, cin)
@@ -2941,10 +2926,8 @@ def test_bn_passes_plain_and_nontemporal_forms(dev, tune, dtype, nt, shape, act,
     """The elementwise / reduction passes of train-mode BatchNorm + SiLU (y3_bn_stats_finalize, y3_bn_act_fwd, y3_bn_act_bwd(_res)) against
     an fp64 torch reference, in their plain form and -- knob bn_nt_bytes = 0 -- in the non-temporal form the library takes for tensors of
     >= 128 MB (the batch-64 activations of the 640 / 320 / 160-pixel layers); both forms must agree bit for bit."""
-    import ctypes as C
 
     _lib, ops = _ops()
-    L = _lib.lib()
     n, h, w, c = shape
     M = n * h * w
     g = torch.Generator(device=dev).manual_seed(3)
@@ -2965,19 +2948,10 @@ def test_bn_passes_plain_and_nontemporal_forms(dev, tune, dtype, nt, shape, act,
         sums = ops.bn_scratch(c, dev)
         scale, shift, mean, invstd, dgamma, dbeta = (torch.empty(c, device=dev) for _ in range(6))
         rmean, rvar = torch.zeros(c, device=dev), torch.ones(c, device=dev)
-        ut, yt, dyt, dut = uv.y3(), yv.y3(), dyv.y3(), duv.y3()
-        dc, a, st = ops.dtype_code(dtype), (_lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE), ops.stream_ptr()
-        _lib.check(L.y3_bn_stats_finalize(C.byref(ut), dc, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.03, rmean.data_ptr(), rvar.data_ptr(), scale.data_ptr(),
-                                          shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), st), "y3_bn_stats_finalize")
-        rt = rv.y3() if rv is not None else None
-        _lib.check(L.y3_bn_act_fwd(C.byref(ut), scale.data_ptr(), shift.data_ptr(), C.byref(rt) if rt is not None else None, C.byref(yt), dc, a, st), "y3_bn_act_fwd")
-        if residual:
-            grt = gr.y3()
-            _lib.check(L.y3_bn_act_bwd_res(C.byref(ut), C.byref(dyt), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dc, a, sums.data_ptr(), C.byref(dut),
-                                           dgamma.data_ptr(), dbeta.data_ptr(), C.byref(grt), 1, st), "y3_bn_act_bwd_res")
-        else:
-            _lib.check(L.y3_bn_act_bwd(C.byref(ut), C.byref(dyt), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dc, a, sums.data_ptr(), C.byref(dut),
-                                       dgamma.data_ptr(), dbeta.data_ptr(), st), "y3_bn_act_bwd")
+        v, a = ops.BnVecs(scale, shift, mean, invstd, sums), (_lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE)
+        ops.bn_stats_finalize(uv, ops.bn_affine(gamma, beta, 1e-3, 0.03, rmean, rvar), v)
+        ops.bn_act_fwd(uv, v, a, yv, rv)
+        ops.bn_act_bwd(uv, dyv, v, a, duv, dgamma, dbeta, gr, gres_accumulate=True)   # (gr is None without a residual: y3_bn_act_bwd, else y3_bn_act_bwd_res)
         torch.cuda.synchronize()
         outs[form] = dict(y=yv.buf.clone(), du=duv.buf.clone(), dgamma=dgamma.clone(), dbeta=dbeta.clone(), mean=mean.clone(), invstd=invstd.clone(), rmean=rmean.clone(),
                           rvar=rvar.clone(), gres=gr.buf.clone() if gr is not None else None)
@@ -3005,10 +2979,8 @@ def test_bn_passes_on_a_tensor_beyond_the_nontemporal_threshold(dev):
     """default knobs on the batch-64 activation of the 160-pixel layers (64 x 160 x 160 x 128 fp16 = 419 MB >= bn_nt_bytes): statistics,
     normalisation + SiLU and the backward reduce / apply run in the forms the benchmarked train step runs them in (non-temporal loads and
     stores, uncapped grids, two-level partial sums) and match a chunked fp32 torch evaluation."""
-    import ctypes as C
 
     _lib, ops = _ops()
-    L = _lib.lib()
     assert ops.tune_get("bn_nt_bytes") == 64 << 20   # (round 6: 64 MiB; the tensor below is beyond either value)
     n, h, w, c = 64, 160, 160, 128
     dtype = torch.float16
@@ -3020,15 +2992,11 @@ def test_bn_passes_on_a_tensor_beyond_the_nontemporal_threshold(dev):
     dyv.buf.normal_(generator=g)
     gamma = torch.rand(c, device=dev, generator=g) + 0.5
     beta = torch.randn(c, device=dev, generator=g) * 0.3
-    sums = ops.bn_scratch(c, dev)
-    scale, shift, mean, invstd, dgamma, dbeta = (torch.empty(c, device=dev) for _ in range(6))
-    ut, yt, dyt, dut = uv.y3(), yv.y3(), dyv.y3(), duv.y3()
-    dc, st = ops.dtype_code(dtype), ops.stream_ptr()
-    _lib.check(L.y3_bn_stats_finalize(C.byref(ut), dc, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.03, None, None, scale.data_ptr(), shift.data_ptr(),
-                                      mean.data_ptr(), invstd.data_ptr(), st), "y3_bn_stats_finalize")
-    _lib.check(L.y3_bn_act_fwd(C.byref(ut), scale.data_ptr(), shift.data_ptr(), None, C.byref(yt), dc, _lib.Y3_ACT_SILU, st), "y3_bn_act_fwd")
-    _lib.check(L.y3_bn_act_bwd(C.byref(ut), C.byref(dyt), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dc, _lib.Y3_ACT_SILU, sums.data_ptr(), C.byref(dut),
-                               dgamma.data_ptr(), dbeta.data_ptr(), st), "y3_bn_act_bwd")
+    scale, shift, mean, invstd, sums = v = ops.BnVecs.alloc(c, dev)
+    dgamma, dbeta = torch.empty(c, device=dev), torch.empty(c, device=dev)
+    ops.bn_stats_finalize(uv, ops.bn_affine(gamma, beta, 1e-3, 0.03, None, None), v)
+    ops.bn_act_fwd(uv, v, _lib.Y3_ACT_SILU, yv)
+    ops.bn_act_bwd(uv, dyv, v, _lib.Y3_ACT_SILU, duv, dgamma, dbeta)
     torch.cuda.synchronize()
     U, DY = uv.buf.view(M, c), dyv.buf.view(M, c)
     s0 = torch.zeros(c, dtype=torch.float64, device=dev)

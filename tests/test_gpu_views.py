@@ -7,7 +7,6 @@ channel count and whose data pointer is offset (ops.View / y3_tensor: "channels 
   3. poison and canary: NaN everywhere outside the input slices, a canary outside the output slice; the output must be finite, canary and inputs bit-unchanged.
 A kernel that rounds K up and leans on zero filter padding multiplies the neighbour's channels by zero: 0 * NaN shows up in (3).
 """
-import ctypes as C
 import math
 
 import pytest
@@ -473,7 +472,6 @@ def test_conv_dgrad_s2_on_sliced_views(dev, tune, dtype, name, shape, knobs, var
 # ------------------------------------------------------------------------------------------------ BatchNorm passes
 def _bn_run(ops, _lib, dev, dtype, shape, act, residual, gres_acc, sliced, split):
     """statistics + finalize, normalise (+ residual), backward (+ residual gradient) on one set of operands; split: the backward as y3_bn_act_bwd_reduce + y3_bn_act_bwd_apply"""
-    L = _lib.lib()
     n, h, w, c = shape
     g = torch.Generator(device=dev).manual_seed(3)
     u = torch.empty(n, h, w, c, device=dev).normal_(generator=g).mul_(1.5).add_(0.25)
@@ -495,21 +493,14 @@ def _bn_run(ops, _lib, dev, dtype, shape, act, residual, gres_acc, sliced, split
     sums = ops.bn_scratch(c, dev)
     scale, shift, mean, invstd, dgamma, dbeta = (torch.full((c,), NAN, device=dev) for _ in range(6))
     rmean, rvar = torch.zeros(c, device=dev), torch.ones(c, device=dev)
-    ut, yt, dyt, dut = ub.v.y3(), yb.v.y3(), dyb.v.y3(), dub.v.y3()
-    rt = rb.v.y3() if rb else None
-    grt = grb.v.y3() if grb else None
-    dc, a, st = ops.dtype_code(dtype), (_lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE), ops.stream_ptr()
-    _lib.check(L.y3_bn_stats_finalize(C.byref(ut), dc, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.03, rmean.data_ptr(), rvar.data_ptr(), scale.data_ptr(),
-                                      shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), st), "y3_bn_stats_finalize")
-    _lib.check(L.y3_bn_act_fwd(C.byref(ut), scale.data_ptr(), shift.data_ptr(), C.byref(rt) if rt is not None else None, C.byref(yt), dc, a, st), "y3_bn_act_fwd")
-    common = (C.byref(ut), C.byref(dyt), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dc, a, sums.data_ptr())
+    v, a, gres = ops.BnVecs(scale, shift, mean, invstd, sums), (_lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE), (grb.v if grb else None)
+    ops.bn_stats_finalize(ub.v, ops.bn_affine(gamma, beta, 1e-3, 0.03, rmean, rvar), v)
+    ops.bn_act_fwd(ub.v, v, a, yb.v, rb.v if rb else None)
     if split:
-        _lib.check(L.y3_bn_act_bwd_reduce(*common, dgamma.data_ptr(), dbeta.data_ptr(), st), "y3_bn_act_bwd_reduce")
-        _lib.check(L.y3_bn_act_bwd_apply(*common, C.byref(dut), C.byref(grt) if grt is not None else None, int(gres_acc), st), "y3_bn_act_bwd_apply")
-    elif residual:
-        _lib.check(L.y3_bn_act_bwd_res(*common, C.byref(dut), dgamma.data_ptr(), dbeta.data_ptr(), C.byref(grt), int(gres_acc), st), "y3_bn_act_bwd_res")
+        ops.bn_act_bwd_reduce(ub.v, dyb.v, v, a, dgamma, dbeta)
+        ops.bn_act_bwd_apply(ub.v, dyb.v, v, a, dub.v, gres, gres_acc)
     else:
-        _lib.check(L.y3_bn_act_bwd(*common, C.byref(dut), dgamma.data_ptr(), dbeta.data_ptr(), st), "y3_bn_act_bwd")
+        ops.bn_act_bwd(ub.v, dyb.v, v, a, dub.v, dgamma, dbeta, gres, gres_acc)
     torch.cuda.synchronize()
     ub.check("bn u")
     dyb.check("bn dy")
@@ -576,7 +567,6 @@ def test_bn_sum_rows_and_devcount_equal_finalize_rows(dev, n_rows):
     """y3_bn_sum_rows + y3_bn_finalize_devcount (the SyncBatchNorm forward of one rank) against y3_bn_finalize_rows with the host count: scale, shift, mean, invstd and the running
     statistics bit for bit -- one level (<= 512 rows) and two levels of the row sum"""
     _lib, ops = _ops()
-    L = _lib.lib()
     c, count = 136, 64 * n_rows - 5
     g = torch.Generator().manual_seed(n_rows)
     rows = torch.empty(n_rows, c, 2)
@@ -589,13 +579,13 @@ def test_bn_sum_rows_and_devcount_equal_finalize_rows(dev, n_rows):
         sums = ops.bn_scratch(c, dev)
         rm, rv = torch.full((c,), 0.25, device=dev), torch.full((c,), 1.5, device=dev)
         scale, shift, mean, invstd = (torch.full((c,), NAN, device=dev) for _ in range(4))
-        tail = (gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.03, rm.data_ptr(), rv.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ops.stream_ptr())
+        affine, v = ops.bn_affine(gamma, beta, 1e-3, 0.03, rm, rv), ops.BnVecs(scale, shift, mean, invstd, sums)
         if form == "rows":
-            _lib.check(L.y3_bn_finalize_rows(rows.data_ptr(), n_rows, count, c, sums.data_ptr(), *tail), "y3_bn_finalize_rows")
+            ops.bn_finalize_rows(rows, n_rows, count, c, affine, v)
         else:
             cnt = torch.tensor([float(count)], dtype=torch.float64, device=dev)
-            _lib.check(L.y3_bn_sum_rows(rows.data_ptr(), n_rows, c, sums.data_ptr(), ops.stream_ptr()), "y3_bn_sum_rows")
-            _lib.check(L.y3_bn_finalize_devcount(sums.data_ptr(), cnt.data_ptr(), c, *tail), "y3_bn_finalize_devcount")
+            ops.bn_sum_rows(rows, n_rows, c, sums)
+            ops.bn_finalize_devcount(cnt, c, affine, v)
         torch.cuda.synchronize()
         outs.append(dict(scale=scale, shift=shift, mean=mean, invstd=invstd, rmean=rm, rvar=rv, totals=sums[: 2 * c].clone()))
     for k_ in outs[0]:
@@ -614,7 +604,6 @@ def test_maxpool_backward_on_a_slice_of_the_spp_gradient(dev, dtype, k):
     then accumulate: the bits of the pitch == c launches, both forms the same bits, and -- fp32, tie-free -- torch's max_pool2d autograd (the 1e-6 of
     test_maxpool_backward_indexed_form)"""
     _lib, ops = _ops()
-    L = _lib.lib()
     n, h, w, c = 3, 11, 17, 40
     j = (5, 9, 13).index(k)
     g = torch.Generator().manual_seed(23)
@@ -643,8 +632,7 @@ def test_maxpool_backward_on_a_slice_of_the_spp_gradient(dev, dtype, k):
             outs = []
             for acc in (False, True):
                 if form == "gather":
-                    a, b, d = xb.v.y3(), gv.y3(), db.v.y3()
-                    _lib.check(L.y3_maxpool2d_bwd(C.byref(a), C.byref(b), C.byref(d), ops.dtype_code(dtype), k, 1, k // 2, 0, 0, int(acc), ops.stream_ptr()), "y3_maxpool2d_bwd")
+                    ops.maxpool2d_bwd_gather(xb.v, gv, db.v, k, 1, k // 2, accumulate=acc)
                 else:
                     ops.maxpool2d_bwd(xb.v, gv, db.v, k, 1, k // 2, accumulate=acc)
                 torch.cuda.synchronize()
@@ -706,9 +694,7 @@ def test_stem_bn_bwd_wgrad_on_sliced_views(dev, dtype, shape, act):
     sums = ops.bn_scratch(cout, dev)
     duv = ops.View.alloc(n, h, w, cout, dtype, dev)
     dg0, db0 = torch.empty(cout, device=dev), torch.empty(cout, device=dev)
-    ut, gt, dt_ = ub.v.y3(), gb.v.y3(), duv.y3()
-    _lib.check(_lib.lib().y3_bn_act_bwd(C.byref(ut), C.byref(gt), scale.data_ptr(), shift.data_ptr(), mean_d.data_ptr(), invstd_d.data_ptr(), ops.dtype_code(dtype), a,
-                                        sums.data_ptr(), C.byref(dt_), dg0.data_ptr(), db0.data_ptr(), ops.stream_ptr()), "y3_bn_act_bwd")
+    ops.bn_act_bwd(ub.v, gb.v, ops.BnVecs(scale, shift, mean_d, invstd_d, sums), a, duv, dg0, db0)
     xin = ops.View.alloc(n, h, w, 8, dtype, dev)
     ops.nchw_to_nhwc(xd, xin)
     dw0, _ = ops.conv2d_wgrad(xin, duv, 3, 1, cout, cin)
@@ -750,8 +736,7 @@ def test_upsample2x_bwd(dev, dtype, accumulate, shape):
         xb = Buf(ops, dev, dtype, (n, h, w, c), px, 7.0)
         xb.v.as_nhwc().copy_(old.to(dev)) if accumulate else xb.v.as_nhwc().fill_(NAN)   # (the write form must not read dx)
         xb.snap()
-        gt, xt = gb.v.y3(), xb.v.y3()
-        _lib.check(_lib.lib().y3_upsample2x_bwd(C.byref(gt), C.byref(xt), ops.dtype_code(dtype), accumulate, ops.stream_ptr()), "y3_upsample2x_bwd")
+        ops.upsample2x_bwd(gb.v, xb.v, accumulate)
         torch.cuda.synchronize()
         gb.check("upsample2x_bwd dy")
         xb.check("upsample2x_bwd dx", written=True)
@@ -786,8 +771,7 @@ def test_detect_raw_bwd_is_a_permutation(dev, dtype, no, ny, nx):
         hb = Buf(ops, dev, dtype, (bs, ny, nx, cpad), pads, 7.0)
         hb.v.as_nhwc().fill_(NAN)
         hb.snap()
-        ht = hb.v.y3()
-        _lib.check(_lib.lib().y3_detect_raw_bwd(graw.data_ptr(), ops.dtype_code(dtype), bs, na, ny, nx, no, C.byref(ht), ops.stream_ptr()), "y3_detect_raw_bwd")
+        ops.detect_raw_bwd(graw, na, no, hb.v)
         torch.cuda.synchronize()
         hb.check("detect_raw_bwd ghead", written=True)
         got = hb.nhwc()

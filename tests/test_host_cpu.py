@@ -83,6 +83,13 @@ def test_product_never_imports_the_oracle():
         assert "oracle" not in f.read_text().replace("# oracle", ""), f
 
 
+def test_training_launches_go_through_ops():
+    """train_engine.py and parallel.py marshal no C call themselves: every launch is an ops wrapper, the one place that has to agree with _lib._SIGNATURES"""
+    for name in ("train_engine.py", "parallel.py"):
+        src = (ROOT / "yolov3_amd" / name).read_text()
+        assert "ctypes" not in src and ".lib()" not in src, name
+
+
 def test_state_dict_layout_matches_reference_keys(golden_dir):
     """keys/shapes must equal the reference's: checked against the oracle's seeded state dict, which
     tests/golden/make_golden.py loads strict=True into the unmodified reference model."""

@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import math
 
@@ -81,6 +82,14 @@ class View:
         return View(torch.empty(n * h * w * pitch, dtype=dtype, device=device), n, h, w, c, pitch, 0)
 
 
+def _ptr(t: torch.Tensor | None):
+    return t.data_ptr() if t is not None else None
+
+
+def _ref(v: View | None):
+    return C.byref(v.y3()) if v is not None else None
+
+
 def packed_filter_elems(cout: int, cin: int, k: int) -> int:
     return int(_lib.lib().y3_packed_filter_elems(cout, cin, k))
 
@@ -145,9 +154,8 @@ def stem_conv(x_nchw: torch.Tensor, filt: torch.Tensor, bias: torch.Tensor, y: V
     require_gpu(x_nchw, "stem_conv")
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    yt = y.y3()
     check(_lib.lib().y3_stem_conv_fwd(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                      dtype_code(y.buf.dtype), _lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE, C.byref(yt), stream_ptr()), "y3_stem_conv_fwd")
+                                      dtype_code(y.buf.dtype), _lib.Y3_ACT_SILU if act else _lib.Y3_ACT_NONE, _ref(y), stream_ptr()), "y3_stem_conv_fwd")
 
 
 def stem_conv_stats_rows(n: int, h: int, w: int) -> int:
@@ -159,10 +167,9 @@ def stem_conv_stats(x_nchw: torch.Tensor, filt: torch.Tensor, bias: torch.Tensor
     require_gpu(x_nchw, "stem_conv_stats")
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    yt = y.y3()
     rows = C.c_int64(0)
     check(_lib.lib().y3_stem_conv_fwd_stats(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                            dtype_code(y.buf.dtype), _lib.Y3_ACT_NONE, C.byref(yt), stat_rows.data_ptr(), int(capacity_rows), C.byref(rows), stream_ptr()),
+                                            dtype_code(y.buf.dtype), _lib.Y3_ACT_NONE, _ref(y), stat_rows.data_ptr(), int(capacity_rows), C.byref(rows), stream_ptr()),
           "y3_stem_conv_fwd_stats")
     return int(rows.value)
 
@@ -172,9 +179,8 @@ def stem_conv_stats_only(x_nchw: torch.Tensor, filt: torch.Tensor, like: View, s
     require_gpu(x_nchw, "stem_conv_stats_only")
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    lt = like.y3()
     rows = C.c_int64(0)
-    check(_lib.lib().y3_stem_conv_stats_only(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), dtype_code(like.buf.dtype), C.byref(lt),
+    check(_lib.lib().y3_stem_conv_stats_only(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), dtype_code(like.buf.dtype), _ref(like),
                                              stat_rows.data_ptr(), int(capacity_rows), C.byref(rows), stream_ptr()), "y3_stem_conv_stats_only")
     return int(rows.value)
 
@@ -184,9 +190,8 @@ def stem_conv_bn(x_nchw: torch.Tensor, filt: torch.Tensor, scale: torch.Tensor, 
     require_gpu(x_nchw, "stem_conv_bn")
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    yt = y.y3()
     check(_lib.lib().y3_stem_conv_fwd_bn(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), scale.data_ptr(), shift.data_ptr(), int(act),
-                                         dtype_code(y.buf.dtype), C.byref(yt), stream_ptr()), "y3_stem_conv_fwd_bn")
+                                         dtype_code(y.buf.dtype), _ref(y), stream_ptr()), "y3_stem_conv_fwd_bn")
 
 
 def stem_bn_bwd_wgrad_recompute(x_nchw: torch.Tensor, filt: torch.Tensor, dy: View, scale, shift, mean, invstd, act: int, sums: torch.Tensor, dgamma, dbeta, dw: torch.Tensor,
@@ -197,8 +202,7 @@ def stem_bn_bwd_wgrad_recompute(x_nchw: torch.Tensor, filt: torch.Tensor, dy: Vi
     n, c, h, w = x.shape
     if dw.dtype != torch.float32 or not dw.is_contiguous() or tuple(dw.shape) != (32, c, 3, 3):
         raise TypeError("stem_bn_bwd_wgrad_recompute: dw must be a contiguous fp32 (32, cin, 3, 3) tensor")
-    gt = dy.y3()
-    check(_lib.lib().y3_stem_bn_bwd_wgrad_recompute(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), C.byref(gt), scale.data_ptr(), shift.data_ptr(),
+    check(_lib.lib().y3_stem_bn_bwd_wgrad_recompute(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt.data_ptr(), _ref(dy), scale.data_ptr(), shift.data_ptr(),
                                                     mean.data_ptr(), invstd.data_ptr(), dtype_code(dy.buf.dtype), int(act), sums.data_ptr(),
                                                     dgamma.data_ptr() if dgamma is not None else None, dbeta.data_ptr() if dbeta is not None else None, dw.data_ptr(),
                                                     workspace.data_ptr(), workspace.numel(), stream_ptr()), "y3_stem_bn_bwd_wgrad_recompute")
@@ -217,8 +221,7 @@ def stem_bn_bwd_wgrad(x_nchw: torch.Tensor, u: View, dy: View, scale, shift, mea
     n, c, h, w = x.shape
     if dw.dtype != torch.float32 or not dw.is_contiguous() or tuple(dw.shape) != (32, c, 3, 3):
         raise TypeError("stem_bn_bwd_wgrad: dw must be a contiguous fp32 (32, cin, 3, 3) tensor")
-    ut, gt = u.y3(), dy.y3()
-    check(_lib.lib().y3_stem_bn_bwd_wgrad(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), C.byref(ut), C.byref(gt), scale.data_ptr(), shift.data_ptr(),
+    check(_lib.lib().y3_stem_bn_bwd_wgrad(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), _ref(u), _ref(dy), scale.data_ptr(), shift.data_ptr(),
                                           mean.data_ptr(), invstd.data_ptr(), dtype_code(u.buf.dtype), int(act), sums.data_ptr(),
                                           dgamma.data_ptr() if dgamma is not None else None, dbeta.data_ptr() if dbeta is not None else None, dw.data_ptr(),
                                           workspace.data_ptr(), workspace.numel(), stream_ptr()), "y3_stem_bn_bwd_wgrad")
@@ -236,9 +239,8 @@ def pack_filter_dgrad(w_oihw: torch.Tensor, cout: int, cin: int, dtype: torch.dt
 
 def bneck_pair(x: View, filt1: torch.Tensor, bias1: torch.Tensor, act1: bool, filt2: torch.Tensor, bias2: torch.Tensor, act2: bool, add: bool, y: View):
     """Bottleneck(C, C), C = 64 or 128: y = [x +] cv2(cv1(x)), cv1 1x1 C -> C/2, cv2 3x3 C/2 -> C, the intermediate kept in LDS (csrc/stem.hip)."""
-    xt, yt = x.y3(), y.y3()
-    check(_lib.lib().y3_bneck_pair_fwd(C.byref(xt), filt1.data_ptr(), bias1.data_ptr(), _lib.Y3_ACT_SILU if act1 else _lib.Y3_ACT_NONE, filt2.data_ptr(), bias2.data_ptr(),
-                                       _lib.Y3_ACT_SILU if act2 else _lib.Y3_ACT_NONE, int(bool(add)), dtype_code(x.buf.dtype), C.byref(yt), stream_ptr()), "y3_bneck_pair_fwd")
+    check(_lib.lib().y3_bneck_pair_fwd(_ref(x), filt1.data_ptr(), bias1.data_ptr(), _lib.Y3_ACT_SILU if act1 else _lib.Y3_ACT_NONE, filt2.data_ptr(), bias2.data_ptr(),
+                                       _lib.Y3_ACT_SILU if act2 else _lib.Y3_ACT_NONE, int(bool(add)), dtype_code(x.buf.dtype), _ref(y), stream_ptr()), "y3_bneck_pair_fwd")
 
 
 def last_conv_variant() -> str:
@@ -303,24 +305,113 @@ def bn_scratch(c: int, device) -> torch.Tensor:
     return torch.zeros((1 + BN_PARTIAL_ROWS) * 2 * c, dtype=torch.float64, device=device)
 
 
+class BnVecs(NamedTuple):
+    """the five per-layer device vectors of the BatchNorm calls: fp32 (C,) scale, shift, mean, invstd and the fp64 scratch bn_scratch (bn_act_fwd reads the first two alone)"""
+    scale: torch.Tensor
+    shift: torch.Tensor
+    mean: torch.Tensor | None = None
+    invstd: torch.Tensor | None = None
+    sums: torch.Tensor | None = None
+
+    @classmethod
+    def alloc(cls, c: int, device) -> "BnVecs":
+        return cls(*(torch.empty(c, dtype=torch.float32, device=device) for _ in range(4)), bn_scratch(c, device))
+
+
+class BnAffine(NamedTuple):
+    """what a finalize call reads of its nn.BatchNorm2d: device fp32 gamma / beta, eps, momentum, the running statistics it updates in place (None: not tracked)"""
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    eps: float = 1e-3       # (the reference's values: models/common.py:75)
+    momentum: float = 0.03
+    running_mean: torch.Tensor | None = None
+    running_var: torch.Tensor | None = None
+
+
+def bn_affine(bn, *explicit) -> BnAffine:
+    """bn_affine(module): the BnAffine of an nn.BatchNorm2d; bn_affine(gamma, beta[, eps, momentum, running_mean, running_var]): of explicit tensors (tests)"""
+    if isinstance(bn, torch.Tensor):
+        return BnAffine(bn, *explicit)
+    return BnAffine(bn.weight, bn.bias, float(bn.eps), float(bn.momentum), bn.running_mean, bn.running_var)
+
+
+def _finalize_tail(a: BnAffine, v: BnVecs):
+    """the eleven trailing arguments of y3_bn_finalize, y3_bn_stats_finalize, y3_bn_finalize_rows and y3_bn_finalize_devcount"""
+    assert v.sums is not None, "a BatchNorm finalize call needs all five BnVecs vectors, not the (scale, shift) pair of bn_act_fwd"
+    return (a.gamma.data_ptr(), a.beta.data_ptr(), a.eps, a.momentum, _ptr(a.running_mean), _ptr(a.running_var), v.scale.data_ptr(), v.shift.data_ptr(), v.mean.data_ptr(),
+            v.invstd.data_ptr(), stream_ptr())
+
+
+def _bwd_head(u: View, dy: View, v: BnVecs, act: int):
+    """the nine leading arguments every y3_bn_act_bwd* entry point shares"""
+    assert v.sums is not None, "a BatchNorm backward call needs all five BnVecs vectors, not the (scale, shift) pair of bn_act_fwd"
+    return (_ref(u), _ref(dy), v.scale.data_ptr(), v.shift.data_ptr(), v.mean.data_ptr(), v.invstd.data_ptr(), dtype_code(u.buf.dtype), int(act), v.sums.data_ptr())
+
+
+def bn_stats(u: View, sums: torch.Tensor):
+    """sums[0 .. 2C) = per-channel (sum, sum of squares) of u"""
+    check(_lib.lib().y3_bn_stats(_ref(u), dtype_code(u.buf.dtype), sums.data_ptr(), stream_ptr()), "y3_bn_stats")
+
+
+def bn_stats_finalize(u: View, affine: BnAffine, v: BnVecs):
+    """scale / shift / mean / invstd of v (and the running statistics) from the batch statistics of u"""
+    check(_lib.lib().y3_bn_stats_finalize(_ref(u), dtype_code(u.buf.dtype), v.sums.data_ptr(), *_finalize_tail(affine, v)), "y3_bn_stats_finalize")
+
+
+def bn_finalize_rows(rows: torch.Tensor, n_rows: int, count: int, c: int, affine: BnAffine, v: BnVecs):
+    """the same from the `n_rows` statistics rows a conv epilogue wrote (conv2d_stats, stem_conv_stats, conv1x1_bnin_stats)"""
+    check(_lib.lib().y3_bn_finalize_rows(rows.data_ptr(), int(n_rows), int(count), int(c), v.sums.data_ptr(), *_finalize_tail(affine, v)), "y3_bn_finalize_rows")
+
+
+def bn_sum_rows(rows: torch.Tensor, n_rows: int, c: int, sums: torch.Tensor):
+    """sums[0 .. 2C) = the column sums of the statistics rows (SyncBatchNorm: what a rank contributes to the all-reduce)"""
+    check(_lib.lib().y3_bn_sum_rows(rows.data_ptr(), int(n_rows), int(c), sums.data_ptr(), stream_ptr()), "y3_bn_sum_rows")
+
+
+def bn_finalize_devcount(count_dev: torch.Tensor, c: int, affine: BnAffine, v: BnVecs):
+    """the same from the totals in v.sums[0 .. 2C) and an element count in device memory (fp64: both all-reduced over a SyncBatchNorm group)"""
+    check(_lib.lib().y3_bn_finalize_devcount(v.sums.data_ptr(), count_dev.data_ptr(), int(c), *_finalize_tail(affine, v)), "y3_bn_finalize_devcount")
+
+
+def bn_act_fwd(u: View, v: BnVecs, act: int, y: View, residual: View | None = None):
+    """y = act(scale u + shift) (+ residual)"""
+    check(_lib.lib().y3_bn_act_fwd(_ref(u), v.scale.data_ptr(), v.shift.data_ptr(), _ref(residual), _ref(y), dtype_code(u.buf.dtype), int(act), stream_ptr()), "y3_bn_act_fwd")
+
+
+def bn_act_bwd(u: View, dy: View, v: BnVecs, act: int, du: View, dgamma, dbeta, gres: View | None = None, gres_accumulate: bool = False):
+    """du, dgamma, dbeta of y = act(bn(u)) (+ residual); with `gres` the residual's gradient is written (or accumulated) on the pass that reads dy anyway"""
+    head = _bwd_head(u, dy, v, act)
+    if gres is None:
+        check(_lib.lib().y3_bn_act_bwd(*head, _ref(du), _ptr(dgamma), _ptr(dbeta), stream_ptr()), "y3_bn_act_bwd")
+    else:
+        check(_lib.lib().y3_bn_act_bwd_res(*head, _ref(du), _ptr(dgamma), _ptr(dbeta), _ref(gres), int(bool(gres_accumulate)), stream_ptr()), "y3_bn_act_bwd_res")
+
+
+def bn_act_bwd_reduce(u: View, dy: View, v: BnVecs, act: int, dgamma, dbeta):
+    """first half of bn_act_bwd: this rank's reduction totals into v.sums[0 .. 2C), dgamma, dbeta (SyncBatchNorm all-reduces the totals before the second half)"""
+    check(_lib.lib().y3_bn_act_bwd_reduce(*_bwd_head(u, dy, v, act), _ptr(dgamma), _ptr(dbeta), stream_ptr()), "y3_bn_act_bwd_reduce")
+
+
+def bn_act_bwd_apply(u: View, dy: View, v: BnVecs, act: int, du: View, gres: View | None = None, gres_accumulate: bool = False):
+    """second half of bn_act_bwd: du (and the residual's gradient) from the means in v.sums[2C .. 4C)"""
+    check(_lib.lib().y3_bn_act_bwd_apply(*_bwd_head(u, dy, v, act), _ref(du), _ref(gres), int(bool(gres_accumulate)), stream_ptr()), "y3_bn_act_bwd_apply")
+
+
 def nchw_to_nhwc(src: torch.Tensor, out: View, divisor: float = 1.0):
     require_gpu(src, "nchw_to_nhwc")
     src = src.contiguous()
     n, c, h, w = src.shape
-    ot = out.y3()
-    check(_lib.lib().y3_nchw_to_nhwc(src.data_ptr(), dtype_code(src.dtype), n, c, h, w, float(divisor), dtype_code(out.buf.dtype), C.byref(ot), stream_ptr()), "y3_nchw_to_nhwc")
+    check(_lib.lib().y3_nchw_to_nhwc(src.data_ptr(), dtype_code(src.dtype), n, c, h, w, float(divisor), dtype_code(out.buf.dtype), _ref(out), stream_ptr()), "y3_nchw_to_nhwc")
 
 
 def nhwc_to_nchw(src: View) -> torch.Tensor:
     dst = torch.empty(src.n, src.c, src.h, src.w, dtype=src.buf.dtype, device=src.buf.device)
-    st = src.y3()
-    check(_lib.lib().y3_nhwc_to_nchw(C.byref(st), dtype_code(src.buf.dtype), dst.data_ptr(), stream_ptr()), "y3_nhwc_to_nchw")
+    check(_lib.lib().y3_nhwc_to_nchw(_ref(src), dtype_code(src.buf.dtype), dst.data_ptr(), stream_ptr()), "y3_nhwc_to_nchw")
     return dst
 
 
 def maxpool2d(x: View, y: View, k: int, stride: int, pad: int, zpad_r: int = 0, zpad_b: int = 0):
-    xt, yt = x.y3(), y.y3()
-    check(_lib.lib().y3_maxpool2d(C.byref(xt), C.byref(yt), dtype_code(x.buf.dtype), k, stride, pad, zpad_r, zpad_b, stream_ptr()), "y3_maxpool2d")
+    check(_lib.lib().y3_maxpool2d(_ref(x), _ref(y), dtype_code(x.buf.dtype), k, stride, pad, zpad_r, zpad_b, stream_ptr()), "y3_maxpool2d")
 
 
 def maxpool2d_bwd(x: View, dy: View, dx: View, k: int, stride: int, pad: int, zpad_r: int = 0, zpad_b: int = 0, accumulate: bool = False):
@@ -332,31 +423,41 @@ def maxpool2d_bwd(x: View, dy: View, dx: View, k: int, stride: int, pad: int, zp
                                          stream_ptr()), "y3_maxpool2d_bwd_ws")
 
 
+def maxpool2d_bwd_gather(x: View, dy: View, dx: View, k: int, stride: int, pad: int, zpad_r: int = 0, zpad_b: int = 0, accumulate: bool = False):
+    """maxpool2d_bwd through the one-pass gather form (k^2 windows of k^2 elements per input element: the training plans run the indexed form; tests compare the two)"""
+    check(_lib.lib().y3_maxpool2d_bwd(_ref(x), _ref(dy), _ref(dx), dtype_code(x.buf.dtype), k, stride, pad, zpad_r, zpad_b, int(bool(accumulate)), stream_ptr()), "y3_maxpool2d_bwd")
+
+
 def spp_pyramid(x: View, y3c: View):
-    xt, yt = x.y3(), y3c.y3()
-    check(_lib.lib().y3_spp_pyramid(C.byref(xt), C.byref(yt), dtype_code(x.buf.dtype), stream_ptr()), "y3_spp_pyramid")
+    check(_lib.lib().y3_spp_pyramid(_ref(x), _ref(y3c), dtype_code(x.buf.dtype), stream_ptr()), "y3_spp_pyramid")
 
 
 def upsample2x(x: View, y: View):
-    xt, yt = x.y3(), y.y3()
-    check(_lib.lib().y3_upsample2x(C.byref(xt), C.byref(yt), dtype_code(x.buf.dtype), stream_ptr()), "y3_upsample2x")
+    check(_lib.lib().y3_upsample2x(_ref(x), _ref(y), dtype_code(x.buf.dtype), stream_ptr()), "y3_upsample2x")
+
+
+def upsample2x_bwd(dy: View, dx: View, accumulate: bool):
+    check(_lib.lib().y3_upsample2x_bwd(_ref(dy), _ref(dx), dtype_code(dy.buf.dtype), int(bool(accumulate)), stream_ptr()), "y3_upsample2x_bwd")
 
 
 def copy_slice(x: View, y: View):
-    xt, yt = x.y3(), y.y3()
-    check(_lib.lib().y3_copy_slice(C.byref(xt), C.byref(yt), dtype_code(x.buf.dtype), stream_ptr()), "y3_copy_slice")
+    check(_lib.lib().y3_copy_slice(_ref(x), _ref(y), dtype_code(x.buf.dtype), stream_ptr()), "y3_copy_slice")
 
 
 def detect_decode(head: View, na: int, no: int, anchors_px, stride: float, raw: torch.Tensor | None, z: torch.Tensor | None, row_offset: int, total_rows: int):
-    ht = head.y3()
     arr = (C.c_float * (na * 2))(*[float(v) for v in anchors_px])
     check(
         _lib.lib().y3_detect_decode(
-            C.byref(ht), dtype_code(head.buf.dtype), na, no, arr, float(stride), raw.data_ptr() if raw is not None else None, z.data_ptr() if z is not None else None,
+            _ref(head), dtype_code(head.buf.dtype), na, no, arr, float(stride), raw.data_ptr() if raw is not None else None, z.data_ptr() if z is not None else None,
             row_offset, total_rows, stream_ptr(),
         ),
         "y3_detect_decode",
     )
+
+
+def detect_raw_bwd(graw: torch.Tensor, na: int, no: int, ghead: View):
+    """ghead[b, y, x, a * no + o] = graw[b, a, y, x, o] (contiguous, ghead's dtype); the pad channels of ghead are zeroed"""
+    check(_lib.lib().y3_detect_raw_bwd(graw.data_ptr(), dtype_code(graw.dtype), ghead.n, na, ghead.h, ghead.w, no, _ref(ghead), stream_ptr()), "y3_detect_raw_bwd")
 
 
 _nms_ws_cache: dict = {}
@@ -608,9 +709,8 @@ def stem_pair(x_nchw: torch.Tensor, filt0: torch.Tensor, bias0: torch.Tensor, ac
     require_gpu(x_nchw, "stem_pair")
     x = x_nchw.contiguous()
     n, c, h, w = x.shape
-    yt = y.y3()
     check(_lib.lib().y3_stem_pair_fwd(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, float(divisor), filt0.data_ptr(), bias0.data_ptr(), _lib.Y3_ACT_SILU if act0 else _lib.Y3_ACT_NONE,
-                                      filt1.data_ptr(), bias1.data_ptr(), _lib.Y3_ACT_SILU if act1 else _lib.Y3_ACT_NONE, dtype_code(y.buf.dtype), C.byref(yt), stream_ptr()),
+                                      filt1.data_ptr(), bias1.data_ptr(), _lib.Y3_ACT_SILU if act1 else _lib.Y3_ACT_NONE, dtype_code(y.buf.dtype), _ref(y), stream_ptr()),
           "y3_stem_pair_fwd")
 
 
@@ -623,3 +723,8 @@ def pack_filter_pair(w_oihw: torch.Tensor, cout: int, cin: int, dtype: torch.dty
     dg = torch.empty(packed_filter_elems(cin, cout, k), dtype=dtype, device=w.device)
     check(_lib.lib().y3_pack_filter_pair(w.data_ptr(), co, ci, k, cout, cin, dtype_code(dtype), fwd.data_ptr(), dg.data_ptr(), stream_ptr()), "y3_pack_filter_pair")
     return fwd, dg
+
+
+def shard_mean(parts: torch.Tensor, n_parts: int, n: int, scale: float, out: torch.Tensor):
+    """out[i] = scale * (parts[0][i] + ... + parts[n_parts - 1][i]), fp32, summed in part order (parallel.GradBuckets: the owner's mean of its gradient shard)"""
+    check(_lib.lib().y3_shard_mean(parts.data_ptr(), int(n_parts), int(n), float(scale), out.data_ptr(), stream_ptr()), "y3_shard_mean")

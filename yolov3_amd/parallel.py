@@ -218,9 +218,9 @@ class GradBuckets:
         mine = flat[rank * n : (rank + 1) * n]
         if flat.is_cuda and flat.dtype == torch.float32:
             # the owner's sum: rank order 0 .. P-1, times 1 / P, one launch of the library (csrc/optim.hip::shard_mean_kernel) on the current (side) stream
-            from . import _lib, ops
+            from . import ops
 
-            _lib.check(_lib.lib().y3_shard_mean(recv.data_ptr(), P, n, 1.0 / P, mine.data_ptr(), ops.stream_ptr()), "y3_shard_mean")
+            ops.shard_mean(recv, P, n, 1.0 / P, mine)
         else:                        # host tensors (the gloo tests) and reduced wire dtypes: the same sum in the same order with torch ops
             parts = recv.view(P, n)
             acc = parts[0].clone() if P > 1 else parts[0]
