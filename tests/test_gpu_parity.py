@@ -640,6 +640,21 @@ def test_layout_and_pool_kernels(dev, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ decode
+def _decode_close(zc, ref, dtype):
+    """the decode criterion (shared with tests/test_gpu_class_counts.py): `zc` the device's z and `ref` the reference's, both as fp32, computed in `dtype`"""
+    if dtype == torch.float32:
+        # sigmoid differs by <= 2 ulp between libm implementations; everything else is exact
+        torch.testing.assert_close(zc, ref, rtol=3e-6, atol=1e-6)
+    else:
+        # every op is rounded through fp16 like torch does; a 1-ulp sigmoid difference may flip a rounding
+        # (bf16: the same statement in its own ulp, 2^-7 of the value, smallest normal 2^-126)
+        tiny, eps = (2.0**-14, 2.0**-10) if dtype == torch.float16 else (2.0**-126, 2.0**-7)
+        ulp = torch.maximum(ref.abs(), torch.tensor(tiny)) * eps
+        diff = (zc - ref).abs()
+        assert (diff > 2 * ulp).sum().item() == 0, f"max diff {diff.max()}"
+        assert (diff > 0).float().mean().item() < 2e-3, "too many fp16 rounding flips"
+
+
 @pytest.mark.parametrize("key,dtype,nc", [("nc80-float32", torch.float32, 80), ("nc80-float16", torch.float16, 80), ("nc3-float16", torch.float16, 3)])
 def test_detect_decode_vs_reference_golden(dev, golden_dir, key, dtype, nc):
     from yolov3_amd import Detect
@@ -663,15 +678,7 @@ def test_detect_decode_vs_reference_golden(dev, golden_dir, key, dtype, nc):
     for r, x in zip(raw, xs):
         exp = x.to(dtype).view(2, 3, no, x.shape[2], x.shape[3]).permute(0, 1, 3, 4, 2)
         assert torch.equal(r.cpu(), exp), "raw (bs,na,ny,nx,no) layout mismatch"
-    if dtype == torch.float32:
-        # sigmoid differs by <= 2 ulp between libm implementations; everything else is exact
-        torch.testing.assert_close(zc, ref, rtol=3e-6, atol=1e-6)
-    else:
-        # every op is rounded through fp16 like torch does; a 1-ulp sigmoid difference may flip a rounding
-        ulp = torch.maximum(ref.abs(), torch.tensor(2.0**-14)) * 2.0**-10
-        diff = (zc - ref).abs()
-        assert (diff > 2 * ulp).sum().item() == 0, f"max diff {diff.max()}"
-        assert (diff > 0).float().mean().item() < 2e-3, "too many fp16 rounding flips"
+    _decode_close(zc, ref, dtype)
 
 
 @pytest.mark.parametrize("cin,cout,hw,res", [(128, 256, 40, True), (256, 512, 20, False), (512, 1024, 20, True)])

@@ -1,7 +1,8 @@
 """The oracle against the UNMODIFIED reference on more seeded cases than tests/test_oracle_golden.py holds -- a wider pin: 120 val
 matches, 60 letterbox geometries, 4 NMS regimes, 8 loss heads / hyp variants, 2 x 3 autobalance calls.  The reference's outputs on these
 cases are recorded in tests/golden/reference_cases.pt (tests/golden/make_golden.py cases); the inputs are regenerated here from the same
-seeds and checked against the recorded checksums.  CPU only."""
+seeds and checked against the recorded checksums.  tests/golden/class_counts.pt (tests/golden/make_class_counts_golden.py) adds
+ComputeLoss on heads with 1, 2, 3 and 60 classes and Detect with 1 and 2.  CPU only."""
 import pytest
 import torch
 import yaml
@@ -143,3 +144,72 @@ def test_autobalance_oracle_equals_reference_over_consecutive_calls(ref):
             torch.testing.assert_close(loss, call["loss"], rtol=1e-6, atol=1e-6)
             torch.testing.assert_close(torch.tensor(balance), torch.tensor(call["balance"]), rtol=1e-6, atol=1e-7)
         assert abs(balance[ssi] - 1.0) < 1e-9 and balance != [4.0, 1.0, 0.4][: len(balance)]
+
+
+# ------------------------------------------------------------------------------------------------ class counts 1 / 2 / 3 / 60 (tests/golden/make_class_counts_golden.py)
+def dense_level(g):
+    """one level's gradient recorded as its objectness plane (channel 4) and the sparse rest"""
+    t = dense(g["rest"])
+    t[..., 4] = g["obj"]
+    return t
+
+
+@pytest.fixture(scope="module")
+def ref_cc(golden_dir):
+    return torch.load(golden_dir / "class_counts.pt")
+
+
+def test_compute_loss_oracle_equals_reference_at_small_class_counts(ref_cc):
+    """ComputeLoss (reference utils/loss.py:98-244) == oracle.compute_loss -- value, items and d loss / d predictions -- on yolov3-tiny heads with 1 and 2 classes
+    (plain, focal, label smoothing, both) and yolov3 heads with 1, 3 and 60 classes.  One class: the reference adds no class loss (`if self.nc > 1`, :164), so items[2]
+    is 0 and no class logit has a gradient."""
+    import class_count_cases as cc
+
+    heads = [("yolov3-tiny", 1, 96, 2), ("yolov3-tiny", 2, 96, 2), ("yolov3-tiny", 2, 96, 2), ("yolov3-tiny", 2, 96, 2), ("yolov3-tiny", 2, 96, 2),
+             ("yolov3", 1, 64, 2), ("yolov3", 3, 64, 2), ("yolov3", 60, 64, 2)]
+    overs = [{}, {}, dict(fl_gamma=1.5), dict(label_smoothing=0.1), dict(fl_gamma=1.5, label_smoothing=0.1), {}, {}, {}]
+    assert [tuple(r["head"]) for r in ref_cc["loss"]] == heads and [r["over"] for r in ref_cc["loss"]] == overs
+    for i, ((name, nc, hw, bs), over, rec) in enumerate(zip(heads, overs, ref_cc["loss"])):
+        layers, save, anchors, nc_v = yo.parse_cfg(yaml.safe_load(open(CFG / f"{name}.yaml")), 3, nc)
+        strides = yo.model_strides(layers)
+        hyp = cc.scaled_hyp(len(strides), nc, hw, over)
+        assert hyp == rec["hyp"], i
+        shapes = [(bs, 3, hw // int(s), hw // int(s), nc + 5) for s in strides]
+        seed, tg = cc.pick_targets(bs, nc, shapes, rec["anchors"], rec["tg_seed"])
+        assert seed == rec["tg_seed"] and checksum(tg) == rec["tg_sum"], f"input drift, head {i}"
+        assert set(tg[:, 1].long().tolist()) >= ({nc - 1} if nc > 4 else set(range(nc)))
+        p = [t.requires_grad_(True) for t in yo.synth_raw_predictions(shapes, seed=rec["p_seed"])]
+        assert sum(checksum(t.detach()) for t in p) == rec["p_sum"], f"input drift, head {i}"
+        loss, items, _ = yo.compute_loss(p, tg, rec["anchors"].clone(), hyp, nc)
+        loss.backward()
+        torch.testing.assert_close(loss, rec["loss"], rtol=1e-6, atol=1e-6)
+        torch.testing.assert_close(items, rec["items"], rtol=1e-6, atol=1e-6)
+        assert len(p) == len(rec["grads"])
+        for a, b in zip(p, rec["grads"]):
+            want = dense_level(b)
+            torch.testing.assert_close(a.grad, want, rtol=1e-5, atol=1e-8)
+            assert (want[..., :4].abs().sum(-1) > 0).any(), "a level without a matched cell pins nothing but the objectness plane"
+            if nc == 1:
+                assert not a.grad[..., 5].any() and not want[..., 5].any()
+        if nc == 1:
+            assert float(rec["items"][2]) == 0.0 and float(items[2]) == 0.0
+            torch.testing.assert_close(loss, (items[0] + items[1]).reshape(1) * bs, rtol=1e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize("nc,dtype", [(1, torch.float32), (1, torch.float16), (2, torch.float32), (2, torch.float16)])
+def test_decode_oracle_equals_reference_at_one_and_two_classes(ref_cc, nc, dtype):
+    """The eval branch of Detect (reference models/yolo.py:98-110) on yolov3-tiny's two levels with no = 6 and 7 == oracle.detect_decode."""
+    gold = ref_cc["decode"][f"nc{nc}-{str(dtype).split('.')[-1]}"]
+    no = nc + 5
+    g = torch.Generator().manual_seed(gold["seed"])
+    xs = [torch.randn(2, 3 * no, s, s + 1, generator=g) * 2.0 for s in gold["sizes"]]
+    if dtype == torch.float16:
+        xs = [x.half() for x in xs]
+    assert sum(checksum(x) for x in xs) == gold["in_sum"], "input drift"
+    raw = [x.view(2, 3, no, x.shape[2], x.shape[3]).permute(0, 1, 3, 4, 2).contiguous() for x in xs]
+    z = yo.detect_decode(raw, gold["anchors_grid"].to(dtype), torch.tensor(gold["strides"]).to(dtype))
+    assert z.dtype == gold["z"].dtype and z.shape == gold["z"].shape == (2, 3 * sum(s * (s + 1) for s in gold["sizes"]), no)
+    if dtype == torch.float32:
+        torch.testing.assert_close(z, gold["z"], rtol=1e-6, atol=1e-6)
+    else:   # (every op rounded through fp16 on both sides, as tests/test_oracle_golden.py::test_decode_matches_reference holds the other class counts)
+        assert torch.equal(z, gold["z"])
