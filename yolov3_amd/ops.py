@@ -666,13 +666,21 @@ def conv2d_stats(x: View, filt: torch.Tensor, bias: torch.Tensor, y: View, k: in
 
 class PackJobs:
     """Every layer's filter banks in one launch (y3_pack_filter_jobs): `add` registers a layer and returns its persistent (forward bank,
-    data-gradient bank) tensors, `run` re-packs all of them from the current fp32 weights.  The job table lives on the device and is
-    rebuilt only when a weight tensor moved (data_ptr changed)."""
+    data-gradient bank) tensors, `run` re-packs them from the current fp32 weights.  The job table lives on the device and is
+    rebuilt only when a weight tensor moved (data_ptr changed).
+
+    `run(select)` packs a subset: `select` is a sequence of (job index, always).  A job with `always` (a weight that is being trained: the optimizer may have
+    written it since the last forward) is packed at every call; one without (a frozen weight) is packed when its banks do not hold the tensor's current
+    (data_ptr, _version) -- once, and again after load_state_dict or any other in-place write that torch's version counter sees."""
+
+    MAX_TABLES = 8   # device job tables kept, one per distinct set of jobs packed together (all of a plan's jobs; the live ones of a frozen plan)
 
     def __init__(self, dtype: torch.dtype, device):
         self.dtype, self.device = dtype, device
         self.jobs = []          # (weight param, fwd bank | None, dgrad bank | None, cout, cin)
-        self._table, self._ptrs, self._blocks = None, None, 0
+        self._packed = []       # per job: the (data_ptr, _version) of the weight its banks were packed from as a frozen job; None = unknown (never packed, or packed as a live one)
+        self._tables = {}       # job indices -> (device table, the weights' data_ptrs, blocks)
+        self._same_weight = {}  # id(weight) -> its jobs (plans that freeze different layers want different banks of one weight)
 
     def add(self, w: torch.Tensor, cout: int, cin: int, want_fwd: bool = True, want_dgrad: bool = True):
         co, ci, k, _ = w.shape
@@ -680,28 +688,50 @@ class PackJobs:
         fwd = torch.zeros(packed_filter_elems(cout, cin, k), dtype=self.dtype, device=self.device) if want_fwd else None
         dg = torch.zeros(packed_filter_elems(cin, cout, k), dtype=self.dtype, device=self.device) if want_dgrad else None
         self.jobs.append((w, fwd, dg, cout, cin))
-        self._table = None
+        self._packed.append(None)
+        self._same_weight.setdefault(id(w), []).append(len(self.jobs) - 1)
+        self._tables.pop(tuple(range(len(self.jobs) - 1)), None)   # ("every job" has one more member now)
         return fwd, dg
 
-    def run(self):
-        if not self.jobs:
+    def stale(self, select=None):
+        """the job indices `run(select)` would pack now"""
+        if select is None:
+            return tuple(range(len(self.jobs)))
+        return tuple(i for i, always in select if always or self._packed[i] is None or self._packed[i] != (self.jobs[i][0].data_ptr(), self.jobs[i][0]._version))
+
+    def run(self, select=None):
+        todo = self.stale(select)
+        if not todo:
             return
-        ptrs = [w.data_ptr() for w, *_ in self.jobs]
-        if self._table is None or ptrs != self._ptrs:
+        ptrs = [self.jobs[i][0].data_ptr() for i in todo]
+        ent = self._tables.get(todo)
+        if ent is None or ent[1] != ptrs:
             import struct
 
             L = _lib.lib()
             rows, first = [], 0
-            for (w, fwd, dg, cout, cin), ptr in zip(self.jobs, ptrs):
+            for i, ptr in zip(todo, ptrs):
+                w, fwd, dg, cout, cin = self.jobs[i]
                 if w.dtype != torch.float32 or not w.is_contiguous():
                     raise TypeError("PackJobs expects contiguous fp32 master weights")
                 co, ci, k, _ = w.shape
                 rows.append(struct.pack("<QQQ6i", ptr, fwd.data_ptr() if fwd is not None else 0, dg.data_ptr() if dg is not None else 0, co, ci, k, cout, cin, first))
                 first += int(L.y3_pack_job_blocks(k, cout, cin, int(fwd is not None), int(dg is not None)))
             host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
-            self._table = host.to(self.device)
-            self._ptrs, self._blocks = ptrs, first
-        check(_lib.lib().y3_pack_filter_jobs(self._table.data_ptr(), len(self.jobs), self._blocks, dtype_code(self.dtype), stream_ptr()), "y3_pack_filter_jobs")
+            self._tables.pop(todo, None)
+            while len(self._tables) >= self.MAX_TABLES:
+                self._tables.pop(next(iter(self._tables)))
+            ent = self._tables[todo] = (host.to(self.device), ptrs, first)
+        check(_lib.lib().y3_pack_filter_jobs(ent[0].data_ptr(), len(todo), ent[2], dtype_code(self.dtype), stream_ptr()), "y3_pack_filter_jobs")
+        # a weight that is being trained may be written by a kernel torch's version counter does not see (FusedSGD): nothing is remembered about ANY of its jobs, so a plan
+        # that freezes it later packs it afresh
+        always = {i for i, a in select if a} if select is not None else set(todo)
+        for i, ptr in zip(todo, ptrs):
+            if i in always:
+                for j in self._same_weight.get(id(self.jobs[i][0]), (i,)):
+                    self._packed[j] = None
+            else:
+                self._packed[i] = (ptr, self.jobs[i][0]._version)
 
 
 def stem_pair(x_nchw: torch.Tensor, filt0: torch.Tensor, bias0: torch.Tensor, act0: bool, filt1: torch.Tensor, bias1: torch.Tensor, act1: bool, y: View, divisor: float = 1.0):

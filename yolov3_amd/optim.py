@@ -38,6 +38,28 @@ def smart_param_groups(model: nn.Module, lr: float, weight_decay: float):
     ]
 
 
+def freeze_layers(model: nn.Module, freeze) -> list:
+    """The reference's --freeze (train.py:217-223): every parameter is set to train, then those whose name contains ``model.{i}.`` for a frozen layer i get
+    ``requires_grad = False``.  `freeze` is the command line's list: one element ``[n]`` freezes layers ``range(n)`` (``[10]``: the yolov3 backbone, ``[0]``:
+    nothing), a longer list names the layer indices (one layer alone: name it twice, ``[4, 4]``).  Matching is by SUBSTRING of the parameter name, exactly as in
+    the reference, so that a run here trains the same parameters as the same command line upstream: the tag may sit anywhere in the name (``module.model.1.`` of a
+    wrapped model matches too), and it is the dot behind the index that keeps ``model.1.`` from matching ``model.11.`` or ``model.21.``.  Returns the names of the
+    frozen parameters.
+
+    The training engine reads requires_grad when it compiles a step (train_engine.TrainPlan): frozen layers run no backward work, their gradients stay None and
+    are not exchanged; they stay in training mode, so their BatchNorm layers keep normalising with batch statistics and updating the running ones, as upstream.
+    Build the optimizer after this call (FusedSGD, like the reference's smart_optimizer, takes the parameters that require a gradient)."""
+    freeze = list(freeze)
+    tags = [f"model.{x}." for x in (freeze if len(freeze) > 1 else range(freeze[0]))]
+    frozen = []
+    for k, v in model.named_parameters():
+        v.requires_grad = True   # train all layers
+        if any(x in k for x in tags):
+            v.requires_grad = False
+            frozen.append(k)
+    return frozen
+
+
 class ModelEMA:
     """Exponential moving average of the parameters (upstream ultralytics ModelEMA; reference train.py:252,421):
     d = decay * (1 - exp(-updates / tau)); ema = d * ema + (1 - d) * p.  Buffers (BN running stats) are copied like the
@@ -59,6 +81,15 @@ class ModelEMA:
             dst = list(self.buffers.values())
             torch._foreach_mul_(dst, d)
             torch._foreach_add_(dst, src, alpha=1.0 - d)
+
+    def update_rest(self, d: float, stepped: set):
+        """the parameters (`stepped`: ids) the fused step did not touch (frozen ones: no gradient): upstream's ModelEMA.update lerps every float entry of the state dict, so their
+        averages still move toward the (unchanged) value -- it matters when the average was loaded from a checkpoint and differs from the weights"""
+        rest = [p for p in self.shadow if id(p) not in stepped]
+        if rest:
+            dst = [self.shadow[p] for p in rest]
+            torch._foreach_mul_(dst, d)
+            torch._foreach_add_(dst, [p.detach() for p in rest], alpha=1.0 - d)
 
 
 class FusedSGD:
@@ -89,7 +120,7 @@ class FusedSGD:
         """One fused update.  grad_scale: the loss scale the gradients still carry -- a Python float, or a 1-element DEVICE fp32
         tensor (GradScaler below: dynamic scale, read by the kernels); max_norm: clip_grad_norm_ threshold (0 = off; the
         reference uses 10.0); ema: ModelEMA to update in the same pass."""
-        recs, n_chunks = [], 0
+        recs, n_chunks, stepped = [], 0, set()
         dev = None
         for g in self.param_groups:
             for p in g["params"]:
@@ -106,6 +137,7 @@ class FusedSGD:
                 e = ema.shadow[p] if ema is not None else None
                 recs.append((p.data_ptr(), grad.data_ptr(), buf.data_ptr(), e.data_ptr() if e is not None else 0, p.numel(), float(g["lr"]), float(g["weight_decay"]), n_chunks, grad))
                 n_chunks += (p.numel() + CHUNK - 1) // CHUNK
+                stepped.add(id(p))
         if not recs:
             return
         L = _lib.lib()
@@ -134,6 +166,8 @@ class FusedSGD:
             )
         if ema is not None:
             ema.update_buffers(d)
+            if len(recs) < len(ema.shadow):
+                ema.update_rest(d, stepped)
         self._steps += 1
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
 

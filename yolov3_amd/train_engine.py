@@ -11,6 +11,9 @@ post-activation ``y``) is kept for the backward -- 288 GB of HBM makes recomputa
 Gradient buffers mirror the activation buffers (Concat sources are channel slices of the Concat's gradient buffer),
 are zero-filled at the start of the backward and every producer ACCUMULATES into them, so fan-out (a tensor feeding
 two consumers, residual connections) needs no special casing.
+
+Frozen layers (reference train.py:217-223, ``yolov3_amd.freeze_layers``): a plan reads the parameters' ``requires_grad`` when it is compiled
+(TrainPlan._mark_needs) and launches no BatchNorm backward, filter gradient or data gradient whose result nobody would read; their gradients are None.
 """
 from __future__ import annotations
 
@@ -36,10 +39,14 @@ class Act:
         # a gradient contribution that is still another tensor (the shortcut of a Bottleneck: d out / d x = identity, so the contribution IS the output's
         # gradient): the next producer adds it while it writes (`take_deferred`), anyone else sees it materialised by `grad()`
         self.deferred: View | None = None
+        # some unit upstream owns a parameter that is trained (TrainPlan._mark_needs): False = nothing reads a gradient of this tensor, none is computed or allocated
+        self.need = True
+        self.slices: list[Act] = []
 
     def slice(self, coff, c):
         a = Act(self.view.slice(coff, c))
         a.parent, a.coff = self, coff
+        self.slices.append(a)
         return a
 
     def defer(self, contribution: View) -> bool:
@@ -58,6 +65,8 @@ class Act:
         return d
 
     def grad(self) -> View:
+        if not self.need:
+            raise RuntimeError("Act.grad: a gradient buffer was asked for a tensor that needs none (every layer upstream of it is frozen)")
         if self.deferred is not None:   # someone needs the buffer itself: copy the deferred contribution in
             d = self.take_deferred()
             g = self.grad()
@@ -127,6 +136,10 @@ class ConvUnit(_Unit):
         self.filt_d = None
         # the data gradient of this unit runs through the generic dgrad bank (not the stride-2 parity-class banks, not layer 0)
         self.pair_pack = need_dx and plan.dtype in (torch.float16, torch.bfloat16) and not (self.s == 2 and self.k == 3)
+        # what the backward of this unit has to produce (TrainPlan._mark_needs, from the parameters' requires_grad): the filter gradient, dgamma / dbeta, the shortcut's
+        # gradient, and whether any pass runs at all; `need_dx` above is the data gradient
+        self.wgrad_on = self.dgamma_on = self.dbeta_on = self.active = True
+        self.need_res = res is not None
         self.bank_fwd = self.bank_dgrad = None   # persistent filter banks filled by the plan's one-launch packing (TrainPlan.pack_jobs)
         # consumer-side BatchNorm (TrainPlan._pair_bn_consumers): `bn_in` = the unit whose normalise + activation (+ shortcut) this 1x1 unit applies on the way in;
         # `act_in_consumer` = this unit's own normalise pass runs inside its 1x1 consumer's launch
@@ -244,23 +257,29 @@ class ConvUnit(_Unit):
         ops.bn_act_fwd(self.u, self.vecs, self.act, self.y.view, self.res.view if self.res is not None else None)
 
     def bwd(self, grads):
+        if not self.active:
+            return
         m = self.m
         gy = self.y.grad()
-        dgamma = self.plan.grad_alloc((self.cout,))
-        dbeta = self.plan.grad_alloc((self.cout,))
+        # (a frozen BatchNorm parameter's sums are still outputs of the launch: they land in scratch outside the gradient arena and go nowhere)
+        dgamma = self.plan.grad_alloc((self.cout,)) if self.dgamma_on else self.plan.discard((self.cout,))
+        dbeta = self.plan.grad_alloc((self.cout,)) if self.dbeta_on else self.plan.discard((self.cout,))
         if self.fused_stem_bwd():
             # layer 0: no data gradient, so du has one consumer -- the filter gradient; both in one pass over (u, dy), du never stored
             xi = self.plan.x_nchw
             if xi._version != self.plan.x_version:
                 raise RuntimeError("the input batch was modified in place between the forward and the backward of this training step")
-            dw = self.plan.grad_alloc(tuple(m.conv.weight.shape))
+            dw = self.plan.grad_alloc(tuple(m.conv.weight.shape)) if self.wgrad_on else self.plan.discard(tuple(m.conv.weight.shape))
             if self.stem_filt is not None:
                 ops.stem_bn_bwd_wgrad_recompute(xi, self.stem_filt, gy, self.scale, self.shift, self.mean, self.invstd, self.act, self.sums, dgamma, dbeta, dw, self.plan.stem_bwd_ws())
             else:
                 ops.stem_bn_bwd_wgrad(xi, self.u, gy, self.scale, self.shift, self.mean, self.invstd, self.act, self.sums, dgamma, dbeta, dw, self.plan.stem_bwd_ws())
-            grads[m.bn.weight] = dgamma   # handed over in the order the arena slices were taken: a bucket is then one contiguous range (parallel.GradBuckets)
-            grads[m.bn.bias] = dbeta
-            grads[m.conv.weight] = dw
+            if self.dgamma_on:
+                grads[m.bn.weight] = dgamma   # handed over in the order the arena slices were taken: a bucket is then one contiguous range (parallel.GradBuckets)
+            if self.dbeta_on:
+                grads[m.bn.bias] = dbeta
+            if self.wgrad_on:
+                grads[m.conv.weight] = dw
             return
         du = self.plan.scratch_like(self.u)
         sync = self.sync_group()
@@ -272,20 +291,24 @@ class ConvUnit(_Unit):
             tot = self.sums[:c2].clone()
             torch.distributed.all_reduce(tot, group=sync[0])
             self.sums[c2 : 2 * c2].copy_(tot / self.count_all)
-            gres = self.res.grad() if self.res is not None else None
-            ops.bn_act_bwd_apply(self.u, gy, self.vecs, self.act, du, gres, self.res is not None and self.res.is_ready())
+            gres = self.res.grad() if self.need_res else None
+            ops.bn_act_bwd_apply(self.u, gy, self.vecs, self.act, du, gres, self.need_res and self.res.is_ready())
         else:
             # out = act(bn(conv)) + res  ->  d res (+)= d out, written by the pass that reads d out anyway.  Deferred, when nothing has written d res yet: d res = d out +
             # (what cv1's data gradient adds) and nothing is stored here -- the data-gradient launch of the other consumer of res (cv1 of the Bottleneck) takes d out as its
             # residual operand and writes d res once: one pass over the tensor less per Bottleneck, 4.4 GB of the batch-64 step (Y3_DEFER_SHORTCUT=0: the stored form, for A/B runs)
-            deferred = self.res is not None and not self.res.is_ready() and os.environ.get("Y3_DEFER_SHORTCUT", "1") != "0" and self.res.defer(gy)
-            gres, accumulate = (self.res.grad(), self.res.is_ready()) if self.res is not None and not deferred else (None, False)
+            # (need_res False: the Bottleneck's input needs no gradient -- every layer upstream of it is frozen -- and the shortcut's is neither stored nor deferred)
+            deferred = self.need_res and not self.res.is_ready() and os.environ.get("Y3_DEFER_SHORTCUT", "1") != "0" and self.res.defer(gy)
+            gres, accumulate = (self.res.grad(), self.res.is_ready()) if self.need_res and not deferred else (None, False)
             ops.bn_act_bwd(self.u, gy, self.vecs, self.act, du, dgamma, dbeta, gres, accumulate)
         if gres is not None:
             self.res.mark_ready()
-        grads[m.bn.weight] = dgamma   # cout == co_real (checked in fwd): whole tensors, so autograd takes them without a copy; handed over in
-        grads[m.bn.bias] = dbeta      # arena order (dgamma, dbeta, then the filter gradient below): buckets stay contiguous, disjoint ranges
-        self.plan.wgrad(grads, m.conv.weight, None, self.x.view, du, self.k, self.s, self.co_real, self.ci_real)
+        if self.dgamma_on:
+            grads[m.bn.weight] = dgamma   # cout == co_real (checked in fwd): whole tensors, so autograd takes them without a copy; handed over in
+        if self.dbeta_on:
+            grads[m.bn.bias] = dbeta      # arena order (dgamma, dbeta, then the filter gradient below): buckets stay contiguous, disjoint ranges
+        if self.wgrad_on:
+            self.plan.wgrad(grads, m.conv.weight, None, self.x.view, du, self.k, self.s, self.co_real, self.ci_real)
         self._dgrad(du, grads)
 
     def _dgrad(self, du: View, grads=None):
@@ -318,6 +341,7 @@ class HeadUnit(_Unit):
         self.raw = None
         self.bank_fwd = self.bank_dgrad = None
         self.filt_d = None
+        self.w_on = self.b_on = self.need_dx = True   # TrainPlan._mark_needs: the weight and the bias are judged each on its own
 
     def fwd(self):
         w = self.conv.weight
@@ -335,9 +359,14 @@ class HeadUnit(_Unit):
         return self.raw
 
     def bwd_from(self, graw, grads):
+        if not (self.w_on or self.b_on or self.need_dx):
+            return
         ghead = self.plan.scratch_like(self.head)
         ops.detect_raw_bwd(graw.contiguous().to(self.plan.dtype), self.det.na, self.det.no, ghead)
-        self.plan.wgrad(grads, self.conv.weight, self.conv.bias, self.x.view, ghead, 1, 1, self.conv.out_channels, self.conv.in_channels)
+        if self.w_on or self.b_on:   # (a live bias under a frozen weight: the one launch that sums it, its filter gradient dropped)
+            self.plan.wgrad(grads, self.conv.weight, self.conv.bias if self.b_on else None, self.x.view, ghead, 1, 1, self.conv.out_channels, self.conv.in_channels, w_live=self.w_on)
+        if not self.need_dx:
+            return
         gx = self.x.grad()
         filt_d, self.filt_d = self.filt_d, None
         if filt_d is None:
@@ -355,6 +384,8 @@ class UpsampleUnit(_Unit):
         ops.upsample2x(self.x.view, self.y.view)
 
     def bwd(self, grads):
+        if not self.x.need:
+            return
         ops.upsample2x_bwd(self.y.grad(), self.x.grad(), accumulate=self.x.is_ready())
         self.x.mark_ready()
 
@@ -367,6 +398,8 @@ class MaxPoolUnit(_Unit):
         ops.maxpool2d(self.x.view, self.y.view, self.k, self.s, self.p, self.zr, self.zb)
 
     def bwd(self, grads):
+        if not self.x.need:
+            return
         # the indexed two-pass form, 16 bytes of channels per thread (round 6; y3_maxpool2d_bwd's gather moved 2 bytes per thread: 8.5 ms of yolov3-tiny's 16.4 ms step)
         ops.maxpool2d_bwd(self.x.view, self.y.grad(), self.x.grad(), self.k, self.s, self.p, self.zr, self.zb, accumulate=self.x.is_ready())
         self.x.mark_ready()
@@ -383,6 +416,8 @@ class SPPPoolUnit(_Unit):
         ops.spp_pyramid(self.x.view, self.y.view)
 
     def bwd(self, grads):
+        if not self.x.need:
+            return
         c = self.x.view.c
         for j, k in enumerate((5, 9, 13)):   # (round 6: the indexed two-pass backward -- the gather form cost 210 ms per batch-64 step on these three pools)
             ops.maxpool2d_bwd(self.x.view, self.y.grad().slice(j * c, c), self.x.grad(), k, 1, k // 2, accumulate=self.x.is_ready())
@@ -445,13 +480,15 @@ class TrainSlot:
         return self.arena[off:off + nbytes].view(dtype)
 
     def banks(self, w, cout, cin, want_fwd, want_dgrad):
-        """persistent (forward bank, data-gradient bank) of weight tensor `w`, registered once per slot with the one-launch packer"""
+        """persistent (forward bank, data-gradient bank, job index) of weight tensor `w`, registered once per slot with the one-launch packer (plans that differ in
+        which layers are frozen may want different banks of one weight: a job each, and a forward packs its own plan's jobs only)"""
         if self.pack_jobs is None:
             self.pack_jobs = ops.PackJobs(self.dtype, self.device)
         key = (id(w), cout, cin, bool(want_fwd), bool(want_dgrad))
         b = self._banks.get(key)
         if b is None:
-            b = self._banks[key] = self.pack_jobs.add(w, cout, cin, want_fwd, want_dgrad)
+            fwd, dg = self.pack_jobs.add(w, cout, cin, want_fwd, want_dgrad)
+            b = self._banks[key] = (fwd, dg, len(self.pack_jobs.jobs) - 1)
         return b
 
     def conv_ws(self):
@@ -542,9 +579,11 @@ class TrainPlan:
                 self.units.append(ConvUnit(self, k, ins[0], out[i], None, need_dx=g.src[i][0] >= 0, label=f"L{i}"))
             else:
                 raise NotImplementedError(type(k).__name__)
-        self._pair_bn_consumers()
         self.params = list(model.parameters())
         self.param_ids = tuple(id(p) for p in self.params)   # run_model_train rebuilds the plan when a Parameter object is replaced
+        self.live = need_pattern(self.params)                # ... and takes another plan when a requires_grad flag changed (the pattern is part of the plan's cache key)
+        self._mark_needs()
+        self._pair_bn_consumers()
         self.x_nchw = None
         self.x_version = 0
 
@@ -566,19 +605,54 @@ class TrainPlan:
         # every conv launch of the plan runs on the compute stream
         self.conv_ws = self.slot.conv_ws() if dtype in (torch.float16, torch.bfloat16) else None   # (one per slot: a slot runs one plan at a time, on one stream)
         self._arena, self._arena_off = None, 0
-        self._arena_numel = sum((p.numel() + 63) // 64 * 64 for p in self.params)
+        self._arena_numel = sum((p.numel() + 63) // 64 * 64 for p, on in zip(self.params, self.live) if on)   # frozen parameters take no slice
+        self.live_bytes = sum(p.numel() * 4 for p, on in zip(self.params, self.live) if on)
         # all filter banks of a step in one launch (Y3_PACK_JOBS=0: one launch per layer, as before); the banks belong to the slot: every shape packs into the same ones
-        self.pack_jobs, self.banks_fresh = None, False
+        # A frozen weight's banks are packed once and again when the tensor's version counter moves (load_state_dict, any in-place write); a unit whose data gradient
+        # does not run has no data-gradient bank.  `pack_select`: this plan's (job, packed at every forward) pairs -- ops.PackJobs.run
+        self.pack_jobs, self.banks_fresh, self.pack_select = None, False, []
         if dtype in (torch.float16, torch.bfloat16) and os.environ.get("Y3_PACK_JOBS", "1") != "0":
             for u in self.units:
                 if isinstance(u, ConvUnit) and not u.use_stem:
-                    u.bank_fwd, u.bank_dgrad = self.slot.banks(u.m.conv.weight, u.cout, u.cin, True, u.pair_pack)
+                    w = u.m.conv.weight
+                    u.bank_fwd, u.bank_dgrad, job = self.slot.banks(w, u.cout, u.cin, True, u.pair_pack)
+                    self.pack_select.append((job, w.requires_grad))
             for hd in self.heads:
-                hd.bank_fwd, hd.bank_dgrad = self.slot.banks(hd.conv.weight, hd.cout, hd.x.view.c, True, True)
+                hd.bank_fwd, hd.bank_dgrad, job = self.slot.banks(hd.conv.weight, hd.cout, hd.x.view.c, True, hd.need_dx)
+                self.pack_select.append((job, hd.conv.weight.requires_grad))
             self.pack_jobs = self.slot.pack_jobs
         self.last_forward = 0
         self.generation = 0        # bumped by every forward: the saved activations belong to exactly one forward
         self.outstanding = False   # a grad-enabled forward ran and its backward has not: the saved state must not be overwritten
+
+    def _mark_needs(self):
+        """What the backward has to compute, from the parameters' requires_grad (reference train.py:217-223 freezes layers by clearing it; autograd then never runs
+        their backward).  A tensor NEEDS a gradient iff a unit upstream of it -- through Concat slices, Upsample, MaxPool, SPP and shortcuts -- owns a live parameter.
+        Per Conv unit: the filter gradient runs iff conv.weight is live; dgamma / dbeta are handed over iff bn.weight / bn.bias are live; the data gradient runs iff the
+        input needs a gradient; the BatchNorm backward pass runs iff any of those is wanted; a unit with none of them (and every pooling / upsample unit under an
+        all-frozen prefix) is skipped.  With every parameter live this marks everything except the image, which is what the engine always did."""
+        for a in self.acts:
+            a.need = False
+        self.x_in.need = False
+
+        def needs(a: Act) -> bool:   # (a Concat buffer: its gradient is one buffer, computed whenever one of its slices needs it)
+            return a.need or any(needs(s_) for s_ in a.slices)
+
+        for u in self.units:   # forward order: every producer of a unit's inputs comes before it
+            if isinstance(u, ConvUnit):
+                bn = u.m.bn
+                u.wgrad_on, u.dgamma_on, u.dbeta_on = u.m.conv.weight.requires_grad, bn.weight.requires_grad, bn.bias.requires_grad
+                u.need_dx = u.need_dx and needs(u.x)
+                u.need_res = u.res is not None and needs(u.res)
+                u.pair_pack = u.pair_pack and u.need_dx
+                u.active = u.wgrad_on or u.dgamma_on or u.dbeta_on or u.need_dx or u.need_res
+                u.y.need = u.active
+            else:
+                u.y.need = needs(u.x)
+        for a in self.acts:
+            a.need = needs(a)
+        for hd in self.heads:
+            hd.w_on, hd.b_on, hd.need_dx = hd.conv.weight.requires_grad, hd.conv.bias.requires_grad, hd.x.need
 
     def _pair_bn_consumers(self):
         """Consumer-side BatchNorm (round 5; Y3_BN_IN_CONSUMER=0: the separate passes, for A/B runs).  Where a Conv unit is IMMEDIATELY followed by a 1x1 Conv unit that reads its
@@ -675,15 +749,28 @@ class TrainPlan:
         self._arena_off += n_al
         return t
 
-    def wgrad(self, grads, w_param, b_param, x: View, du: View, k, s, co_real, ci_real):
+    def discard(self, shape):
+        """fp32 scratch for an output of a launch that nothing reads (the gradient of a frozen parameter that the kernel form produces anyway): outside the arena"""
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def wgrad(self, grads, w_param, b_param, x: View, du: View, k, s, co_real, ci_real, w_live=True):
         """Filter (and bias) gradient of one layer.  Nothing downstream in the backward needs it, so it CAN go to a second HIP
         stream (Y3_WGRAD_STREAM=1; see __init__ for the measurement).  `du` was produced on the current stream: the side
         stream waits for an event recorded here."""
         side = self.wgrad_stream
         ws = self.wgrad_ws(ops.conv2d_wgrad_workspace_bytes(x, du.c, k, s))   # (taken on the compute stream: nothing is ever allocated under the side stream)
+        alloc = self.grad_alloc
+        if not w_live:   # only the bias gradient is wanted (a Detect head with a frozen weight): the filter gradient, asked for first, lands in scratch
+            spare = [self.discard((co_real, ci_real, k, k))]
+            if side is not None:
+                spare[0].record_stream(side)
+
+            def alloc(shape):
+                return spare.pop() if spare else self.grad_alloc(shape)
         if side is None:
-            dw, db = ops.conv2d_wgrad(x, du, k, s, co_real, ci_real, want_bias=b_param is not None, alloc=self.grad_alloc, workspace=ws)
-            grads[w_param] = dw
+            dw, db = ops.conv2d_wgrad(x, du, k, s, co_real, ci_real, want_bias=b_param is not None, alloc=alloc, workspace=ws)
+            if w_live:
+                grads[w_param] = dw
             if b_param is not None:
                 grads[b_param] = db
             return
@@ -695,9 +782,10 @@ class TrainPlan:
         du.buf.record_stream(side)   # scratch of this layer: keep it from being recycled while the side stream still reads it
         with torch.cuda.stream(side):
             side.wait_event(ev)
-            dw, db = ops.conv2d_wgrad(x, du, k, s, co_real, ci_real, want_bias=b_param is not None, alloc=self.grad_alloc, workspace=ws)   # arena slices in host order, as on one stream
+            dw, db = ops.conv2d_wgrad(x, du, k, s, co_real, ci_real, want_bias=b_param is not None, alloc=alloc, workspace=ws)   # arena slices in host order, as on one stream
             dw.record_stream(cur)
-            grads[w_param] = dw      # handed over under the side stream: a gradient sink that launches collectives waits for the right stream
+            if w_live:
+                grads[w_param] = dw  # handed over under the side stream: a gradient sink that launches collectives waits for the right stream
             if b_param is not None:
                 db.record_stream(cur)
                 grads[b_param] = db
@@ -764,7 +852,7 @@ class TrainPlan:
         with torch.no_grad():
             try:
                 if self.pack_jobs is not None:
-                    self.pack_jobs.run()
+                    self.pack_jobs.run(self.pack_select)
                     self.banks_fresh = True
                 for u in self.units:
                     u.fwd()
@@ -776,7 +864,7 @@ class TrainPlan:
 
     def backward(self, graws):
         sync = getattr(self.model, "grad_sync", None)  # parallel.GradBuckets: overlapped gradient all-reduce
-        grads = _GradSink(sync, sum(p.numel() * 4 for p in self.params))
+        grads = _GradSink(sync, self.live_bytes)   # (frozen parameters produce nothing: the exchange and the tail flush count the live ones)
         self._arena, self._arena_off = None, 0          # a new arena per backward (see grad_alloc)
         self._bwd_stream = torch.cuda.current_stream() if self.wgrad_stream is not None else None
         for a in self.acts:
@@ -787,7 +875,8 @@ class TrainPlan:
                     g = torch.zeros_like(hd.raw)
                 hd.bwd_from(g, grads)
             for u in reversed(self.units):
-                u.bwd(grads)
+                if not isinstance(u, ConvUnit) or u.active:   # (the other kinds check their input's need themselves)
+                    u.bwd(grads)
             if self.wgrad_stream is not None:
                 torch.cuda.current_stream().wait_stream(self.wgrad_stream)   # every filter gradient has landed
         for a in self.acts:
@@ -867,6 +956,50 @@ class _TrainFn(torch.autograd.Function):
         return (None, None, *grads)
 
 
+def need_pattern(params) -> tuple:
+    """requires_grad of every parameter, in `params` order: which gradients a training plan computes.  Part of the plan's identity (acquire_plan)."""
+    return tuple(bool(p.requires_grad) for p in params)
+
+
+def acquire_plan(model, n, h, w, dtype, device, grad=True):
+    """the compiled training plan of `model` for this shape and for the CURRENT requires_grad pattern of its parameters, in an idle slot; built when there is none.
+    A plan skips the backward work of frozen layers, so one built for another pattern is never served: thawing layers after some epochs takes (and keeps) a second plan."""
+    from .engine import plan_cache
+
+    pc = plan_cache(model)
+    with pc.lock:
+        # A slot (TrainSlot: activation arena + filter banks, shared by every shape) runs one forward at a time.  A forward whose backward is still outstanding keeps
+        # its slot busy (two micro-batches whose losses are summed, a no_grad pass between forward and backward): take the first idle slot; when every slot is busy
+        # the least recently used one is taken over and the stale backward raises (see _TrainFn.backward)
+        slots = pc.train_slots(dtype, device, TrainSlot)
+        slot = next((sl for sl in slots if not sl.busy()), None)
+        if slot is None:
+            slot = min(slots, key=lambda sl: sl.last_forward)
+        params = list(model.parameters())
+        ids = tuple(id(p) for p in params)
+        if slot.param_ids != ids:
+            # a Parameter OBJECT was replaced since the slot captured them (re-created head, pruning, `m.conv.weight = nn.Parameter(..)`): a plan's backward would
+            # return None for it and the banks would be packed from the old tensor -- start over (in-place updates keep the ids: banks are re-packed per forward)
+            had = slot.param_ids is not None
+            slot.reset(ids)
+            if had:
+                pc.drop_train_slot(slot)
+        key = ("train", n, h, w, dtype, device.index, slot.index)
+        live = need_pattern(params)
+        if not all(live):   # (the plan with every parameter live keeps the key it always had; a frozen pattern is one more element)
+            key += (live,)
+        plan = pc.get(key)
+        if plan is not None and (plan.slot_generation != slot.generation or plan.param_ids != ids):
+            del pc.plans[key]   # built on an arena that has been replaced since / for other Parameter objects
+            plan = None
+        if plan is None:
+            plan = TrainPlan.build(model, n, h, w, dtype, device, slot, siblings=[p for k, p in pc.plans.items() if k[0] == "train"])   # (a larger shape grows the arena
+            pc.put(key, plan)                                                                                                      #  and re-points the slot's other plans)
+        slot.take_over(plan)
+        plan.outstanding = grad
+    return plan
+
+
 def run_model_train(model, x: torch.Tensor):
     """DetectionModel.forward in training mode: list of raw (bs, na, ny, nx, no) tensors attached to autograd."""
     ops.require_gpu(x, "DetectionModel.forward")
@@ -877,36 +1010,8 @@ def run_model_train(model, x: torch.Tensor):
     if dtype not in (torch.float16, torch.bfloat16, torch.float32):
         raise TypeError(f"unsupported training activation dtype {dtype}")
     n, c, h, w = x.shape
-    from .engine import plan_cache
-
-    pc = plan_cache(model)
     grad = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())
-    with pc.lock:
-        # A slot (TrainSlot: activation arena + filter banks, shared by every shape) runs one forward at a time.  A forward whose backward is still outstanding keeps
-        # its slot busy (two micro-batches whose losses are summed, a no_grad pass between forward and backward): take the first idle slot; when every slot is busy
-        # the least recently used one is taken over and the stale backward raises (see _TrainFn.backward)
-        slots = pc.train_slots(dtype, x.device, TrainSlot)
-        slot = next((sl for sl in slots if not sl.busy()), None)
-        if slot is None:
-            slot = min(slots, key=lambda sl: sl.last_forward)
-        ids = tuple(id(p) for p in model.parameters())
-        if slot.param_ids != ids:
-            # a Parameter OBJECT was replaced since the slot captured them (re-created head, pruning, `m.conv.weight = nn.Parameter(..)`): a plan's backward would
-            # return None for it and the banks would be packed from the old tensor -- start over (in-place updates keep the ids: banks are re-packed per forward)
-            had = slot.param_ids is not None
-            slot.reset(ids)
-            if had:
-                pc.drop_train_slot(slot)
-        key = ("train", n, h, w, dtype, x.device.index, slot.index)
-        plan = pc.get(key)
-        if plan is not None and (plan.slot_generation != slot.generation or plan.param_ids != ids):
-            del pc.plans[key]   # built on an arena that has been replaced since / for other Parameter objects
-            plan = None
-        if plan is None:
-            plan = TrainPlan.build(model, n, h, w, dtype, x.device, slot, siblings=[p for k, p in pc.plans.items() if k[0] == "train"])   # (a larger shape grows the arena
-            pc.put(key, plan)                                                                                                      #  and re-points the slot's other plans)
-        slot.take_over(plan)
-        plan.outstanding = grad
+    plan = acquire_plan(model, n, h, w, dtype, x.device, grad)
     if not grad:
         with torch.no_grad():
             return plan.forward(x)   # nothing to save for: no autograd node, the plan stays idle
