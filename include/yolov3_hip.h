@@ -455,6 +455,19 @@ int y3_sgd_step_dynamic(const void* tensor_table, int32_t n_tensors, int32_t n_c
                         void* stream);
 int y3_loss_scale_update(float* loss_scale, int32_t* growth_tracker, const int32_t* found_inf, float growth_factor,
                          float backoff_factor, int32_t growth_interval, void* stream);
+/* Fused Adam / AdamW / RMSProp steps: torch's single-tensor algorithms with fp32 state (amsgrad, maximize and centered off), behind the same two passes as
+ * y3_sgd_step -- unscale + inf check + global norm + clip coefficient, then ONE streaming update that also does the ModelEMA lerp.  `tensor_table`: DEVICE array of
+ *   { float* param; const float* grad; float* s1; float* s2; float* ema (or NULL); int64 numel; double lr, weight_decay, h0, h1, eps; int32 first_chunk; int32 pad; }
+ * (y3_optim_tensor_record_bytes() == 96; chunks of 16384 elements).  Adam: s1 = exp_avg, s2 = exp_avg_sq, h0 / h1 = beta1 / beta2.  RMSProp: s1 = square_avg,
+ * s2 = momentum buffer (NULL without momentum), h0 = alpha, h1 = momentum.  Pointers need 4-byte alignment; tensors whose pointers are all 16-byte aligned are streamed
+ * 16 bytes at a time.  The gradients carry inv_scale^-1 (times *loss_scale when that DEVICE float is given; NULL: none).  `step`: DEVICE int32, the optimizer's step
+ * count t; it advances (before the update, which reads it for the bias corrections) only when no gradient was inf/nan -- a skipped step changes nothing but
+ * found_inf.  decoupled != 0: AdamW (p *= 1 - lr * wd, no decay in the gradient).  scratch / found_inf: as y3_sgd_step. */
+size_t y3_optim_tensor_record_bytes(void);
+int y3_adam_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* loss_scale, float max_norm, int32_t decoupled,
+                 float ema_decay, int32_t* step, float* scratch, int32_t* found_inf, void* stream);
+int y3_rmsprop_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* loss_scale, float max_norm, float ema_decay,
+                    int32_t* step, float* scratch, int32_t* found_inf, void* stream);
 /* The owner's step of the two-phase gradient exchange that replaces a bucket's all-reduce on a fully connected xGMI mesh (reference: DDP's gradient
    averaging, utils/torch_utils.py:60-72 smart_DDP / train.py:411): `parts` holds n_parts contributions of n floats each ([n_parts][n], what the all-to-all
    of the shards delivered); out[i] = (parts[0][i] + ... + parts[n_parts - 1][i]) * scale, added in that order.  `out` may alias none of `parts`. */

@@ -13,6 +13,7 @@ ap.add_argument("--imgsz", type=int, default=640)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--model", default="yolov3")
 ap.add_argument("--fused", action="store_true")
+ap.add_argument("--optimizer", choices=["SGD", "Adam", "AdamW", "RMSProp"], default="SGD", help="the reference's --optimizer; with --fused the fused step of that family (smart_optimizer)")
 ap.add_argument("--freeze", type=int, nargs="+", default=[0], help="the reference's --freeze (train.py:217): [n] = layers 0 .. n-1 (10: the yolov3 backbone), a longer list names layers")
 ap.add_argument("--launches", action="store_true", help="one more step under _lib.CallTimer: calls and milliseconds per C function, forward and backward")
 args = ap.parse_args()
@@ -21,12 +22,15 @@ m = DetectionModel(f"{args.model}.yaml").to(dev).train()
 frozen = freeze_layers(m, args.freeze)
 m.hyp = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=4.0, fl_gamma=0.0, label_smoothing=0.0)
 crit = ComputeLoss(m)
-from yolov3_amd.optim import FusedSGD, ModelEMA, smart_param_groups
+from yolov3_amd.optim import FusedSGD, ModelEMA, smart_optimizer, smart_param_groups
 if args.fused:
-    opt = FusedSGD(smart_param_groups(m, 0.01, 5e-4), momentum=0.937, nesterov=True)
+    opt = FusedSGD(smart_param_groups(m, 0.01, 5e-4), momentum=0.937, nesterov=True) if args.optimizer == "SGD" else smart_optimizer(m, args.optimizer, 0.001, 0.937, 5e-4)
     ema = ModelEMA(m)
-else:
+elif args.optimizer == "SGD":
     opt = torch.optim.SGD([p_ for p_ in m.parameters() if p_.requires_grad], lr=0.01, momentum=0.937, nesterov=True)
+else:
+    live = [p_ for p_ in m.parameters() if p_.requires_grad]
+    opt = {"Adam": torch.optim.Adam, "AdamW": torch.optim.AdamW, "RMSProp": torch.optim.RMSprop}[args.optimizer](live, lr=0.001)
 x = torch.rand(args.batch, 3, args.imgsz, args.imgsz, device=dev)
 tg = yo.synth_targets(args.batch, 80, seed=1).to(dev)
 def sync(): torch.cuda.synchronize(); return time.perf_counter()
@@ -65,7 +69,7 @@ if args.launches:
     launches["backward"] = {k: [round(v[0], 3), v[1]] for k, v in sorted(t_b.by_function().items())}
     opt.zero_grad()
 print(json.dumps({"workload": f"{args.model} train step {args.imgsz}x{args.imgsz} batch={args.batch} autocast fp16 (fwd BN batch stats + ComputeLoss + bwd + torch SGD)",
-                  "ms": {"forward": round(f, 2), "loss": round(l, 2), "backward": round(b, 2), "optimizer(fused sgd+clip+ema)" if args.fused else "optimizer(torch sgd)": round(o, 2), "total": round(tot, 2)},
+                  "ms": {"forward": round(f, 2), "loss": round(l, 2), "backward": round(b, 2), (f"optimizer(fused {args.optimizer.lower()}+clip+ema)" if args.fused else f"optimizer(torch {args.optimizer.lower()})"): round(o, 2), "total": round(tot, 2)},
                   "steps_ms": [round(sum(r) * 1e3, 2) for r in res], "freeze": args.freeze, "frozen_parameters": len(frozen),
                   "live_parameter_elements": sum(p_.numel() for p_ in m.parameters() if p_.requires_grad),
                   "images_per_sec": round(args.batch / tot * 1e3, 1), "loss": float(loss), **({"launches_ms_calls": launches} if launches else {})}))

@@ -21,7 +21,22 @@ struct OptTensor {            // one entry per parameter tensor, DEVICE memory, 
     int pad;
 };
 
-__device__ int find_tensor(const OptTensor* __restrict__ t, int n, int chunk) {
+// the moment optimizers' record (Adam / AdamW: s1 = exp_avg, s2 = exp_avg_sq, h0 = beta1, h1 = beta2; RMSProp: s1 = square_avg, s2 = momentum buffer or null,
+// h0 = alpha, h1 = momentum).  Hyper-parameters are doubles, as torch holds them: 1 - beta2 = 0.001 taken from a float beta2 is already 6e-5 off.
+struct MomentTensor {
+    float* param;
+    const float* grad;
+    float* s1;
+    float* s2;
+    float* ema;               // may be null
+    long long numel;
+    double lr, weight_decay, h0, h1, eps;
+    int first_chunk;          // prefix sum of chunk counts
+    int pad;
+};
+
+template <class Rec>
+__device__ int find_tensor(const Rec* __restrict__ t, int n, int chunk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -31,12 +46,13 @@ __device__ int find_tensor(const OptTensor* __restrict__ t, int n, int chunk) {
 }
 
 // pass 1: sum of squares of the (unscaled) gradients + non-finite detection; one partial per block
-__global__ __launch_bounds__(256) void grad_norm_kernel(const OptTensor* __restrict__ t, int n, float inv_scale, const float* __restrict__ scale_dev,
+template <class Rec>
+__global__ __launch_bounds__(256) void grad_norm_kernel(const Rec* __restrict__ t, int n, float inv_scale, const float* __restrict__ scale_dev,
                                                           float* __restrict__ partial, int* __restrict__ found_inf) {
     __shared__ float red[256];
     if (scale_dev) inv_scale *= 1.0f / scale_dev[0];   // dynamic loss scale (GradScaler): lives on the device, no host round trip
     const int ti = find_tensor(t, n, blockIdx.x);
-    const OptTensor T = t[ti];
+    const Rec T = t[ti];
     const long long base = (long long)(blockIdx.x - T.first_chunk) * CHUNK;
     float a = 0.0f;
     bool bad = false;
@@ -102,6 +118,122 @@ __global__ __launch_bounds__(256) void sgd_update_kernel(const OptTensor* __rest
     }
 }
 
+// ---- Adam / AdamW / RMSProp: torch's single-tensor algorithms (torch/optim/adam.py, rmsprop.py; amsgrad, maximize, centered off), fp32 state --------------
+// The step count t lives on the device: it advances only when the step is not skipped, so the bias corrections stay torch's after an overflow step.
+__global__ void step_advance_kernel(int* __restrict__ step, const int* __restrict__ found_inf) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && !*found_inf) *step = *step + 1;
+}
+
+// Tensor.lerp_(end, w) as ATen computes it
+__device__ __forceinline__ float lerp_aten(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w); }
+
+struct AdamCoef {             // block-uniform, from the record and t
+    float wd, decay, w1, b2, w2, bc2_sqrt, eps, neg_step;
+    int decoupled;
+    __device__ AdamCoef(const MomentTensor& T, int t, int decoupled_) : decoupled(decoupled_) {
+        wd = (float)T.weight_decay;
+        decay = (float)(1.0 - T.lr * T.weight_decay);
+        w1 = (float)(1.0 - T.h0);
+        b2 = (float)T.h1;
+        w2 = (float)(1.0 - T.h1);
+        const double bc1 = 1.0 - pow(T.h0, (double)t), bc2 = 1.0 - pow(T.h1, (double)t);
+        bc2_sqrt = (float)sqrt(bc2);
+        eps = (float)T.eps;
+        neg_step = (float)(-(T.lr / bc1));
+    }
+    // g arrives unscaled and clipped; s1 = exp_avg, s2 = exp_avg_sq
+    __device__ __forceinline__ void apply(float& p, float g, float& m, float& v) const {
+        if (wd != 0.0f) {
+            if (decoupled) p *= decay; else g += wd * p;
+        }
+        m = lerp_aten(m, g, w1);
+        v = v * b2 + w2 * g * g;
+        const float denom = sqrtf(v) / bc2_sqrt + eps;
+        p += neg_step * m / denom;
+    }
+};
+
+struct RmsCoef {
+    float wd, alpha, w, eps, mu, neg_lr;
+    __device__ RmsCoef(const MomentTensor& T, int, int) {
+        wd = (float)T.weight_decay;
+        alpha = (float)T.h0;
+        w = (float)(1.0 - T.h0);
+        eps = (float)T.eps;
+        mu = (float)T.h1;
+        neg_lr = (float)(-T.lr);
+    }
+    // s1 = square_avg, s2 = momentum buffer (read and written only when mu > 0)
+    __device__ __forceinline__ void apply(float& p, float g, float& s, float& b) const {
+        if (wd != 0.0f) g += wd * p;
+        s = s * alpha + w * g * g;
+        const float avg = sqrtf(s) + eps;
+        if (mu > 0.0f) {
+            b = b * mu + g / avg;
+            p += neg_lr * b;
+        } else {
+            p += neg_lr * g / avg;
+        }
+    }
+};
+
+// pass 2 of the moment optimizers.  HBM-bound: per element one read of grad, read + write of param, the state buffers and EMA.  A tensor whose pointers are all
+// 16-byte aligned is streamed as float4 (a chunk starts at a multiple of 16384 elements, so alignment carries over); the last numel % 4 elements and misaligned
+// tensors (a gradient is a view into a flat arena: 4-byte alignment is all a record promises) go one float at a time.  HAS_S2 = false: RMSProp without momentum.
+template <class Coef, bool HAS_S2>
+__device__ __forceinline__ void moment_update_chunk(const MomentTensor& T, const Coef& c, long long base, float gs, float ema_decay) {
+    const long long left = T.numel - base;
+    const int lim = left < CHUNK ? (int)left : CHUNK;
+    uintptr_t bits = (uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.s1 | (uintptr_t)T.ema;
+    if (HAS_S2) bits |= (uintptr_t)T.s2;
+    const int nvec = (bits & 15) == 0 ? (lim & ~3) : 0;   // elements handled as float4
+    const float em = 1.0f - ema_decay;
+    for (int i = threadIdx.x * 4; i < nvec; i += 1024) {
+        const long long e = base + i;
+        f32x4 p = *(const f32x4*)(T.param + e);
+        const f32x4 g = *(const f32x4*)(T.grad + e) * gs;
+        f32x4 a = *(const f32x4*)(T.s1 + e);
+        f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (HAS_S2) b = *(const f32x4*)(T.s2 + e);
+        f32x4 m = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (T.ema) m = *(const f32x4*)(T.ema + e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float pk = p[k], ak = a[k], bk = b[k];
+            c.apply(pk, g[k], ak, bk);
+            p[k] = pk, a[k] = ak, b[k] = bk;
+        }
+        *(f32x4*)(T.param + e) = p;
+        *(f32x4*)(T.s1 + e) = a;
+        if (HAS_S2) *(f32x4*)(T.s2 + e) = b;
+        if (T.ema) *(f32x4*)(T.ema + e) = ema_decay * m + em * p;
+    }
+    for (int i = nvec + threadIdx.x; i < lim; i += 256) {
+        const long long e = base + i;
+        float p = T.param[e], a = T.s1[e], b = HAS_S2 ? T.s2[e] : 0.0f;
+        c.apply(p, T.grad[e] * gs, a, b);
+        T.param[e] = p;
+        T.s1[e] = a;
+        if (HAS_S2) T.s2[e] = b;
+        if (T.ema) T.ema[e] = ema_decay * T.ema[e] + em * p;
+    }
+}
+
+template <class Coef>
+__global__ __launch_bounds__(256) void moment_update_kernel(const MomentTensor* __restrict__ t, int n, float inv_scale, const float* __restrict__ scale_dev,
+                                                              const float* __restrict__ clip, const int* __restrict__ found_inf, const int* __restrict__ step, int decoupled,
+                                                              float ema_decay) {
+    if (*found_inf) return;  // skipped step: parameters, state and EMA stay bit for bit
+    if (scale_dev) inv_scale *= 1.0f / scale_dev[0];
+    const int ti = find_tensor(t, n, blockIdx.x);
+    const MomentTensor T = t[ti];
+    const long long base = (long long)(blockIdx.x - T.first_chunk) * CHUNK;
+    const float gs = inv_scale * clip[1];
+    const Coef c(T, *step, decoupled);
+    if (T.s2) moment_update_chunk<Coef, true>(T, c, base, gs, ema_decay);
+    else moment_update_chunk<Coef, false>(T, c, base, gs, ema_decay);
+}
+
 // torch.cuda.amp.GradScaler.update() (reference train.py:345,416-417; ATen _amp_update_scale_): on a step that found inf/nan the scale
 // is multiplied by backoff_factor and the growth counter reset; otherwise the counter advances and every growth_interval clean steps
 // the scale is multiplied by growth_factor (unless that overflows fp32).  All on the device.
@@ -159,7 +291,7 @@ static int sgd_step_impl(const void* tensor_table, int32_t n_tensors, int32_t n_
     hipStream_t st = (hipStream_t)stream;
     const OptTensor* t = (const OptTensor*)tensor_table;
     Y3_HIP(hipMemsetAsync(found_inf, 0, sizeof(int), st));
-    hipLaunchKernelGGL(grad_norm_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, t, n_tensors, inv_scale, scale_dev, scratch + 2, found_inf);
+    hipLaunchKernelGGL(grad_norm_kernel<OptTensor>, dim3((unsigned)n_chunks), dim3(256), 0, st, t, n_tensors, inv_scale, scale_dev, scratch + 2, found_inf);
     Y3_CHECK_LAUNCH();
     hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, st, (const float*)(scratch + 2), n_chunks, max_norm, scratch);
     Y3_CHECK_LAUNCH();
@@ -186,4 +318,38 @@ extern "C" int y3_loss_scale_update(float* loss_scale, int32_t* growth_tracker, 
     hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval);
     Y3_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" size_t y3_optim_tensor_record_bytes(void) { return sizeof(MomentTensor); }
+
+template <class Coef>
+static int moment_step_impl(const char* who, const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* scale_dev, float max_norm, int32_t decoupled,
+                            float ema_decay, int32_t* step, float* scratch, int32_t* found_inf, void* stream) {
+    if (!tensor_table) Y3_FAIL("%s: null tensor table", who);
+    if (n_tensors <= 0 || n_chunks <= 0) Y3_FAIL("%s: n_tensors %d and n_chunks %d must be positive", who, (int)n_tensors, (int)n_chunks);
+    if (!step) Y3_FAIL("%s: null step counter", who);
+    if (!scratch || !found_inf) Y3_FAIL("%s: null scratch or found_inf", who);
+    hipStream_t st = (hipStream_t)stream;
+    const MomentTensor* t = (const MomentTensor*)tensor_table;
+    Y3_HIP(hipMemsetAsync(found_inf, 0, sizeof(int), st));
+    hipLaunchKernelGGL(grad_norm_kernel<MomentTensor>, dim3((unsigned)n_chunks), dim3(256), 0, st, t, n_tensors, inv_scale, scale_dev, scratch + 2, found_inf);
+    Y3_CHECK_LAUNCH();
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, st, (const float*)(scratch + 2), n_chunks, max_norm, scratch);
+    Y3_CHECK_LAUNCH();
+    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, st, step, (const int*)found_inf);
+    Y3_CHECK_LAUNCH();
+    hipLaunchKernelGGL(moment_update_kernel<Coef>, dim3((unsigned)n_chunks), dim3(256), 0, st, t, n_tensors, inv_scale, scale_dev, (const float*)scratch, (const int*)found_inf,
+                       (const int*)step, decoupled, ema_decay);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_adam_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* loss_scale, float max_norm, int32_t decoupled,
+                            float ema_decay, int32_t* step, float* scratch, int32_t* found_inf, void* stream) {
+    return moment_step_impl<AdamCoef>("y3_adam_step", tensor_table, n_tensors, n_chunks, inv_scale, loss_scale, max_norm, decoupled, ema_decay, step, scratch, found_inf, stream);
+}
+
+extern "C" int y3_rmsprop_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* loss_scale, float max_norm, float ema_decay,
+                               int32_t* step, float* scratch, int32_t* found_inf, void* stream) {
+    return moment_step_impl<RmsCoef>("y3_rmsprop_step", tensor_table, n_tensors, n_chunks, inv_scale, loss_scale, max_norm, 0, ema_decay, step, scratch, found_inf, stream);
 }

@@ -1,4 +1,4 @@
-"""Fused SGD(Nesterov) + GradScaler unscale/inf-check + clip_grad_norm_ + ModelEMA on MI355X (csrc/optim.hip).
+"""Fused SGD(Nesterov) / Adam / AdamW / RMSProp + GradScaler unscale/inf-check + clip_grad_norm_ + ModelEMA on MI355X (csrc/optim.hip).
 
 Mirror of the reference's optimizer step, train.py:414-422:
     scaler.unscale_(optimizer); clip_grad_norm_(model.parameters(), max_norm=10.0); scaler.step(optimizer); ema.update(model)
@@ -170,6 +170,273 @@ class FusedSGD:
                 ema.update_rest(d, stepped)
         self._steps += 1
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
+
+    def state_dict(self):
+        """torch.optim.SGD's format: a checkpoint written here loads into torch.optim.SGD(momentum, nesterov) and the other way round"""
+        extra = {"momentum": self.momentum, "dampening": 0, "nesterov": self.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
+        return _pack_state_dict(self.param_groups, extra, lambda p: {"momentum_buffer": self.state[p]} if p in self.state else None)
+
+    def load_state_dict(self, sd):
+        saved = _check_groups(self.param_groups, sd)
+        mus = {float(g["momentum"]) for g in saved if "momentum" in g}
+        if len(mus) > 1:
+            raise ValueError(f"FusedSGD keeps one momentum for all groups, the checkpoint has {sorted(mus)}")
+        if any(g.get("dampening", 0) != 0 or g.get("maximize", False) for g in saved):
+            raise ValueError("FusedSGD does not support dampening / maximize")
+        if mus:
+            self.momentum = mus.pop()
+        if saved and "nesterov" in saved[0]:
+            self.nesterov = bool(saved[0]["nesterov"])
+        _load_groups(self.param_groups, saved, ("lr", "weight_decay"))
+        self.state = {}
+        for p, st in _saved_state(self.param_groups, sd):
+            if st.get("momentum_buffer") is not None:
+                self.state[p] = st["momentum_buffer"].detach().to(device=p.device, dtype=torch.float32).clone().contiguous()
+        # torch takes "first step" per parameter from a missing buffer; here a zero buffer gives the same result (mu * 0 + g), so one loaded buffer ends the first step
+        self._steps = 1 if self.state else 0
+
+
+def _pack_state_dict(groups, extra: dict, state_of):
+    """{"state": {index: {...}}, "param_groups": [{..., "params": [indices]}]} -- torch.optim.Optimizer.state_dict()'s layout, parameters numbered in group order"""
+    index, out_groups, state = {}, [], {}
+    for g in groups:
+        d = {k: v for k, v in g.items() if k != "params"}
+        for k, v in extra.items():
+            d.setdefault(k, v)
+        d["params"] = []
+        for p in g["params"]:
+            i = index.setdefault(id(p), len(index))
+            d["params"].append(i)
+            st = state_of(p)
+            if st is not None:
+                state[i] = st
+        out_groups.append(d)
+    return {"state": state, "param_groups": out_groups}
+
+
+def _check_groups(groups, sd):
+    saved = sd["param_groups"]
+    if len(saved) != len(groups):
+        raise ValueError("loaded state dict has a different number of parameter groups")
+    if any(len(g["params"]) != len(s["params"]) for g, s in zip(groups, saved)):
+        raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+    return saved
+
+
+def _load_groups(groups, saved, keys):
+    for g, s in zip(groups, saved):
+        for k in keys:
+            if k in s:
+                g[k] = tuple(s[k]) if isinstance(s[k], (list, tuple)) else s[k]
+
+
+def _saved_state(groups, sd):
+    """(parameter, its saved state) pairs: the saved indices are matched to this optimizer's parameters by position, as torch does"""
+    ids = [i for s in sd["param_groups"] for i in s["params"]]
+    params = [p for g in groups for p in g["params"]]
+    return [(p, sd["state"][i]) for i, p in zip(ids, params) if i in sd["state"]]
+
+
+class _FusedMoment:
+    """What FusedAdam / FusedAdamW / FusedRMSProp share: torch's param_groups layout (every hyper-parameter is read from its group at every step, so schedulers may
+    rewrite them), lazily allocated fp32 state, ONE step counter on the device (it advances only on steps that are not skipped), and the step itself -- the two
+    passes of FusedSGD with another update kernel (csrc/optim.hip).  `last_norm` / `found_inf` are device tensors, as FusedSGD's: GradScaler.step drives these too."""
+
+    _what = ""            # class name in messages
+    _state_keys = ()      # torch's names of s1, s2
+
+    def _init_groups(self, params, defaults: dict):
+        groups = list(params)
+        if groups and not isinstance(groups[0], dict):
+            groups = [{"params": groups}]
+        self.param_groups = []
+        for g in groups:
+            g = dict(g)
+            for k, v in defaults.items():
+                g.setdefault(k, v)
+            g["params"] = [p for p in g["params"] if p.requires_grad]
+            self.param_groups.append(g)
+        self.state: dict = {}
+        self._step_dev = None       # device int32, the step count t
+        self._step_init = 0         # t before the counter exists (load_state_dict on an optimizer that has not stepped)
+        self._dev_bufs = None
+        self.last_norm = None
+
+    zero_grad = FusedSGD.zero_grad
+
+    def _record(self, g, p):      # -> (s1, s2 or None, h0, h1)
+        raise NotImplementedError
+
+    def _launch(self, L, *a):
+        raise NotImplementedError
+
+    def _buf(self, p, key):
+        st = self.state.setdefault(p, {})
+        if key not in st:
+            st[key] = torch.zeros_like(p)
+        return st[key]
+
+    @torch.no_grad()
+    def step(self, grad_scale=1.0, max_norm: float = 0.0, ema: ModelEMA | None = None):
+        """One fused update; the arguments are FusedSGD.step's."""
+        recs, keep, n_chunks, stepped = [], [], 0, set()
+        dev = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                ops.require_gpu(p, f"{self._what}.step")
+                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous():
+                    raise TypeError(f"{self._what} expects contiguous fp32 master parameters and fp32 gradients")
+                dev = p.device
+                s1, s2, h0, h1 = self._record(g, p)
+                grad = p.grad.contiguous()
+                keep.append(grad)
+                e = ema.shadow[p] if ema is not None else None
+                recs.append(struct.pack("<QQQQQqdddddii", p.data_ptr(), grad.data_ptr(), s1.data_ptr(), s2.data_ptr() if s2 is not None else 0,
+                                        e.data_ptr() if e is not None else 0, p.numel(), float(g["lr"]), float(g["weight_decay"]), float(h0), float(h1), float(g["eps"]),
+                                        n_chunks, 0))
+                n_chunks += (p.numel() + CHUNK - 1) // CHUNK
+                stepped.add(id(p))
+        if not recs:
+            return
+        L = _lib.lib()
+        assert L.y3_optim_tensor_record_bytes() == 96
+        host = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
+        if self._dev_bufs is None or self._dev_bufs[0].numel() < host.numel() or self._dev_bufs[1].numel() < n_chunks + 2:
+            self._dev_bufs = (torch.empty(host.numel(), dtype=torch.uint8, device=dev), torch.empty(n_chunks + 2, dtype=torch.float32, device=dev),
+                              torch.zeros(1, dtype=torch.int32, device=dev))
+        if self._step_dev is None:
+            self._step_dev = torch.full((1,), self._step_init, dtype=torch.int32, device=dev)
+        tab, scratch, found = self._dev_bufs
+        tab[: host.numel()].copy_(host, non_blocking=True)
+        d = ema.next_decay() if ema is not None else 0.0
+        if isinstance(grad_scale, torch.Tensor):
+            if grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != dev:
+                raise TypeError("a dynamic loss scale must be a 1-element fp32 tensor on the parameters' device")
+            inv, scale_ptr = 1.0, grad_scale.data_ptr()
+        else:
+            inv, scale_ptr = 1.0 / float(grad_scale), None
+        self._launch(L, tab.data_ptr(), len(recs), n_chunks, inv, scale_ptr, float(max_norm), float(d), self._step_dev.data_ptr(), scratch.data_ptr(), found.data_ptr(),
+                     ops.stream_ptr())
+        if ema is not None:
+            ema.update_buffers(d)
+            if len(recs) < len(ema.shadow):
+                ema.update_rest(d, stepped)
+        self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
+
+    def _torch_group_extra(self) -> dict:
+        raise NotImplementedError
+
+    def state_dict(self):
+        """torch's format (the key names of torch.optim.Adam / AdamW / RMSprop; `step` is a 0-d fp32 CPU tensor, as torch keeps it).  Reads the device step counter:
+        synchronises, like GradScaler.get_scale -- for checkpoints only."""
+        t = int(self._step_dev.item()) if self._step_dev is not None else self._step_init
+
+        def state_of(p):
+            st = self.state.get(p)
+            return None if st is None else {"step": torch.tensor(float(t), dtype=torch.float32), **{k: st[k] for k in self._state_keys if k in st}}
+
+        return _pack_state_dict(self.param_groups, self._torch_group_extra(), state_of)
+
+    def _check_flags(self, g):
+        raise NotImplementedError
+
+    def load_state_dict(self, sd):
+        saved = _check_groups(self.param_groups, sd)
+        for g in saved:
+            self._check_flags(g)
+        pairs = _saved_state(self.param_groups, sd)
+        steps = {int(float(st["step"])) for _, st in pairs if "step" in st}
+        if len(steps) > 1:
+            raise ValueError(f"{self._what} keeps one step counter for all parameters, the checkpoint's `step` values differ: {sorted(steps)}")
+        _load_groups(self.param_groups, saved, self._group_keys)
+        self.state = {}
+        for p, st in pairs:
+            self.state[p] = {k: st[k].detach().to(device=p.device, dtype=torch.float32).clone().contiguous() for k in self._state_keys if st.get(k) is not None}
+        self._step_init = steps.pop() if steps else 0
+        if self._step_dev is not None:
+            self._step_dev.fill_(self._step_init)
+
+
+def _reject(what, **flags):
+    for k, v in flags.items():
+        if v:
+            raise ValueError(f"{what} does not support {k}={v!r}")
+
+
+class FusedAdam(_FusedMoment):
+    """torch.optim.Adam (single-tensor algorithm, fp32 state; amsgrad / maximize unsupported) as one fused step: see _FusedMoment."""
+
+    _what, _decoupled = "FusedAdam", False
+    _state_keys = ("exp_avg", "exp_avg_sq")
+    _group_keys = ("lr", "betas", "eps", "weight_decay")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False):
+        _reject(self._what, amsgrad=amsgrad, maximize=maximize)
+        self._init_groups(params, {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay})
+
+    def _record(self, g, p):
+        return self._buf(p, "exp_avg"), self._buf(p, "exp_avg_sq"), g["betas"][0], g["betas"][1]
+
+    def _launch(self, L, tab, n, n_chunks, inv, scale_ptr, max_norm, d, step, scratch, found, stream):
+        _lib.check(L.y3_adam_step(tab, n, n_chunks, inv, scale_ptr, max_norm, int(self._decoupled), d, step, scratch, found, stream), "y3_adam_step")
+
+    def _torch_group_extra(self):
+        return {"amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": self._decoupled}
+
+    def _check_flags(self, g):
+        _reject(self._what, amsgrad=g.get("amsgrad", False), maximize=g.get("maximize", False))
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: Adam with decoupled weight decay (p *= 1 - lr * wd before the update; torch's default weight_decay 0.01)."""
+
+    _what, _decoupled = "FusedAdamW", True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize)
+
+
+class FusedRMSProp(_FusedMoment):
+    """torch.optim.RMSprop (single-tensor algorithm, fp32 state; centered / maximize unsupported) as one fused step: see _FusedMoment.  A group with momentum > 0
+    keeps a momentum buffer, one without does not (as torch)."""
+
+    _what = "FusedRMSProp"
+    _state_keys = ("square_avg", "momentum_buffer")
+    _group_keys = ("lr", "alpha", "eps", "weight_decay", "momentum")
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, *, maximize=False):
+        _reject(self._what, centered=centered, maximize=maximize)
+        self._init_groups(params, {"lr": lr, "momentum": momentum, "alpha": alpha, "eps": eps, "weight_decay": weight_decay})
+
+    def _record(self, g, p):
+        mu = float(g["momentum"])
+        return self._buf(p, "square_avg"), (self._buf(p, "momentum_buffer") if mu > 0 else None), g["alpha"], mu
+
+    def _launch(self, L, tab, n, n_chunks, inv, scale_ptr, max_norm, d, step, scratch, found, stream):
+        _lib.check(L.y3_rmsprop_step(tab, n, n_chunks, inv, scale_ptr, max_norm, d, step, scratch, found, stream), "y3_rmsprop_step")
+
+    def _torch_group_extra(self):
+        return {"centered": False, "capturable": False, "foreach": None, "maximize": False, "differentiable": False}
+
+    def _check_flags(self, g):
+        _reject(self._what, centered=g.get("centered", False), maximize=g.get("maximize", False))
+
+
+def smart_optimizer(model: nn.Module, name: str = "Adam", lr: float = 0.001, momentum: float = 0.9, decay: float = 1e-5):
+    """The optimizer behind the reference's `train.py --optimizer {SGD,Adam,AdamW}` (RMSProp as well), on smart_param_groups' three groups: biases, weights (the only
+    group with weight decay), norm weights.  `momentum` is SGD's and RMSProp's momentum and Adam's / AdamW's beta1."""
+    groups = smart_param_groups(model, lr, decay)
+    if name == "SGD":
+        return FusedSGD(groups, lr=lr, momentum=momentum, nesterov=True)
+    if name == "Adam":
+        return FusedAdam(groups, lr=lr, betas=(momentum, 0.999))
+    if name == "AdamW":
+        return FusedAdamW(groups, lr=lr, betas=(momentum, 0.999), weight_decay=0.0)
+    if name == "RMSProp":
+        return FusedRMSProp(groups, lr=lr, momentum=momentum)
+    raise NotImplementedError(f"Optimizer {name} not implemented.")
 
 
 class GradScaler:
