@@ -406,6 +406,28 @@ typedef struct y3_pack_job {
 } y3_pack_job;
 int64_t y3_pack_job_blocks(int32_t ksize, int32_t cout, int32_t cin, int32_t want_fwd, int32_t want_dgrad);
 int y3_pack_filter_jobs(const y3_pack_job* jobs_device, int32_t n_jobs, int64_t total_blocks, int32_t dtype, void* stream);
+/* Conv + BatchNorm fold AND pack of every layer of an inference plan in one launch (what yolov3_amd/engine.py did per layer with torch arithmetic and one
+ * y3_pack_filter launch).  Per filter co: scale = gamma / sqrt(eps + var), w' = scale * w, b' = scale * b + (beta - gamma * mean / sqrt(var + eps)), b = conv_bias or 0,
+ * evaluated in fp32 with IEEE sqrt / division and no FMA contraction (the operations of upstream fuse_conv_and_bn one by one: the results equal torch's bit for
+ * bit), then w' is rounded to `dtype` (f16 / bf16 / f32) and written in the layout of y3_pack_filter -- or, stem != 0 (ksize 3, cin_src <= 4), of
+ * y3_pack_filter_stem -- and b' to bias[0 .. cout_src).  A job without BatchNorm (the Detect heads) has the four bn_* pointers NULL: w' = w, b' = b.
+ * `jobs` is a DEVICE array of 96-byte records; job i occupies blocks [first_block, first_block + y3_pack_job_blocks(ksize, cout, cin, 1, 0)) of the grid, the jobs
+ * laid out back to back.  Only elements that come from a weight are written: ZERO-FILL banks and bias vectors once when they are allocated. */
+typedef struct y3_fold_pack_job {
+    const float* w;            /* OIHW fp32 weights (nn.Conv2d.weight) */
+    const float* conv_bias;    /* cout_src floats, or NULL */
+    const float* bn_gamma;     /* nn.BatchNorm2d weight / bias / running_mean / running_var, cout_src floats each; all four NULL: no BatchNorm */
+    const float* bn_beta;
+    const float* bn_mean;
+    const float* bn_var;
+    void* packed;              /* y3_packed_filter_elems(cout, cin, ksize) elements of `dtype` (stem: y3_packed_filter_stem_elems(cout)) */
+    float* bias;               /* cout floats */
+    float bn_eps;
+    int32_t cout_src, cin_src, ksize, cout, cin;
+    int32_t stem;
+    int32_t first_block;
+} y3_fold_pack_job;
+int y3_fold_pack_jobs(const y3_fold_pack_job* jobs_device, int32_t n_jobs, int64_t total_blocks, int32_t dtype, void* stream);
 /* Data gradient of a 3x3 stride-2 pad-1 conv without multiplying the zero taps of the dilated form: four output-parity
  * classes, each a small stride-1 conv of du (1, 2, 2 and 4 taps) with its own filter bank, written to every second
  * pixel of gx (+= residual when given; residual may alias gx).  f16/bf16 only. */
@@ -468,6 +490,11 @@ int y3_adam_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, 
                  float ema_decay, int32_t* step, float* scratch, int32_t* found_inf, void* stream);
 int y3_rmsprop_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float inv_scale, const float* loss_scale, float max_norm, float ema_decay,
                     int32_t* step, float* scratch, int32_t* found_inf, void* stream);
+/* ModelEMA.update(model) on its own (reference train.py:421): ema = d * ema + (1 - d) * src for every record of the DEVICE table, one launch, with the lerp
+ * function of the fused steps above (the same bits as their ema pass).  Records of 32 bytes:
+ *   { float* ema; const float* src; int64 numel; int32 first_chunk; int32 pad; }   (chunks of 16384 elements; n_chunks = their total)
+ * 4-byte alignment is enough; tensors whose two pointers are 16-byte aligned are streamed 16 bytes at a time.  0 <= d <= 1. */
+int y3_ema_update(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float d, void* stream);
 /* The owner's step of the two-phase gradient exchange that replaces a bucket's all-reduce on a fully connected xGMI mesh (reference: DDP's gradient
    averaging, utils/torch_utils.py:60-72 smart_DDP / train.py:411): `parts` holds n_parts contributions of n floats each ([n_parts][n], what the all-to-all
    of the shards delivered); out[i] = (parts[0][i] + ... + parts[n_parts - 1][i]) * scale, added in that order.  `out` may alias none of `parts`. */

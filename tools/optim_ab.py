@@ -59,13 +59,15 @@ def torch_arm(**form):
     m, ps = model_with_grads(1.0)
     opt = torch.optim.Adam(smart_param_groups(m, 1e-3, 5e-4), **form)
     ema = ModelEMA(m)
+    src = [p.detach() for p in ema.shadow] + list(ema.buffers)
+    dst = list(ema.shadow.values()) + list(ema.buffers.values())
 
     def step():
         torch.nn.utils.clip_grad_norm_(ps, max_norm=MAX_NORM)
         opt.step()
         d = ema.next_decay()
-        ema.update_buffers(d)
-        ema.update_rest(d, set())   # the foreach lerp over every parameter
+        torch._foreach_mul_(dst, d)   # the foreach lerp over every parameter and float buffer (what ModelEMA ran before y3_ema_update: tools/ema_fold_pack_ab.py)
+        torch._foreach_add_(dst, src, alpha=1.0 - d)
 
     return step
 

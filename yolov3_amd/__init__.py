@@ -8,9 +8,10 @@ Public surface mirrors the reference's own Python signatures:
     ap_per_class / compute_ap / fitness  (reference utils/metrics.py:15-118; host NumPy, as in the reference)
     ap_per_class_device / ValStats / ConfusionMatrix / run_batches   (the same statistics kept and computed on the device: val.py:386-428)
     ComputeLoss                          (reference utils/loss.py)
-    FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update)
+    FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update; ema.ema is the averaged model)
     smart_optimizer / FusedAdam / FusedAdamW / FusedRMSProp   (reference utils/torch_utils.py:207-237, train.py --optimizer; torch-format state dicts)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
+    save_checkpoint / smart_resume / strip_optimizer   (reference train.py:470-488, utils/torch_utils.py smart_resume, utils/general.py strip_optimizer)
     DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py)
 Everything executes through libyolov3_hip.so (include/yolov3_hip.h); there is no CPU/PyTorch fallback.
 """
@@ -20,7 +21,7 @@ from .val import detect_batches, process_batch, process_batch_batched, run_batch
 from .metrics import ConfusionMatrix, ValStats, ap_per_class, ap_per_class_device, compute_ap, fitness  # noqa: F401
 from .backend import DetectMultiBackend  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
-from .compat import attempt_load  # noqa: F401
+from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401
 from .loss import ComputeLoss  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, FusedRMSProp, FusedSGD, GradScaler, ModelEMA, freeze_layers, smart_optimizer, smart_param_groups  # noqa: F401
 from .yolo import Detect, DetectionModel, Model, parse_model  # noqa: F401

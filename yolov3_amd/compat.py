@@ -12,6 +12,9 @@ including the reference's own classes when somebody else's ``torch.load`` produc
 which re-classes the module tree (the attribute names -- ``conv/bn/act``, ``cv1/cv2/add``, ``m/anchors/stride`` -- are
 the same) and swaps torch's parameter-free layers for the stand-ins the engine plans with.
 
+``save_checkpoint`` / ``smart_resume`` / ``strip_optimizer`` are the way OUT and back: the reference's checkpoint dict (train.py:470-488), its resume
+(utils/torch_utils.py smart_resume) and its final strip (utils/general.py strip_optimizer), over this package's model, ModelEMA and fused optimizers.
+
 ``install_aliases()`` remains for callers that use a plain ``torch.load`` in a process WITHOUT a reference checkout: it
 registers ``models`` / ``models.yolo`` / ``models.common`` / ``models.experimental`` alias modules, and only then: a real
 ``models`` package that is imported or importable is never shadowed or overwritten.
@@ -201,3 +204,59 @@ def attempt_load(weights, device=None, inplace=True, fuse=True):
         if isinstance(m, yolo.Detect):
             m.inplace = inplace
     return model
+
+
+def save_checkpoint(path, model, ema, optimizer, epoch, best_fitness=None, **extra):
+    """The reference's checkpoint (train.py:470-488): ``{"epoch", "best_fitness", "model": deepcopy(de_parallel(model)).half(), "ema": deepcopy(ema.ema).half(),
+    "updates": ema.updates, "optimizer": optimizer.state_dict(), **extra}`` written with ``torch.save``.  The half copies are made with torch on the copies (the
+    masters stay fp32); compiled plans live outside the modules and are never pickled.  Returns the dict."""
+    from copy import deepcopy
+
+    from .loss import de_parallel
+
+    ckpt = {
+        "epoch": epoch,
+        "best_fitness": best_fitness,
+        "model": deepcopy(de_parallel(model)).half(),
+        "ema": deepcopy(ema.ema).half() if ema is not None else None,
+        "updates": ema.updates if ema is not None else None,
+        "optimizer": optimizer.state_dict() if optimizer is not None else None,
+        **extra,
+    }
+    torch.save(ckpt, str(path))
+    return ckpt
+
+
+def smart_resume(ckpt, optimizer=None, ema=None, weights="", epochs=300, resume=True):
+    """reference utils/torch_utils.py smart_resume: restore the optimizer state, the averaged model and its update count from a checkpoint dict (``load_checkpoint``
+    reads one); returns (best_fitness, start_epoch, epochs)."""
+    best_fitness = 0.0
+    start_epoch = ckpt["epoch"] + 1
+    if ckpt.get("optimizer") is not None and optimizer is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+        best_fitness = ckpt["best_fitness"] if ckpt.get("best_fitness") is not None else 0.0
+    if ema is not None and ckpt.get("ema"):
+        ema.ema.load_state_dict(ckpt["ema"].float().state_dict())
+        ema.updates = ckpt["updates"]
+        ema.touched()   # (load_state_dict copies in place, which torch's version counters see; the bump covers a loader that does not)
+    if resume:
+        assert start_epoch > 0, f"{weights} training to {epochs} epochs is finished, nothing to resume.\nStart a new training without --resume, i.e. 'python train.py --weights {weights}'"
+    if epochs < start_epoch:
+        epochs += ckpt["epoch"]   # finetune additional epochs
+    return best_fitness, start_epoch, epochs
+
+
+def strip_optimizer(f="best.pt", s=""):
+    """reference utils/general.py strip_optimizer: finalise a checkpoint file -- ``model`` becomes the averaged model, the training state goes, half precision,
+    no gradients.  Written to `s` (or over `f`)."""
+    x = load_checkpoint(f)
+    if x.get("ema"):
+        x["model"] = x["ema"]
+    for k in ("optimizer", "best_fitness", "ema", "updates"):
+        x[k] = None
+    x["epoch"] = -1
+    x["model"].half()
+    for p in x["model"].parameters():
+        p.requires_grad = False
+    torch.save(x, str(s or f))
+    return x

@@ -93,6 +93,10 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
     }
 }
 
+// The ModelEMA lerp (upstream ModelEMA.update: v *= d; v += (1 - d) * p), the ONE definition every kernel of this file applies: the fused steps to the parameters
+// they just wrote, ema_update_kernel to everything else.  This file is built without FMA contraction: two products and a sum, each rounded once.
+__device__ __forceinline__ float ema_lerp(float e, float p, float d) { return d * e + (1.0f - d) * p; }
+
 // pass 2: p, buf, ema update (torch.optim.SGD semantics: g += wd*p; buf = first ? g : mu*buf + g; g = nesterov ? g + mu*buf : buf)
 __global__ __launch_bounds__(256) void sgd_update_kernel(const OptTensor* __restrict__ t, int n, float inv_scale, const float* __restrict__ scale_dev,
                                                            const float* __restrict__ clip, const int* __restrict__ found_inf, float momentum, int nesterov, int first_step,
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void sgd_update_kernel(const OptTensor* __rest
         g = nesterov ? g + momentum * b : b;
         p -= T.lr * g;
         T.param[e] = p;
-        if (T.ema) T.ema[e] = ema_decay * T.ema[e] + (1.0f - ema_decay) * p;
+        if (T.ema) T.ema[e] = ema_lerp(T.ema[e], p, ema_decay);
     }
 }
 
@@ -187,7 +191,6 @@ __device__ __forceinline__ void moment_update_chunk(const MomentTensor& T, const
     uintptr_t bits = (uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.s1 | (uintptr_t)T.ema;
     if (HAS_S2) bits |= (uintptr_t)T.s2;
     const int nvec = (bits & 15) == 0 ? (lim & ~3) : 0;   // elements handled as float4
-    const float em = 1.0f - ema_decay;
     for (int i = threadIdx.x * 4; i < nvec; i += 1024) {
         const long long e = base + i;
         f32x4 p = *(const f32x4*)(T.param + e);
@@ -206,7 +209,11 @@ __device__ __forceinline__ void moment_update_chunk(const MomentTensor& T, const
         *(f32x4*)(T.param + e) = p;
         *(f32x4*)(T.s1 + e) = a;
         if (HAS_S2) *(f32x4*)(T.s2 + e) = b;
-        if (T.ema) *(f32x4*)(T.ema + e) = ema_decay * m + em * p;
+        if (T.ema) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m[k] = ema_lerp(m[k], p[k], ema_decay);
+            *(f32x4*)(T.ema + e) = m;
+        }
     }
     for (int i = nvec + threadIdx.x; i < lim; i += 256) {
         const long long e = base + i;
@@ -215,7 +222,7 @@ __device__ __forceinline__ void moment_update_chunk(const MomentTensor& T, const
         T.param[e] = p;
         T.s1[e] = a;
         if (HAS_S2) T.s2[e] = b;
-        if (T.ema) T.ema[e] = ema_decay * T.ema[e] + em * p;
+        if (T.ema) T.ema[e] = ema_lerp(T.ema[e], p, ema_decay);
     }
 }
 
@@ -232,6 +239,38 @@ __global__ __launch_bounds__(256) void moment_update_kernel(const MomentTensor* 
     const Coef c(T, *step, decoupled);
     if (T.s2) moment_update_chunk<Coef, true>(T, c, base, gs, ema_decay);
     else moment_update_chunk<Coef, false>(T, c, base, gs, ema_decay);
+}
+
+// ModelEMA.update(model) on its own (reference train.py:421 after `scaler.step(optimizer)`; also what a fused step leaves over: the float buffers and the parameters
+// it did not touch): ema = ema_lerp(ema, src, d) for every record, one launch.  Streams 12 bytes per element; float4 where both pointers allow it.
+struct EmaTensor {
+    float* ema;
+    const float* src;
+    long long numel;
+    int first_chunk;          // prefix sum of chunk counts
+    int pad;
+};
+static_assert(sizeof(EmaTensor) == 32, "the host mirror (yolov3_amd/optim.py) packs 32-byte records");
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor* __restrict__ t, int n, float d) {
+    const int ti = find_tensor(t, n, blockIdx.x);
+    const EmaTensor T = t[ti];
+    const long long base = (long long)(blockIdx.x - T.first_chunk) * CHUNK;
+    const long long left = T.numel - base;
+    const int lim = left < CHUNK ? (int)left : CHUNK;
+    const int nvec = (((uintptr_t)T.ema | (uintptr_t)T.src) & 15) == 0 ? (lim & ~3) : 0;
+    for (int i = threadIdx.x * 4; i < nvec; i += 1024) {
+        const long long e = base + i;
+        f32x4 m = *(const f32x4*)(T.ema + e);
+        const f32x4 p = *(const f32x4*)(T.src + e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m[k] = ema_lerp(m[k], p[k], d);
+        *(f32x4*)(T.ema + e) = m;
+    }
+    for (int i = nvec + threadIdx.x; i < lim; i += 256) {
+        const long long e = base + i;
+        T.ema[e] = ema_lerp(T.ema[e], T.src[e], d);
+    }
 }
 
 // torch.cuda.amp.GradScaler.update() (reference train.py:345,416-417; ATen _amp_update_scale_): on a step that found inf/nan the scale
@@ -316,6 +355,15 @@ extern "C" int y3_loss_scale_update(float* loss_scale, int32_t* growth_tracker, 
                                     void* stream) {
     if (!loss_scale || !growth_tracker || !found_inf || growth_interval < 1) Y3_FAIL("y3_loss_scale_update: bad argument");
     hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_ema_update(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float d, void* stream) {
+    if (!tensor_table) Y3_FAIL("y3_ema_update: null tensor table");
+    if (n_tensors <= 0 || n_chunks <= 0) Y3_FAIL("y3_ema_update: n_tensors %d and n_chunks %d must be positive", (int)n_tensors, (int)n_chunks);
+    if (!(d >= 0.0f && d <= 1.0f)) Y3_FAIL("y3_ema_update: decay %g is outside [0, 1]", (double)d);
+    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const EmaTensor*)tensor_table, n_tensors, d);
     Y3_CHECK_LAUNCH();
     return 0;
 }

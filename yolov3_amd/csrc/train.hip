@@ -1081,6 +1081,94 @@ __global__ __launch_bounds__(256) void pack_filter_jobs_kernel(const y3_pack_job
     }
 }
 
+// ---- inference plans: Conv + BatchNorm fold and pack of EVERY layer in one launch (y3_fold_pack_jobs) ------------------------------------------------------------
+// The algebra of upstream fuse_conv_and_bn as yolov3_amd/engine.py::_fold evaluates it with torch, operation for operation: IEEE sqrt and division, every product and
+// sum rounded on its own (no FMA contraction in these two functions, whatever the file is built with) -- the banks equal the ones _fold + y3_pack_filter write, bit for bit.
+__device__ __forceinline__ float fold_scale(float gamma, float var, float eps) {
+#pragma clang fp contract(off)
+    return gamma / sqrtf(eps + var);
+}
+__device__ __forceinline__ float fold_bias(float scale, float b, float gamma, float beta, float mean, float var, float eps) {
+#pragma clang fp contract(off)
+    const float gm = gamma * mean;
+    const float b_bn = beta - gm / sqrtf(var + eps);
+    const float sb = scale * b;
+    return sb + b_bn;
+}
+
+// The tiling of pack_filter_jobs_kernel (a block owns 32 filters x 32 channels of one job, found by a binary search over first_block); the weights are scaled by their
+// filter's BatchNorm factor on the way into LDS and leave in the layout of y3_pack_filter (+ the fragment-ordered copy) or, for a `stem` job, of y3_pack_filter_stem
+// ([filter][kh][kw * 4 + channel]).  The block of channel tile 0 also writes its 32 entries of the fp32 bias vector.  Only elements that come from a weight are written:
+// banks and bias vectors are zero-filled once by the caller.
+template <typename T>
+__global__ __launch_bounds__(256) void fold_pack_jobs_kernel(const y3_fold_pack_job* __restrict__ jobs, int n_jobs) {
+    __shared__ T tile[9][32][34];
+    __shared__ float sc[32];
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const y3_fold_pack_job j = jobs[lo];
+    const float* __restrict__ src = j.w;
+    const int ks = j.ksize, KK = ks * ks, cin = j.cin, cout = j.cout;
+    const int n_tci = (cin + 31) / 32;
+    const int t = (int)blockIdx.x - j.first_block;
+    const int co0 = (t / n_tci) * 32, ci0 = (t % n_tci) * 32;
+    if (co0 >= j.cout_src || ci0 >= j.cin_src) return;   // a tile of padding only (uniform)
+    const int tid = threadIdx.x;
+    const bool bn = j.bn_gamma != nullptr;
+    if (tid < 32) {
+        const int co = co0 + tid;
+        float s = 1.0f;
+        if (co < j.cout_src) {
+            if (bn) s = fold_scale(j.bn_gamma[co], j.bn_var[co], j.bn_eps);
+            if (ci0 == 0) {
+                const float b = j.conv_bias ? j.conv_bias[co] : 0.0f;
+                j.bias[co] = bn ? fold_bias(s, b, j.bn_gamma[co], j.bn_beta[co], j.bn_mean[co], j.bn_var[co], j.bn_eps) : b;
+            }
+        }
+        sc[tid] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < 32 * 32 * KK; e += 256) {
+        const int co_l = e / (32 * KK), r = e - co_l * (32 * KK);
+        const int ci_l = r / KK, tap = r - ci_l * KK;
+        const int co = co0 + co_l, ci = ci0 + ci_l;
+        float v = 0.0f;
+        if (co < j.cout_src && ci < j.cin_src) {
+            v = src[((long long)co * j.cin_src + ci) * KK + tap];
+            if (bn) v = sc[co_l] * v;
+        }
+        tile[tap][co_l][ci_l] = from_f32<T>(v);
+    }
+    __syncthreads();
+    T* __restrict__ dst = (T*)j.packed;
+    if (j.stem) {   // ksize 3, <= 4 channels (checked by the host mirror): one channel tile
+        for (int e = tid; e < 32 * 4 * 9; e += 256) {
+            const int c = e & 3, co_l = (e >> 2) & 31, tap = e >> 7;
+            const int co = co0 + co_l;
+            if (co < j.cout_src && c < j.cin_src) {
+                const int kh = tap / 3, kw = tap - kh * 3;
+                dst[(long long)co * 48 + kh * 16 + kw * 4 + c] = tile[tap][co_l][c];
+            }
+        }
+        return;
+    }
+    const int rows_f = (cout + 127) / 128 * 128, kpad_f = (KK * cin + 63) / 64 * 64;
+    const bool frag = y3_filter_has_frag(cout, cin, ks);
+    for (int e = tid; e < 32 * 32 * KK; e += 256) {
+        const int ci_l = e & 31, co_l = (e >> 5) & 31, tap = e >> 10;
+        const int co = co0 + co_l, ci = ci0 + ci_l;
+        if (co < j.cout_src && ci < j.cin_src) {
+            const T v = tile[tap][co_l][ci_l];
+            const int k = tap * cin + ci;
+            dst[(long long)co * kpad_f + k] = v;
+            if (frag) dst[(long long)rows_f * kpad_f + y3_frag_index(co, k, cin)] = v;   // the copy conv_v10.h reads (y3_common.h)
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // backward of nearest x2 upsampling: dx[h,w] (+)= sum of the 2x2 block of dy
 template <typename T>
@@ -2146,6 +2234,22 @@ extern "C" int y3_pack_filter_jobs(const y3_pack_job* jobs_device, int32_t n_job
     if (dtype == Y3_F16) hipLaunchKernelGGL((pack_filter_jobs_kernel<f16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs);
     else if (dtype == Y3_BF16) hipLaunchKernelGGL((pack_filter_jobs_kernel<bf16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs);
     else Y3_FAIL("y3_pack_filter_jobs: f16/bf16 only");
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+// One launch for a whole model's inference banks: see fold_pack_jobs_kernel.  The table is DEVICE memory and cannot be inspected here: its geometry is the host mirror's
+// (yolov3_amd/engine.py::FoldPackJobs) to get right.
+extern "C" int y3_fold_pack_jobs(const y3_fold_pack_job* jobs_device, int32_t n_jobs, int64_t total_blocks, int32_t dtype, void* stream) {
+    if (!jobs_device) Y3_FAIL("y3_fold_pack_jobs: null job table");
+    if (n_jobs <= 0 || total_blocks <= 0 || total_blocks > 0x7fffffffLL) Y3_FAIL("y3_fold_pack_jobs: n_jobs %d and total_blocks %lld must be positive (and fit a grid)", (int)n_jobs, (long long)total_blocks);
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case Y3_F16: hipLaunchKernelGGL((fold_pack_jobs_kernel<f16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
+        case Y3_BF16: hipLaunchKernelGGL((fold_pack_jobs_kernel<bf16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
+        case Y3_F32: hipLaunchKernelGGL((fold_pack_jobs_kernel<float>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
+        default: Y3_FAIL("y3_fold_pack_jobs: bad dtype %d (f16 / bf16 / f32)", (int)dtype);
+    }
     Y3_CHECK_LAUNCH();
     return 0;
 }

@@ -188,13 +188,14 @@ def _fold(conv: nn.Conv2d, bn):
 KEEP_FOLDED = False  # tests set this to keep the fp32 folded (w, b) next to the packed bank
 
 
-def make_conv_weights(conv: nn.Conv2d, bn, act: bool, dtype, cin_pad=None, cache: dict | None = None) -> ConvWeights:
+def make_conv_weights(conv: nn.Conv2d, bn, act: bool, dtype, cin_pad=None, cache: dict | None = None, fold: "FoldPackJobs | None" = None) -> ConvWeights:
     """Fold + pack one conv.  `cache` (PlanCache.weights) shares the packed bank between the plans of a model: rect-batch
-    validation compiles dozens of (h, w) shapes (reference utils/dataloaders.py:548-570) and each used to re-pack 124 MB."""
+    validation compiles dozens of (h, w) shapes (reference utils/dataloaders.py:548-570) and each used to re-pack 124 MB.
+    With `fold` (the model's FoldPackJobs) the bank is only allocated here: one launch fills every bank of the model before the plan runs."""
     key = (id(conv), id(bn), bool(act), dtype, cin_pad)
     if cache is not None and key in cache:
         return cache[key]
-    cw = _make_conv_weights(conv, bn, act, dtype, cin_pad)
+    cw = fold.add(conv, bn, act, cin_pad) if fold is not None else _make_conv_weights(conv, bn, act, dtype, cin_pad)
     if cache is not None:
         cache[key] = cw
     return cw
@@ -212,6 +213,80 @@ def _make_conv_weights(conv: nn.Conv2d, bn, act: bool, dtype, cin_pad=None) -> C
     if KEEP_FOLDED:
         cw.folded = (w, b)
     return cw
+
+
+class FoldPackJobs:
+    """Every bank of a model's inference plans in ONE launch (y3_fold_pack_jobs: Conv + BatchNorm fold and pack on the device, from the parameters as they are --
+    fp32 masters are rounded to the plan dtype once, here).  `add` registers a conv (+ its BatchNorm) and returns its ConvWeights with a zero-filled bank and bias
+    vector, `run` fills all of them from the current parameters.  The plans hold pointers to the banks, so after a weight change `run` alone brings every compiled
+    plan up to date.  Modelled on ops.PackJobs: the device job table is persistent and rebuilt only when a tensor moved (data_ptr changed) or a job was added."""
+
+    def __init__(self, dtype: torch.dtype, device):
+        self.dtype, self.device = dtype, device
+        self.jobs = []        # (conv, bn, ConvWeights, real (cout, cin, k), stem)
+        self.dirty = False    # the banks do not hold the current parameters
+        self._table = None    # (device table, source data_ptrs, blocks)
+        self._keep = None     # fp32 copies of parameters that are not fp32 (a model cast to half), alive until the next run
+
+    def add(self, conv: nn.Conv2d, bn, act: bool, cin_pad=None, stem=False) -> ConvWeights:
+        co, ci, k, _ = conv.weight.shape
+        cout = _pad8(co)
+        if stem:
+            cin, elems = ci, int(_lib.lib().y3_packed_filter_stem_elems(cout))
+            if k != 3 or ci > 4:
+                raise ValueError("the stem bank holds 3x3 filters over at most 4 channels")
+        else:
+            cin = cin_pad or _pad8(ci)
+            elems = ops.packed_filter_elems(cout, cin, k)
+        # zero-filled ONCE: the launch writes only the elements that come from a weight (the row / K padding of a bank and the bias padding stay zero)
+        cw = ConvWeights(torch.zeros(elems, dtype=self.dtype, device=self.device), torch.zeros(cout, dtype=torch.float32, device=self.device), cin, cout, k,
+                         conv.stride[0], act)
+        self.jobs.append((conv, bn, cw, (co, ci, k), bool(stem)))
+        self._table, self.dirty = None, True
+        return cw
+
+    def valid(self) -> bool:
+        """every registered layer still has the weight shape (and the BatchNorm) its bank was sized for"""
+        return all(tuple(conv.weight.shape[:3]) == shape and (bn is None or bn.running_var is not None) for conv, bn, _cw, shape, _s in self.jobs)
+
+    @staticmethod
+    def _f32(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+    def run(self):
+        if not self.jobs:
+            self.dirty = False
+            return
+        import struct
+
+        srcs = []
+        for conv, bn, _cw, _shape, _stem in self.jobs:
+            ts = (conv.weight, conv.bias) + ((bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4)
+            srcs.append([self._f32(t) for t in ts])
+        ptrs = [t.data_ptr() if t is not None else 0 for row in srcs for t in row]
+        if self._table is None or self._table[1] != ptrs:
+            L = _lib.lib()
+            rows, first = [], 0
+            for (conv, bn, cw, (co, ci, k), stem), row in zip(self.jobs, srcs):
+                if tuple(row[0].shape) != (co, ci, k, k) or any(t is not None and t.numel() != co for t in row[1:]):
+                    raise ValueError("a layer changed shape under its compiled plans: call model._drop_plans()")
+                grid_cin = 8 if stem else cw.cin
+                rows.append(struct.pack("<8Qf7i", *(t.data_ptr() if t is not None else 0 for t in row), cw.filt.data_ptr(), cw.bias.data_ptr(),
+                                        float(bn.eps) if bn is not None else 0.0, co, ci, k, cw.cout, grid_cin, int(stem), first))
+                first += int(L.y3_pack_job_blocks(k, cw.cout, grid_cin, 1, 0))
+            host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
+            self._table = (host.to(self.device), ptrs, first)
+        self._keep = srcs
+        _lib.check(_lib.lib().y3_fold_pack_jobs(self._table[0].data_ptr(), len(self.jobs), self._table[2], ops.dtype_code(self.dtype), ops.stream_ptr()), "y3_fold_pack_jobs")
+        self.dirty = False
+
+
+def fold_pack_enabled() -> bool:
+    """Y3_FOLD_PACK=0 restores the fold with torch arithmetic and one y3_pack_filter launch per layer (A/B runs; the tests compare the two)"""
+    return os.environ.get("Y3_FOLD_PACK", "1") != "0" and not KEEP_FOLDED
 
 
 # ------------------------------------------------------------------------------------------- plan
@@ -424,8 +499,8 @@ def _param_version(params):
 
 # ------------------------------------------------------------------------------------------- graph compiler
 class _Compiler:
-    def __init__(self, plan: Plan, dtype, training=False, wcache=None):
-        self.plan, self.dtype, self.training, self.wcache = plan, dtype, training, wcache
+    def __init__(self, plan: Plan, dtype, training=False, wcache=None, fold=None):
+        self.plan, self.dtype, self.training, self.wcache, self.fold = plan, dtype, training, wcache, fold
         if training:
             raise NotImplementedError(
                 "training-mode forward (batch-statistics BatchNorm + backward) is not implemented on the MI355X path yet; "
@@ -434,7 +509,7 @@ class _Compiler:
 
     def conv_unit(self, m: Conv, x: SView, y: SView = None, residual=None, ups=False, label="", cin_pad=None):
         p = self.plan
-        w = make_conv_weights(m.conv, getattr(m, "bn", None), isinstance(m.act, nn.SiLU), self.dtype, cin_pad=cin_pad, cache=self.wcache)
+        w = make_conv_weights(m.conv, getattr(m, "bn", None), isinstance(m.act, nn.SiLU), self.dtype, cin_pad=cin_pad, cache=self.wcache, fold=self.fold)
         if y is None:
             ho, wo = _conv_hw((x.h, x.w), w.k, w.s)
             y = p.new_view(x.n, ho, wo, w.cout, label)
@@ -446,8 +521,8 @@ class _Compiler:
             # Bottleneck(64, 64) / Bottleneck(128, 128) (yolov3 layers 2 and 4, the 320x320 / 160x160 maps): one kernel, the C/2-channel
             # intermediate stays in LDS and x is read once
             p = self.plan
-            w1 = make_conv_weights(m.cv1.conv, getattr(m.cv1, "bn", None), isinstance(m.cv1.act, nn.SiLU), self.dtype, cin_pad=x.c, cache=self.wcache)
-            w2 = make_conv_weights(m.cv2.conv, getattr(m.cv2, "bn", None), isinstance(m.cv2.act, nn.SiLU), self.dtype, cin_pad=x.c // 2, cache=self.wcache)
+            w1 = make_conv_weights(m.cv1.conv, getattr(m.cv1, "bn", None), isinstance(m.cv1.act, nn.SiLU), self.dtype, cin_pad=x.c, cache=self.wcache, fold=self.fold)
+            w2 = make_conv_weights(m.cv2.conv, getattr(m.cv2, "bn", None), isinstance(m.cv2.act, nn.SiLU), self.dtype, cin_pad=x.c // 2, cache=self.wcache, fold=self.fold)
             if y is None:
                 y = p.new_view(x.n, x.h, x.w, x.c, label)
             p.add("bneck_pair", [x], [y], x=x, y=y, w1=w1, w2=w2, add=bool(m.add), label=label)
@@ -513,11 +588,18 @@ def _stem_pair_eligible(g: Graph, placed, fused_ups) -> bool:
             and c1.dilation == (1, 1) and c1.groups == 1 and isinstance(m0.act, (nn.SiLU, nn.Identity)) and isinstance(m1.act, (nn.SiLU, nn.Identity)))
 
 
-def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
+EVAL_PLAN_BUILDS = 0   # compile_model calls in this process (the tests of per-epoch validation count them)
+
+
+def compile_model(model, n, h, w, dtype, device, wcache=None, fold: FoldPackJobs | None = None) -> Plan:
+    """`fold`: the model's FoldPackJobs (run_model passes it): banks are registered there instead of being folded and packed layer by layer, and are valid once
+    `fold.run()` has been issued."""
     from .yolo import Detect
 
+    global EVAL_PLAN_BUILDS
+    EVAL_PLAN_BUILDS += 1
     plan = Plan(device, dtype, n, h, w)
-    comp = _Compiler(plan, dtype, training=model.training, wcache=wcache)
+    comp = _Compiler(plan, dtype, training=model.training, wcache=wcache, fold=fold)
     g = Graph(model, h, w)
     layers = g.layers
 
@@ -552,7 +634,7 @@ def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
             heads = []
             for lvl, xv in enumerate(ins):
                 conv = k.m[lvl]
-                wts = make_conv_weights(conv, None, False, dtype, cin_pad=xv.c, cache=wcache)
+                wts = make_conv_weights(conv, None, False, dtype, cin_pad=xv.c, cache=wcache, fold=fold)
                 hv = plan.new_view(xv.n, xv.h, xv.w, wts.cout, f"{lab}.head{lvl}")
                 hv.buf.pinned = True
                 plan.conv(xv, wts, hv, label=f"{lab}.m{lvl}")
@@ -594,12 +676,16 @@ def compile_model(model, n, h, w, dtype, device, wcache=None) -> Plan:
             out[i] = y
         elif isinstance(k, Conv) and i == 1 and pair:
             w0 = pair
-            w1 = make_conv_weights(k.conv, getattr(k, "bn", None), isinstance(k.act, nn.SiLU), dtype, cin_pad=32, cache=wcache)
+            w1 = make_conv_weights(k.conv, getattr(k, "bn", None), isinstance(k.act, nn.SiLU), dtype, cin_pad=32, cache=wcache, fold=fold)
             plan.add("stem_pair", [], [y], w0=w0, w1=w1, y=y, cin=w0.cin, h=h, w=w, label="L0+L1")
             out[i] = y
         elif i == 0 and _stem_eligible(g, dtype):
             skey = ("stem", id(k.conv), id(getattr(k, "bn", None)), dtype)
             wts = wcache.get(skey) if wcache is not None else None
+            if wts is None and fold is not None:
+                wts = fold.add(k.conv, getattr(k, "bn", None), isinstance(k.act, nn.SiLU), stem=True)
+                if wcache is not None:
+                    wcache[skey] = wts
             if wts is None:
                 cw, cb = _fold(k.conv, getattr(k, "bn", None))
                 co = cw.shape[0]
@@ -684,6 +770,8 @@ class PlanCache:
         self.plans: "OrderedDict" = OrderedDict()
         self.weights: dict = {}
         self.weights_version = None
+        self.weights_epoch = 0   # the model's weights_epoch the banks were filled at
+        self.fold: dict = {}    # plan dtype -> FoldPackJobs: every bank in self.weights of that dtype (None values: the per-layer path, Y3_FOLD_PACK=0)
         self.slots: dict = {}   # (dtype, device index) -> [TrainSlot] * MAX_TRAIN
         self.lock = threading.Lock()
 
@@ -691,6 +779,7 @@ class PlanCache:
         with self.lock:
             self.plans.clear()
             self.weights.clear()
+            self.fold.clear()
             self.slots.clear()
             self.weights_version = None
 
@@ -764,7 +853,8 @@ def run_model(model, x: torch.Tensor, profile=False):
         from .train_engine import run_model_train
 
         return run_model_train(model, x)
-    dtype = _engine_dtype(model)
+    dtype = getattr(model, "infer_dtype", None) or _engine_dtype(model)   # infer_dtype: half-precision plans straight from fp32 masters (yolo.BaseModel)
+    ops.dtype_code(dtype)
     n, c, h, w = x.shape
     stream = ops.stream_ptr()
     pc = plan_cache(model)
@@ -772,16 +862,39 @@ def run_model(model, x: torch.Tensor, profile=False):
     with pc.lock:
         refs = list(model.parameters()) + list(model.buffers())
         version = (_param_version(refs), len(refs))
-        if pc.weights_version != version:   # parameters were modified in place (or replaced) since the filters were packed
+        # weights_epoch: writers torch's version counters do not see (ModelEMA: the fused steps write the average through raw pointers) count their updates there
+        epoch = int(getattr(model, "weights_epoch", 0))
+        use_fold = fold_pack_enabled()
+        refill = pc.weights_version == version and pc.weights_epoch != epoch and use_fold and bool(pc.fold) and all(f is not None and f.valid() for f in pc.fold.values())
+        if refill:
+            # only the epoch moved (an EMA update): the tensors are the ones the banks were made from, with new values.  The plans point at the banks: one launch per
+            # dtype refills them (below, when a plan of that dtype runs) and nothing is rebuilt -- per-epoch validation of a moving average compiles once
+            for f in pc.fold.values():
+                f.dirty = True
+        elif pc.weights_version != version or pc.weights_epoch != epoch:
+            # parameters were modified in place where torch sees it (or replaced) since the filters were packed: plans and banks go, as they always did
             for k in [k for k in pc.plans if k[0] != "train"]:   # training plans re-pack their banks from the fp32 masters every forward: they stay
                 del pc.plans[k]
             pc.weights.clear()
-            pc.weights_version = version
+            pc.fold.clear()
+        pc.weights_version, pc.weights_epoch = version, epoch
+        if dtype in pc.fold and (pc.fold[dtype] is not None) != use_fold:   # the switch moved since the banks of this dtype were made
+            for k in [k for k in pc.plans if k[0] != "train" and k[4] == dtype]:
+                del pc.plans[k]
+            for k in [k for k in pc.weights if dtype in k]:
+                del pc.weights[k]
+            del pc.fold[dtype]
+        if dtype not in pc.fold:
+            pc.fold[dtype] = FoldPackJobs(dtype, x.device) if use_fold else None
+        fold = pc.fold[dtype]
         plan = pc.get(key)
         if plan is None:
             with torch.no_grad():
-                plan = compile_model(model, n, h, w, dtype, x.device, wcache=pc.weights)
+                plan = compile_model(model, n, h, w, dtype, x.device, wcache=pc.weights, fold=fold)
             pc.put(key, plan)
+        if fold is not None and fold.dirty:
+            with torch.no_grad():
+                fold.run()
     # uint8 images are normalised inside the first kernel: the `im.half(); im /= 255` of reference val.py:358-359 / detect.py:187-189 /
     # models/common.py:868 without a separate pass over the batch
     div = 255.0 if x.dtype == torch.uint8 else 1.0

@@ -61,35 +61,98 @@ def freeze_layers(model: nn.Module, freeze) -> list:
 
 
 class ModelEMA:
-    """Exponential moving average of the parameters (upstream ultralytics ModelEMA; reference train.py:252,421):
-    d = decay * (1 - exp(-updates / tau)); ema = d * ema + (1 - d) * p.  Buffers (BN running stats) are copied like the
-    float entries of the state dict are lerped upstream -- here they are lerped by a torch foreach on the (small) buffers."""
+    """Exponential moving average of the model (upstream ultralytics ModelEMA; reference train.py:252,421,437): d = decay * (1 - exp(-updates / tau));
+    ema = d * ema + (1 - d) * model, over every floating entry of the state dict.
+
+    ``ema`` is the averaged MODEL, as upstream: a deep copy of the (de-parallelised) model in eval mode whose parameters do not require a gradient -- validate it
+    (``run_batches(ema.ema, ..., half=True)``), save it (``compat.save_checkpoint``).  Its parameters and float buffers are the very tensors the fused optimizer steps
+    lerp into (``step(ema=ema)``; what a step does not touch -- buffers, frozen parameters -- follows in one y3_ema_update launch), and ``update(model)`` is the
+    reference's standalone call: one launch for everything.  ``shadow`` / ``buffers`` map the TRAINING model's parameters / float buffers to their averages.
+
+    The kernels write the averages through raw pointers, which torch's version counters do not see: every update bumps ``ema.weights_epoch`` instead, and the engine
+    refills the filter banks of ``ema``'s inference plans when that moved (no plan is rebuilt, nothing is launched here)."""
 
     def __init__(self, model: nn.Module, decay=0.9999, tau=2000, updates=0):
+        from copy import deepcopy
+
+        from .loss import de_parallel
+
         self.model = model
-        self.shadow = {p: p.detach().clone() for p in model.parameters()}
-        self.buffers = {b: b.detach().clone() for b in model.buffers() if b.dtype.is_floating_point}
+        self.ema = deepcopy(de_parallel(model)).eval()
+        for p in self.ema.parameters():
+            p.requires_grad_(False)
+            p.grad = None
         self.decay, self.tau, self.updates = decay, tau, updates
+        self.rebind(model)
+
+    def rebind(self, model: nn.Module):
+        """(re)build the maps from `model`'s tensors to the averages (after the parameters of either were replaced: ``.to()``, ``.float()``)"""
+        from .loss import de_parallel
+
+        m = de_parallel(model)
+        self.shadow = dict(zip(m.parameters(), self.ema.parameters()))
+        self.buffers = {b: e for b, e in zip(m.buffers(), self.ema.buffers()) if b.dtype.is_floating_point}
+        self._tables = {}
 
     def next_decay(self) -> float:
         self.updates += 1
         return self.decay * (1 - math.exp(-self.updates / self.tau))
 
+    def touched(self):
+        """the averages were written behind torch's back: make the plan cache of `ema` see a new version (host only)"""
+        self.ema.weights_epoch = int(getattr(self.ema, "weights_epoch", 0)) + 1
+
+    def _lerp(self, kind: str, pairs, d: float):
+        """ema = d * ema + (1 - d) * src over (src, ema) pairs in one y3_ema_update launch; the device table of `kind` is rebuilt only when a tensor moved"""
+        if not pairs:
+            return
+        ptrs = [t.data_ptr() for pr in pairs for t in pr]
+        ent = self._tables.get(kind)
+        if ent is None or ent[1] != ptrs:
+            rows, n_chunks = [], 0
+            for src, dst in pairs:
+                ops.require_gpu(dst, "ModelEMA.update")
+                if src.dtype != torch.float32 or dst.dtype != torch.float32 or not src.is_contiguous() or not dst.is_contiguous() or src.numel() != dst.numel() or src.device != dst.device:
+                    raise TypeError("ModelEMA averages contiguous fp32 tensors (fp32 master weights) that live on the model's device")
+                if src.numel() == 0:
+                    continue
+                rows.append(struct.pack("<QQqii", dst.data_ptr(), src.data_ptr(), src.numel(), n_chunks, 0))
+                n_chunks += (src.numel() + CHUNK - 1) // CHUNK
+            host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
+            ent = self._tables[kind] = (host.to(pairs[0][1].device), ptrs, len(rows), n_chunks)
+        _lib.check(_lib.lib().y3_ema_update(ent[0].data_ptr(), ent[2], ent[3], float(d), ops.stream_ptr()), "y3_ema_update")
+
+    @torch.no_grad()
+    def update(self, model: nn.Module):
+        """The reference's ``ema.update(model)`` after ``scaler.step(optimizer)`` (train.py:421) for loops that do not pass ``ema=`` to the fused step."""
+        from .loss import de_parallel
+
+        m = de_parallel(model)
+        d = self.next_decay()
+        msd, esd = m.state_dict(keep_vars=True), self.ema.state_dict(keep_vars=True)
+        self._lerp("all", [(msd[k].detach(), v.detach()) for k, v in esd.items() if v.dtype.is_floating_point], d)
+        self.touched()
+
     def update_buffers(self, d: float):
-        if self.buffers:
-            src = list(self.buffers.keys())
-            dst = list(self.buffers.values())
-            torch._foreach_mul_(dst, d)
-            torch._foreach_add_(dst, src, alpha=1.0 - d)
+        self._lerp("buffers", [(b, e) for b, e in self.buffers.items()], d)
 
     def update_rest(self, d: float, stepped: set):
         """the parameters (`stepped`: ids) the fused step did not touch (frozen ones: no gradient): upstream's ModelEMA.update lerps every float entry of the state dict, so their
         averages still move toward the (unchanged) value -- it matters when the average was loaded from a checkpoint and differs from the weights"""
-        rest = [p for p in self.shadow if id(p) not in stepped]
-        if rest:
-            dst = [self.shadow[p] for p in rest]
-            torch._foreach_mul_(dst, d)
-            torch._foreach_add_(dst, [p.detach() for p in rest], alpha=1.0 - d)
+        self._lerp("rest", [(p.detach(), e) for p, e in self.shadow.items() if id(p) not in stepped], d)
+
+    def after_step(self, d: float, stepped: set):
+        """what a fused step with ``ema=`` leaves over -- the float buffers and the parameters it did not touch -- in one launch, and the version bump"""
+        pairs = [(p.detach(), e) for p, e in self.shadow.items() if id(p) not in stepped] if len(stepped) < len(self.shadow) else []
+        self._lerp("after_step", pairs + [(b, e) for b, e in self.buffers.items()], d)
+        self.touched()
+
+    def update_attr(self, model: nn.Module, include=(), exclude=("process_group", "reducer")):
+        """upstream copy_attr (reference train.py:437 ``ema.update_attr(model, include=["yaml", "nc", "hyp", "names", "stride", "class_weights"])``)"""
+        for k, v in model.__dict__.items():
+            if (len(include) and k not in include) or k.startswith("_") or k in exclude:
+                continue
+            setattr(self.ema, k, v)
 
 
 class FusedSGD:
@@ -165,9 +228,7 @@ class FusedSGD:
                 "y3_sgd_step",
             )
         if ema is not None:
-            ema.update_buffers(d)
-            if len(recs) < len(ema.shadow):
-                ema.update_rest(d, stepped)
+            ema.after_step(d, stepped)
         self._steps += 1
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
 
@@ -320,9 +381,7 @@ class _FusedMoment:
         self._launch(L, tab.data_ptr(), len(recs), n_chunks, inv, scale_ptr, float(max_norm), float(d), self._step_dev.data_ptr(), scratch.data_ptr(), found.data_ptr(),
                      ops.stream_ptr())
         if ema is not None:
-            ema.update_buffers(d)
-            if len(recs) < len(ema.shadow):
-                ema.update_rest(d, stepped)
+            ema.after_step(d, stepped)
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
 
     def _torch_group_extra(self) -> dict:

@@ -46,11 +46,40 @@ def process_batch_batched(rows, counts, labels, label_offsets, iouv):
     return ops.match_detections_raw(rows, rows.stride(0), rows.stride(1), counts, rows.shape[0], rows.shape[1], lab, offs, thr)
 
 
-def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, max_det=300):
+class _infer_dtype:
+    """``with _infer_dtype(model, half, dtype):`` -- the model's inference plans run in `dtype` (half: float16) inside the block, whatever its parameters are: fp32
+    masters are read as they are and rounded once when the filter banks are packed (no ``model.half()`` ... ``model.float()`` round trip, reference val.py).
+    Neither given: the block changes nothing."""
+
+    def __init__(self, model, half=False, dtype=None):
+        self.dtype = dtype if dtype is not None else (torch.float16 if half else None)
+        self.target = None
+        if self.dtype is not None:
+            self.target = model if hasattr(model, "infer_dtype") else getattr(model, "model", None)   # (DetectMultiBackend wraps the model)
+            if not hasattr(self.target, "infer_dtype"):
+                raise TypeError("half= / dtype= need a yolov3_amd model (DetectionModel, or a DetectMultiBackend around one)")
+
+    def __enter__(self):
+        if self.target is not None:
+            self.saved = self.target.__dict__.get("infer_dtype", self)
+            self.target.infer_dtype = self.dtype
+        return self.dtype
+
+    def __exit__(self, *exc):
+        if self.target is not None:
+            if self.saved is self:
+                self.target.__dict__.pop("infer_dtype", None)
+            else:
+                self.target.infer_dtype = self.saved
+        return False
+
+
+def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, max_det=300, half=False, dtype=None):
     """Throughput form of the `model(im)` -> `non_max_suppression(preds)` pair of reference val.py:364-376 / detect.py:196-200
     over a stream of batches: the NMS of batch i (a chain of small launches ending in the one device->host copy of the counts)
     runs on a second HIP stream while the forward of batch i+1 fills the CUs on the current stream.  Yields, in order and one
-    batch late, the list of (n, 6) detections of every batch -- the same tensors the sequential pair returns."""
+    batch late, the list of (n, 6) detections of every batch -- the same tensors the sequential pair returns.  `half` / `dtype`: run the forwards in that
+    precision from the parameters as they are (fp32 masters stay fp32); floating batches are cast to it, as DetectMultiBackend(fp16=True).forward does."""
     from .general import non_max_suppression
 
     cur = torch.cuda.current_stream()
@@ -67,8 +96,12 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
         cur.wait_stream(side)
         return dets
 
+    scope = _infer_dtype(model, half, dtype)
     for x in batches:
-        out = model(x)
+        with scope as dt:   # (per forward: a generator must not leave the model changed between its yields)
+            if dt is not None and x.is_floating_point() and x.dtype != dt:
+                x = x.to(dt)
+            out = model(x)
         pred = out[0] if isinstance(out, (list, tuple)) else out
         ev = torch.cuda.Event()
         ev.record(cur)
@@ -79,12 +112,13 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
         yield finish(pending)
 
 
-def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False):
+def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False, half=False, dtype=None):
     """The validation loop of reference val.py:351-428 over ``(im, targets, shapes)`` triples in the reference dataloader's format: im (bs, 3, h, w)
     (uint8 is scaled by 1 / 255 like val.py:358-359), targets (nl, 6) [image, class, x, y, w, h] normalised and grouped by image, shapes[i] =
     ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))).  The post-processing of batch i (NMS, scale_boxes, labels to native space, process_batch, the
     statistics and optionally the confusion matrix) runs on a second HIP stream while the forward of batch i + 1 fills the CUs, as in `detect_batches`;
-    its only device->host copy is the NMS counts.  Returns ((mp, mr, map50, map), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
+    its only device->host copy is the NMS counts.  `half` (`dtype`): validate in float16 (that dtype) from the parameters as they are -- the reference's
+    ``validate.run(model=ema.ema, half=amp)`` (train.py:445) without casting the averaged fp32 weights to half and back.  Returns ((mp, mr, map50, map), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
     from . import ops
     from .general import _gain_pad, non_max_suppression_batched
     from .metrics import ConfusionMatrix, ValStats
@@ -95,7 +129,8 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     iouv = torch.linspace(0.5, 0.95, 10, device=dev)
     stats = ValStats(nc, iouv, dev)
     cm = ConfusionMatrix(nc) if confusion else None
-    dtype = next(model.parameters()).dtype
+    scope = _infer_dtype(model, half, dtype)
+    dtype = scope.dtype or getattr(model, "infer_dtype", None) or next(model.parameters()).dtype
     pending = None
 
     def finish(p):
@@ -126,7 +161,8 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
         elif im.dtype != dtype:
             im = im.to(dtype)
         targets = targets.to(dev, torch.float32, non_blocking=True).contiguous()
-        out = model(im)
+        with scope:
+            out = model(im)
         pred = out[0] if isinstance(out, (list, tuple)) else out
         ev = torch.cuda.Event()
         ev.record(cur)

@@ -130,6 +130,12 @@ def fuse_conv_and_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d) -> nn.Conv2d:
 class BaseModel(nn.Module):
     """reference models/yolo.py:126-187."""
 
+    # dtype of the inference plans; None: the parameters' own.  torch.float16 / bfloat16 on a model with fp32 parameters runs half-precision inference straight from
+    # the masters (they are rounded once, when the filter banks are packed) -- what the reference does by `model.half()` ... `model.float()` around validation
+    infer_dtype = None
+    # bumped by whoever writes the parameters behind torch's back (ModelEMA): the engine re-packs the banks of this model when it moves
+    weights_epoch = 0
+
     @property
     def _plans(self):
         """compiled execution plans of this model: a view of the engine's cache, which lives OUTSIDE the module so that
