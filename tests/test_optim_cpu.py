@@ -33,7 +33,7 @@ def test_new_symbols_are_declared_bound_and_exported_at_abi_5(lib):
     header = (ROOT / "include" / "yolov3_hip.h").read_text()
     declared = set(re.findall(r"\b(y3_[a-z0-9_]+)\s*\(", header))
     assert set(NEW_SYMBOLS) <= declared and set(NEW_SYMBOLS) <= set(_lib.exported_symbols())
-    assert "#define Y3_ABI_VERSION 5" in re.sub(r"[ \t]+", " ", header) and lib.y3_abi_version() == 5 == _lib.ABI_VERSION
+    assert "#define Y3_ABI_VERSION 6" in re.sub(r"[ \t]+", " ", header) and lib.y3_abi_version() == 6 == _lib.ABI_VERSION
     dynamic = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True, check=True).stdout
     assert all(re.search(rf"\bT {s}\b", dynamic) for s in NEW_SYMBOLS)
     assert lib.y3_optim_tensor_record_bytes() == 96 and lib.y3_sgd_tensor_record_bytes() == 56

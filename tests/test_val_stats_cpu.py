@@ -44,7 +44,7 @@ def test_new_symbols_are_declared_bound_and_exported_at_abi_5(lib):
     header = (ROOT / "include" / "yolov3_hip.h").read_text()
     declared = set(re.findall(r"\b(y3_[a-z0-9_]+)\s*\(", header))
     assert set(NEW_SYMBOLS) <= declared and set(NEW_SYMBOLS) <= set(_lib.exported_symbols())
-    assert "#define Y3_ABI_VERSION 5" in re.sub(r"[ \t]+", " ", header) and lib.y3_abi_version() == 5 == _lib.ABI_VERSION
+    assert "#define Y3_ABI_VERSION 6" in re.sub(r"[ \t]+", " ", header) and lib.y3_abi_version() == 6 == _lib.ABI_VERSION
     assert ("val_stats.hip", ["-ffp-contract=off"]) in __import__("yolov3_amd.build", fromlist=["SOURCES"]).SOURCES
 
 

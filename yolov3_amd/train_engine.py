@@ -146,7 +146,6 @@ class ConvUnit(_Unit):
         self.bn_in: ConvUnit | None = None
         self.act_in_consumer = False
         self.bnin_rows = -1
-        self.stem_filt = None   # layer 0 by recomputation (stem_recompute): the stem-packed bank of this step's forward, kept for the backward
 
     def sync_group(self):
         """the process group of a torch.nn.SyncBatchNorm layer (reference train.py:270-272: --sync-bn converts every BatchNorm2d before DDP wraps the
@@ -186,14 +185,6 @@ class ConvUnit(_Unit):
         return (self.use_stem and self.plan.x_nchw is not None and not self.need_dx and self.res is None and self.cout == 32 and self.ci_real <= 3
                 and os.environ.get("Y3_STEM_BWD", "1") != "0" and not self.sync_group())   # (SyncBatchNorm: the two-phase backward below)
 
-    def stem_recompute(self) -> bool:
-        """layer 0 without its pre-BatchNorm tensor (round 6, Y3_STEM_RECOMPUTE=1; default off): statistics-only pass, one pass that writes act(bn(u)), and a backward that
-        rebuilds u from the image -- the 1.68 GB tensor (batch 64) is neither written nor read back three times, and the step needs that much less memory.  Same bits in the
-        forward (tests), but NOT faster: the four passes are bound by their patch staging / elementwise VALU work, not by HBM -- 1.18 + 1.08 + 0.98 ms against 0.74 + 0.66 +
-        0.69 + 0.98 ms of the stored path, whole step 55.87 -> 56.11 ms on one box (profiles/r06_stem_recompute_ab.txt).  Kept as a switch for memory-bound configurations."""
-        return (self.fused_stem_bwd() and self.plan.epilogue_stats and not self.act_in_consumer and self.plan.dtype in (torch.float16, torch.bfloat16)
-                and os.environ.get("Y3_STEM_RECOMPUTE", "0") == "1")
-
     def fwd(self):
         if self.cout != self.co_real:
             raise NotImplementedError("BatchNorm over a channel-padded conv")
@@ -211,9 +202,7 @@ class ConvUnit(_Unit):
                 xi = self.plan.x_nchw
                 rows = ops.stem_conv_stats_rows(xi.shape[0], xi.shape[2], xi.shape[3])
                 buf = self.plan.stat_buffer(rows * 2 * self.cout)
-                recompute = self.stem_recompute()
-                self.stem_filt = filt if recompute else None   # the backward multiplies with the same bank
-                stat = buf, (ops.stem_conv_stats_only(xi, filt, self.u, buf, rows) if recompute else ops.stem_conv_stats(xi, filt, self.zero_bias, self.u, buf, rows))
+                stat = buf, ops.stem_conv_stats(xi, filt, self.zero_bias, self.u, buf, rows)
             else:
                 ops.stem_conv(self.plan.x_nchw, filt, self.zero_bias, self.u, act=False)
         else:
@@ -251,9 +240,6 @@ class ConvUnit(_Unit):
     def _normalise(self):
         if self.act_in_consumer:
             return   # y = act(scale u + shift) (+ shortcut) is computed and stored by the 1x1 consumer's launch (the next unit)
-        if self.stem_filt is not None:
-            ops.stem_conv_bn(self.plan.x_nchw, self.stem_filt, self.scale, self.shift, self.act, self.y.view)   # u recomputed from the image, never stored
-            return
         ops.bn_act_fwd(self.u, self.vecs, self.act, self.y.view, self.res.view if self.res is not None else None)
 
     def bwd(self, grads):
@@ -270,10 +256,7 @@ class ConvUnit(_Unit):
             if xi._version != self.plan.x_version:
                 raise RuntimeError("the input batch was modified in place between the forward and the backward of this training step")
             dw = self.plan.grad_alloc(tuple(m.conv.weight.shape)) if self.wgrad_on else self.plan.discard(tuple(m.conv.weight.shape))
-            if self.stem_filt is not None:
-                ops.stem_bn_bwd_wgrad_recompute(xi, self.stem_filt, gy, self.scale, self.shift, self.mean, self.invstd, self.act, self.sums, dgamma, dbeta, dw, self.plan.stem_bwd_ws())
-            else:
-                ops.stem_bn_bwd_wgrad(xi, self.u, gy, self.scale, self.shift, self.mean, self.invstd, self.act, self.sums, dgamma, dbeta, dw, self.plan.stem_bwd_ws())
+            ops.stem_bn_bwd_wgrad(xi, self.u, gy, self.scale, self.shift, self.mean, self.invstd, self.act, self.sums, dgamma, dbeta, dw, self.plan.stem_bwd_ws())
             if self.dgamma_on:
                 grads[m.bn.weight] = dgamma   # handed over in the order the arena slices were taken: a bucket is then one contiguous range (parallel.GradBuckets)
             if self.dbeta_on:
