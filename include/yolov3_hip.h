@@ -481,6 +481,11 @@ int y3_rmsprop_step(const void* tensor_table, int32_t n_tensors, int32_t n_chunk
  *   { float* ema; const float* src; int64 numel; int32 first_chunk; int32 pad; }   (chunks of 16384 elements; n_chunks = their total)
  * 4-byte alignment is enough; tensors whose two pointers are 16-byte aligned are streamed 16 bytes at a time.  0 <= d <= 1. */
 int y3_ema_update(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, float d, void* stream);
+/* The same lerp after a fused optimizer step, with ModelEMA's update count and decay kept on the DEVICE (added within ABI 6: nothing else changed).  `ema_state`:
+ * 24 DEVICE bytes { int32 updates; float d; double decay; double tau; }.  Unless *found_inf is set (NULL: never), updates += 1 and d = decay * (1 - exp(-updates / tau)),
+ * computed in double and rounded once, then every record is lerped with that d.  With *found_inf set -- the step before it was skipped -- nothing is written: the
+ * averages stay bit for bit and the count does not advance, so the next update uses the decay of the updates really made.  No host synchronisation. */
+int y3_ema_update_counted(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, void* ema_state, const int32_t* found_inf, void* stream);
 /* The owner's step of the two-phase gradient exchange that replaces a bucket's all-reduce on a fully connected xGMI mesh (reference: DDP's gradient
    averaging, utils/torch_utils.py:60-72 smart_DDP / train.py:411): `parts` holds n_parts contributions of n floats each ([n_parts][n], what the all-to-all
    of the shards delivered); out[i] = (parts[0][i] + ... + parts[n_parts - 1][i]) * scale, added in that order.  `out` may alias none of `parts`. */

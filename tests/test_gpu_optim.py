@@ -127,21 +127,22 @@ _TORCH: dict = {}
 
 def torch_run(kind, inf_at=None, dtype=torch.float32):
     """the reference sequence on the CPU (clip_grad_norm_, torch.optim step, the EMA lerp); a step with an inf gradient is one torch's GradScaler would not make:
-    no step(), no lerp -- but ModelEMA's update count still advances, as it does in the fused path.  Computed once per case and shared."""
+    no step(), no lerp, and ModelEMA's update count does not advance either (the fused path keeps it on the device).  Computed once per case and shared."""
     key = (kind, inf_at, dtype)
     if key in _TORCH:
         return _TORCH[key]
     ref = [torch.nn.Parameter(v.to(dtype)) for v in initial_values()]
     opt = make_torch(kind, ref)
     ema = [p.detach().clone() for p in ref]
-    snaps = []
+    snaps, updates = [], 0
     for step in range(STEPS):
         opt.param_groups[1]["lr"] = lr_of_group1(step)
         for r, g in zip(ref, gradients(step, inf_at)):
             r.grad = g.to(dtype)
-        d = 0.9999 * (1 - math.exp(-(step + 1) / 2000))
         norm = None
         if step != inf_at:
+            updates += 1
+            d = 0.9999 * (1 - math.exp(-updates / 2000))
             norm = float(torch.nn.utils.clip_grad_norm_(ref, max_norm=MAX_NORM))
             opt.step()
             for e, r in zip(ema, ref):
@@ -168,6 +169,7 @@ def fused_run(kind, dev, arena, inf_at=None):
         assert int(opt.found_inf.item()) == int(step == inf_at)
         snaps.append(snapshot(kind, ps, lambda p: opt.state[p], [ema.shadow[p] for p in ps], float(opt.last_norm.item())))
         counters.append(int(opt._step_dev.item()))
+    assert ema.updates == STEPS - (inf_at is not None)   # a skipped step is no update of the average
     return snaps, counters
 
 

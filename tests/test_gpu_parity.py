@@ -2256,6 +2256,69 @@ parallel.finalize()
     assert out.returncode == 0 and out.stdout.count("ok") == 2, out.stdout + out.stderr
 
 
+@pytest.mark.parametrize("backend", ["nccl", "gloo"])
+def test_gradient_exchange_two_ranks_accumulated(tmp_path, backend):
+    """gradient accumulation under the exchange (reference train.py:411: several backward() calls per optimizer step, every one of them exchanged): per rank two
+    micro-batches A and B; the averaged gradients of each alone, then A and B without zero_grad in between, with grad_sync on.  The second backward's exchange runs
+    on a fresh arena while .grad holds views of the first one's, so the accumulated gradients are the fp32 sum of the two averaged ones bit for bit, with either form
+    of the bucket collective, and the second backward issued as many collectives as the first.  One launch of two processes covers both forms."""
+    import subprocess
+    import sys
+
+    if backend == "nccl" and torch.cuda.device_count() < 2:
+        pytest.skip("needs 2 GPUs (the 1-GPU test box runs the gloo form)")
+
+    script = tmp_path / "two_rank_accumulated.py"
+    script.write_text(f"""
+import sys, torch, yaml
+sys.path.insert(0, {str(ROOT)!r})
+from yolov3_amd import ComputeLoss, DetectionModel, parallel
+from oracle import yolo_oracle as yo
+rank, local_rank, world = parallel.init({backend!r})
+dev = parallel.local_device(local_rank)
+torch.cuda.set_device(dev)
+torch.manual_seed(0)
+m = DetectionModel("yolov3-tiny.yaml", nc=80).to(dev).train()
+m.hyp = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=4.0, fl_gamma=0.0, label_smoothing=0.0)
+parallel.broadcast_parameters(m)
+crit = ComputeLoss(m)
+xs = [torch.rand(4, 3, 128, 128, generator=torch.Generator().manual_seed(10 + rank + 2 * j)).to(dev) for j in range(2)]
+tgs = [yo.synth_targets(4, 80, seed=20 + rank + 2 * j).to(dev) for j in range(2)]
+def backward(j):
+    with torch.autocast("cuda", dtype=torch.float16):   # the deterministic path (no atomics), as in the two-rank test above
+        loss = crit(m(xs[j]), tgs[j])[0]
+    (loss * 64.0).backward()
+    torch.cuda.synchronize()
+def flat():
+    return torch.cat([p.grad.flatten() for p in m.parameters()]).clone()
+for exchange in ("all_reduce", "direct"):
+    gb = m.grad_sync = parallel.GradBuckets(bucket_bytes=8 << 20, exchange=exchange)
+    alone = []
+    for j in range(2):
+        m.zero_grad(set_to_none=True)
+        backward(j)
+        alone.append(flat())
+    per_backward = gb.collectives[exchange] // 2
+    assert per_backward >= 2 and gb.collectives[exchange] == 2 * per_backward and sum(gb.collectives.values()) == gb.collectives[exchange], gb.collectives
+    m.zero_grad(set_to_none=True)
+    backward(0)
+    assert gb.collectives[exchange] == 3 * per_backward, gb.collectives
+    backward(1)
+    assert gb.collectives[exchange] == 4 * per_backward, gb.collectives   # the second backward was exchanged too: the counter doubled
+    acc = flat()
+    assert not torch.equal(alone[0], alone[1]) and float(alone[1].abs().max()) > 0
+    assert torch.equal(acc, alone[0] + alone[1]), (exchange, float((acc - (alone[0] + alone[1])).abs().max()), float(acc.abs().max()))
+    check = acc.clone()   # (and the ranks hold the same accumulated gradients)
+    torch.distributed.all_reduce(check)
+    assert torch.equal(check, acc * world), exchange
+    print("rank", rank, exchange, "ok")
+parallel.finalize()
+""")
+    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29539", str(script)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.count("ok") == 4, out.stdout + out.stderr
+
+
 def test_multi_scale_training_reuses_one_arena(dev):
     """The reference's --multi-scale training (train.py:394-399) draws a new size from [0.5, 1.5] x imgsz in steps of the grid size for EVERY batch: 21 sizes at
     imgsz 640.  All of them stay compiled (PlanCache.MAX_TRAIN_SHAPES >= 24) as views into ONE activation arena per slot: after the first pass over the sizes no plan

@@ -177,3 +177,99 @@ def test_step_on_cpu_parameters_raises(cls):
     with pytest.raises(RuntimeError, match="no CPU / PyTorch fallback"):
         getattr(optim, cls)([p]).step()
     assert torch.equal(p.detach(), torch.zeros(4))
+
+
+# ------------------------------------------------------------------------------------------------ FusedSGD: momentum and nesterov live in the groups
+def test_sgd_and_rmsprop_groups_carry_momentum_adam_groups_do_not(model):
+    """the reference's warmup (train.py:383-391) writes ``x["momentum"]`` only ``if "momentum" in x``: true for SGD and RMSProp, false for Adam / AdamW, as with torch"""
+    from yolov3_amd import FusedSGD, smart_optimizer, smart_param_groups
+
+    for m in (0.85, 0.937):
+        opt = smart_optimizer(model, "SGD", lr=0.01, momentum=m, decay=5e-4)
+        assert len(opt.param_groups) == 3 and all(g["momentum"] == m and g["nesterov"] is True for g in opt.param_groups)
+        assert opt.momentum == m and opt.nesterov is True
+        plain = FusedSGD(smart_param_groups(model, 0.01, 5e-4), momentum=m, nesterov=False)
+        assert all(g["momentum"] == m and g["nesterov"] is False for g in plain.param_groups) and plain.nesterov is False
+    flat = FusedSGD([torch.nn.Parameter(torch.zeros(3))], momentum=0.6)   # a bare parameter list: one group
+    assert [(g["momentum"], g["nesterov"]) for g in flat.param_groups] == [(0.6, True)]
+    own = FusedSGD([{"params": [torch.nn.Parameter(torch.zeros(3))], "momentum": 0.5}], momentum=0.9)   # a group's own key wins, as in torch
+    assert own.param_groups[0]["momentum"] == 0.5 and own.momentum == 0.5
+    assert all("momentum" in g for g in smart_optimizer(model, "RMSProp", momentum=0.85).param_groups)
+    for name in ("Adam", "AdamW"):
+        theirs = TORCH[name]([torch.nn.Parameter(torch.zeros(3))])
+        assert all("momentum" not in g and "betas" in g for g in smart_optimizer(model, name, momentum=0.85).param_groups) and "momentum" not in theirs.param_groups[0]
+    assert "momentum" in torch.optim.SGD([torch.nn.Parameter(torch.zeros(3))], lr=0.1).param_groups[0]
+
+
+def test_sgd_state_dict_follows_the_groups_momentum():
+    """what a warmup wrote into the groups is what state_dict() reports (and torch.optim.SGD takes over); load_state_dict writes the loaded momentum into the groups"""
+    from yolov3_amd import FusedSGD
+
+    ps = [torch.nn.Parameter(torch.randn(5)), torch.nn.Parameter(torch.randn(2, 3))]
+    groups = lambda: [{"params": [ps[0]], "weight_decay": 0.0}, {"params": [ps[1]], "weight_decay": 5e-4}]
+    ours = FusedSGD(groups(), lr=0.01, momentum=0.937, nesterov=True)
+    for g in ours.param_groups:
+        g["momentum"] = 0.8685   # the reference's warmup, half way
+    sd = ours.state_dict()
+    assert [g["momentum"] for g in sd["param_groups"]] == [0.8685, 0.8685] and all(g["nesterov"] is True for g in sd["param_groups"]) and ours.momentum == 0.8685
+    theirs = torch.optim.SGD(groups(), lr=1.0, momentum=0.1, nesterov=True)
+    assert set(sd["param_groups"][0]) == set(theirs.state_dict()["param_groups"][0])
+    theirs.load_state_dict(sd)
+    assert [g["momentum"] for g in theirs.param_groups] == [0.8685, 0.8685]
+    ours.momentum = 0.7   # the attribute is a property over the groups
+    assert [g["momentum"] for g in ours.param_groups] == [0.7, 0.7]
+    fresh = FusedSGD(groups(), lr=0.5, momentum=0.1, nesterov=False)
+    fresh.load_state_dict(sd)
+    assert [(g["momentum"], g["nesterov"], g["lr"]) for g in fresh.param_groups] == [(0.8685, True, 0.01)] * 2 and fresh.momentum == 0.8685 and fresh.nesterov is True
+    sd["param_groups"][1]["momentum"] = 0.5
+    with pytest.raises(ValueError, match="keeps one momentum for all groups"):
+        fresh.load_state_dict(sd)
+    assert [g["momentum"] for g in fresh.param_groups] == [0.8685, 0.8685]   # a refused checkpoint changes nothing
+
+
+def test_sgd_step_with_differing_momenta_raises_before_any_launch():
+    """CPU parameters with gradients: the agreement check comes first (ValueError), not the device check (RuntimeError: no CPU fallback), and nothing moved"""
+    from yolov3_amd import FusedSGD
+
+    ps = [torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.zeros(3))]
+    for p in ps:
+        p.grad = torch.ones_like(p)
+    opt = FusedSGD([{"params": [ps[0]]}, {"params": [ps[1]]}], lr=0.1, momentum=0.9)
+    opt.param_groups[1]["momentum"] = 0.8
+    with pytest.raises(ValueError, match="keeps one momentum for all groups"):
+        opt.step()
+    with pytest.raises(ValueError, match="keeps one momentum for all groups"):
+        opt.momentum
+    assert all(torch.equal(p.detach(), torch.zeros_like(p)) for p in ps) and opt.state == {} and opt._steps == 0
+    opt.param_groups[1]["momentum"] = 0.9   # in agreement again: the next refusal is the device's
+    with pytest.raises(RuntimeError, match="no CPU / PyTorch fallback"):
+        opt.step()
+
+
+def test_ema_update_counted_is_declared_bound_exported_and_rejects_bad_arguments(lib):
+    """the update behind a fused step (ModelEMA.after_step): count and decay on the device, nothing written after a skipped step"""
+    from yolov3_amd import _lib
+
+    header = (ROOT / "include" / "yolov3_hip.h").read_text()
+    assert re.search(r"\by3_ema_update_counted\s*\(", header) and "y3_ema_update_counted" in _lib.exported_symbols()
+    P = 1 << 20   # a fake, aligned device address: validation never dereferences it
+
+    def fails(status, needle):
+        msg = lib.y3_last_error()
+        assert status != 0 and msg.startswith(b"y3_ema_update_counted") and needle in msg, (status, msg)
+
+    fails(lib.y3_ema_update_counted(None, 3, 5, P, P, None), b"null tensor table")
+    fails(lib.y3_ema_update_counted(P, 0, 5, P, P, None), b"positive")
+    fails(lib.y3_ema_update_counted(P, 3, -1, P, None, None), b"positive")
+    fails(lib.y3_ema_update_counted(P, 3, 5, None, P, None), b"null ema state")
+
+
+def test_model_ema_updates_is_a_host_count_until_a_fused_step(model):
+    from yolov3_amd import ModelEMA
+
+    ema = ModelEMA(model, decay=0.99, tau=100, updates=7)
+    assert ema.updates == 7 and ema._state is None
+    d = ema.next_decay()
+    assert ema.updates == 8 and d == pytest.approx(0.99 * (1 - torch.exp(torch.tensor(-8 / 100.0)).item()))
+    ema.updates = 41
+    assert ema.updates == 41 and ema._state is None

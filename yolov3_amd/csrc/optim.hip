@@ -252,7 +252,29 @@ struct EmaTensor {
 };
 static_assert(sizeof(EmaTensor) == 32, "the host mirror (yolov3_amd/optim.py) packs 32-byte records");
 
-__global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor* __restrict__ t, int n, float d) {
+// ModelEMA's counter and decay ON THE DEVICE (y3_ema_update_counted): a fused optimizer step learns only on the device whether it was skipped (found_inf), and the
+// reference's d = decay * (1 - exp(-updates / tau)) depends on how many updates were really made.  The host mirror (yolov3_amd/optim.py) packs these 24 bytes.
+struct EmaState {
+    int updates;
+    float d;                  // the decay of update number `updates`
+    double decay, tau;
+};
+static_assert(sizeof(EmaState) == 24, "the host mirror (yolov3_amd/optim.py) packs 24 bytes");
+
+// updates += 1 and the decay that goes with it (in double, rounded once to fp32: what the host computes for y3_ema_update) -- unless the step was skipped
+__global__ void ema_advance_kernel(EmaState* __restrict__ s, const int* __restrict__ found_inf) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (found_inf && *found_inf) return;
+    const int n = s->updates + 1;
+    s->updates = n;
+    s->d = (float)(s->decay * (1.0 - exp(-(double)n / s->tau)));
+}
+
+// `state` given: the decay is state->d; `found_inf` given and set: nothing is written (a skipped step leaves the averages bit for bit)
+__global__ __launch_bounds__(256) void ema_update_kernel(const EmaTensor* __restrict__ t, int n, float d, const EmaState* __restrict__ state,
+                                                           const int* __restrict__ found_inf) {
+    if (found_inf && *found_inf) return;
+    if (state) d = state->d;
     const int ti = find_tensor(t, n, blockIdx.x);
     const EmaTensor T = t[ti];
     const long long base = (long long)(blockIdx.x - T.first_chunk) * CHUNK;
@@ -363,7 +385,21 @@ extern "C" int y3_ema_update(const void* tensor_table, int32_t n_tensors, int32_
     if (!tensor_table) Y3_FAIL("y3_ema_update: null tensor table");
     if (n_tensors <= 0 || n_chunks <= 0) Y3_FAIL("y3_ema_update: n_tensors %d and n_chunks %d must be positive", (int)n_tensors, (int)n_chunks);
     if (!(d >= 0.0f && d <= 1.0f)) Y3_FAIL("y3_ema_update: decay %g is outside [0, 1]", (double)d);
-    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const EmaTensor*)tensor_table, n_tensors, d);
+    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, (const EmaTensor*)tensor_table, n_tensors, d, (const EmaState*)nullptr,
+                       (const int*)nullptr);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_ema_update_counted(const void* tensor_table, int32_t n_tensors, int32_t n_chunks, void* ema_state, const int32_t* found_inf, void* stream) {
+    if (!tensor_table) Y3_FAIL("y3_ema_update_counted: null tensor table");
+    if (n_tensors <= 0 || n_chunks <= 0) Y3_FAIL("y3_ema_update_counted: n_tensors %d and n_chunks %d must be positive", (int)n_tensors, (int)n_chunks);
+    if (!ema_state) Y3_FAIL("y3_ema_update_counted: null ema state");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ema_advance_kernel, dim3(1), dim3(64), 0, st, (EmaState*)ema_state, (const int*)found_inf);
+    Y3_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, (const EmaTensor*)tensor_table, n_tensors, 0.0f, (const EmaState*)ema_state,
+                       (const int*)found_inf);
     Y3_CHECK_LAUNCH();
     return 0;
 }

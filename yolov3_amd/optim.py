@@ -65,9 +65,10 @@ class ModelEMA:
     ema = d * ema + (1 - d) * model, over every floating entry of the state dict.
 
     ``ema`` is the averaged MODEL, as upstream: a deep copy of the (de-parallelised) model in eval mode whose parameters do not require a gradient -- validate it
-    (``run_batches(ema.ema, ..., half=True)``), save it (``compat.save_checkpoint``).  Its parameters and float buffers are the very tensors the fused optimizer steps
-    lerp into (``step(ema=ema)``; what a step does not touch -- buffers, frozen parameters -- follows in one y3_ema_update launch), and ``update(model)`` is the
-    reference's standalone call: one launch for everything.  ``shadow`` / ``buffers`` map the TRAINING model's parameters / float buffers to their averages.
+    (``run_batches(ema.ema, ..., half=True)``), save it (``compat.save_checkpoint``).  Its parameters and float buffers are the very tensors the kernels lerp into: ``step(ema=ema)`` of a
+    fused optimizer is followed by one y3_ema_update_counted launch over all of them, which makes no update when the step was skipped for an inf / nan gradient
+    (``after_step``: the update count and the decay live on the device, nothing is read back), and ``update(model)`` is the reference's standalone call: one
+    y3_ema_update launch for everything.  ``shadow`` / ``buffers`` map the TRAINING model's parameters / float buffers to their averages.
 
     The kernels write the averages through raw pointers, which torch's version counters do not see: every update bumps ``ema.weights_epoch`` instead, and the engine
     refills the filter banks of ``ema``'s inference plans when that moved (no plan is rebuilt, nothing is launched here)."""
@@ -82,8 +83,30 @@ class ModelEMA:
         for p in self.ema.parameters():
             p.requires_grad_(False)
             p.grad = None
-        self.decay, self.tau, self.updates = decay, tau, updates
+        self.decay, self.tau = decay, tau
+        self._updates, self._state = int(updates), None
         self.rebind(model)
+
+    @property
+    def updates(self) -> int:
+        """the number of updates made.  After a fused step with ``ema=`` the count lives on the device (a skipped step must not advance it, and only the device knows):
+        reading it then synchronises, like GradScaler.get_scale -- for checkpoints and logging."""
+        if self._state is not None:
+            self._updates = int(self._state[0][:4].view(torch.int32).item())
+        return self._updates
+
+    @updates.setter
+    def updates(self, value):
+        self._updates, self._state = int(value), None   # (the device copy is made again from this value by the next fused step)
+
+    def _device_state(self, device):
+        """{int32 updates; float d; double decay; double tau} on `device` (csrc/optim.hip::EmaState), made from the host's values when there is none"""
+        key = (device, float(self.decay), float(self.tau))
+        if self._state is None or self._state[1] != key:
+            n = self.updates
+            host = torch.frombuffer(bytearray(struct.pack("<ifdd", n, 0.0, key[1], key[2])), dtype=torch.uint8)
+            self._updates, self._state = n, (host.to(device), key)
+        return self._state[0]
 
     def rebind(self, model: nn.Module):
         """(re)build the maps from `model`'s tensors to the averages (after the parameters of either were replaced: ``.to()``, ``.float()``)"""
@@ -95,17 +118,23 @@ class ModelEMA:
         self._tables = {}
 
     def next_decay(self) -> float:
+        """the host's count: ``update(model)`` (no step that could be skipped goes with it)"""
         self.updates += 1
-        return self.decay * (1 - math.exp(-self.updates / self.tau))
+        return self.decay * (1 - math.exp(-self._updates / self.tau))
 
     def touched(self):
         """the averages were written behind torch's back: make the plan cache of `ema` see a new version (host only)"""
         self.ema.weights_epoch = int(getattr(self.ema, "weights_epoch", 0)) + 1
 
     def _lerp(self, kind: str, pairs, d: float):
-        """ema = d * ema + (1 - d) * src over (src, ema) pairs in one y3_ema_update launch; the device table of `kind` is rebuilt only when a tensor moved"""
+        """ema = d * ema + (1 - d) * src over (src, ema) pairs in one y3_ema_update launch"""
         if not pairs:
             return
+        ent = self._table(kind, pairs)
+        _lib.check(_lib.lib().y3_ema_update(ent[0].data_ptr(), ent[2], ent[3], float(d), ops.stream_ptr()), "y3_ema_update")
+
+    def _table(self, kind: str, pairs):
+        """the device table of (src, ema) records of `kind`; rebuilt only when a tensor moved"""
         ptrs = [t.data_ptr() for pr in pairs for t in pr]
         ent = self._tables.get(kind)
         if ent is None or ent[1] != ptrs:
@@ -120,7 +149,7 @@ class ModelEMA:
                 n_chunks += (src.numel() + CHUNK - 1) // CHUNK
             host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
             ent = self._tables[kind] = (host.to(pairs[0][1].device), ptrs, len(rows), n_chunks)
-        _lib.check(_lib.lib().y3_ema_update(ent[0].data_ptr(), ent[2], ent[3], float(d), ops.stream_ptr()), "y3_ema_update")
+        return ent
 
     @torch.no_grad()
     def update(self, model: nn.Module):
@@ -141,10 +170,17 @@ class ModelEMA:
         averages still move toward the (unchanged) value -- it matters when the average was loaded from a checkpoint and differs from the weights"""
         self._lerp("rest", [(p.detach(), e) for p, e in self.shadow.items() if id(p) not in stepped], d)
 
-    def after_step(self, d: float, stepped: set):
-        """what a fused step with ``ema=`` leaves over -- the float buffers and the parameters it did not touch -- in one launch, and the version bump"""
-        pairs = [(p.detach(), e) for p, e in self.shadow.items() if id(p) not in stepped] if len(stepped) < len(self.shadow) else []
-        self._lerp("after_step", pairs + [(b, e) for b, e in self.buffers.items()], d)
+    def after_step(self, found_inf: torch.Tensor):
+        """the update that goes with a fused step (``step(ema=ema)``): every parameter -- stepped or frozen -- and every float buffer, in one y3_ema_update_counted
+        launch behind the step's kernels.  `found_inf` is the step's DEVICE flag: a step that was skipped for an inf / nan gradient makes NO update -- the averages
+        stay bit for bit, buffers included, and the count does not advance, so the next update's decay is that of the updates really made (what a loop gets that
+        calls ``ema.update(model)`` only after a step that happened).  Nothing is read back."""
+        pairs = [(p.detach(), e) for p, e in self.shadow.items()] + [(b, e) for b, e in self.buffers.items()]
+        if not pairs:
+            return
+        ent = self._table("after_step", pairs)
+        state = self._device_state(pairs[0][1].device)
+        _lib.check(_lib.lib().y3_ema_update_counted(ent[0].data_ptr(), ent[2], ent[3], state.data_ptr(), found_inf.data_ptr(), ops.stream_ptr()), "y3_ema_update_counted")
         self.touched()
 
     def update_attr(self, model: nn.Module, include=(), exclude=("process_group", "reducer")):
@@ -156,6 +192,10 @@ class ModelEMA:
 
 
 class FusedSGD:
+    """torch.optim.SGD(momentum, nesterov) as one fused step.  Every group carries torch's keys ``lr``, ``weight_decay``, ``momentum`` and ``nesterov`` and the step
+    reads them there, so a loop that rewrites them between steps -- the reference's warmup, train.py:383-391: ``x["lr"] = ...; if "momentum" in x: x["momentum"] =
+    ...`` -- takes effect.  The kernel takes one momentum (and one nesterov flag) per launch: the groups must agree at step time, as they do under that loop."""
+
     def __init__(self, params, lr=0.01, momentum=0.937, nesterov=True, weight_decay=0.0):
         groups = list(params)
         if groups and not isinstance(groups[0], dict):
@@ -165,13 +205,40 @@ class FusedSGD:
             g = dict(g)
             g.setdefault("lr", lr)
             g.setdefault("weight_decay", weight_decay)
+            g.setdefault("momentum", momentum)
+            g.setdefault("nesterov", nesterov)
             g["params"] = [p for p in g["params"] if p.requires_grad]
             self.param_groups.append(g)
-        self.momentum, self.nesterov = momentum, nesterov
+        self._defaults = (momentum, nesterov)   # what the properties below answer for an optimizer without groups
         self.state: dict = {}
         self._steps = 0
         self._dev_bufs = None
         self.last_norm = None
+
+    def _agreed(self, key, default):
+        """the one value of `key` over the groups (the kernel takes one per launch)"""
+        vals = {type(default)(g[key]) for g in self.param_groups}
+        if len(vals) > 1:
+            raise ValueError(f"FusedSGD keeps one {key} for all groups, the groups have {sorted(vals)}")
+        return vals.pop() if vals else default
+
+    @property
+    def momentum(self):
+        return self._agreed("momentum", float(self._defaults[0]))
+
+    @momentum.setter
+    def momentum(self, value):
+        for g in self.param_groups:
+            g["momentum"] = value
+
+    @property
+    def nesterov(self):
+        return self._agreed("nesterov", bool(self._defaults[1]))
+
+    @nesterov.setter
+    def nesterov(self, value):
+        for g in self.param_groups:
+            g["nesterov"] = value
 
     def zero_grad(self, set_to_none=True):
         for g in self.param_groups:
@@ -182,8 +249,10 @@ class FusedSGD:
     def step(self, grad_scale=1.0, max_norm: float = 0.0, ema: ModelEMA | None = None):
         """One fused update.  grad_scale: the loss scale the gradients still carry -- a Python float, or a 1-element DEVICE fp32
         tensor (GradScaler below: dynamic scale, read by the kernels); max_norm: clip_grad_norm_ threshold (0 = off; the
-        reference uses 10.0); ema: ModelEMA to update in the same pass."""
-        recs, n_chunks, stepped = [], 0, set()
+        reference uses 10.0); ema: ModelEMA to update in the same pass.  lr, weight_decay, momentum and nesterov are read from the groups
+        now; groups whose momenta (or nesterov flags) differ raise ValueError before anything is launched."""
+        momentum, nesterov = self.momentum, self.nesterov
+        recs, n_chunks = [], 0
         dev = None
         for g in self.param_groups:
             for p in g["params"]:
@@ -197,10 +266,8 @@ class FusedSGD:
                 if buf is None:
                     buf = self.state[p] = torch.zeros_like(p)
                 grad = p.grad.contiguous()
-                e = ema.shadow[p] if ema is not None else None
-                recs.append((p.data_ptr(), grad.data_ptr(), buf.data_ptr(), e.data_ptr() if e is not None else 0, p.numel(), float(g["lr"]), float(g["weight_decay"]), n_chunks, grad))
+                recs.append((p.data_ptr(), grad.data_ptr(), buf.data_ptr(), 0, p.numel(), float(g["lr"]), float(g["weight_decay"]), n_chunks, grad))
                 n_chunks += (p.numel() + CHUNK - 1) // CHUNK
-                stepped.add(id(p))
         if not recs:
             return
         L = _lib.lib()
@@ -212,29 +279,29 @@ class FusedSGD:
                               torch.zeros(1, dtype=torch.int32, device=dev))
         tab, scratch, found = self._dev_bufs
         tab[: host.numel()].copy_(host, non_blocking=True)
-        d = ema.next_decay() if ema is not None else 0.0
+        d = 0.0   # (the kernels' own ema pass is not used: the average follows in ModelEMA.after_step, which knows on the device whether the step was made)
         if isinstance(grad_scale, torch.Tensor):
             if grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != dev:
                 raise TypeError("a dynamic loss scale must be a 1-element fp32 tensor on the parameters' device")
             _lib.check(
-                L.y3_sgd_step_dynamic(tab.data_ptr(), len(recs), n_chunks, grad_scale.data_ptr(), float(max_norm), float(self.momentum), int(self.nesterov),
+                L.y3_sgd_step_dynamic(tab.data_ptr(), len(recs), n_chunks, grad_scale.data_ptr(), float(max_norm), float(momentum), int(nesterov),
                                       int(self._steps == 0), float(d), scratch.data_ptr(), found.data_ptr(), ops.stream_ptr()),
                 "y3_sgd_step_dynamic",
             )
         else:
             _lib.check(
-                L.y3_sgd_step(tab.data_ptr(), len(recs), n_chunks, 1.0 / float(grad_scale), float(max_norm), float(self.momentum), int(self.nesterov), int(self._steps == 0),
+                L.y3_sgd_step(tab.data_ptr(), len(recs), n_chunks, 1.0 / float(grad_scale), float(max_norm), float(momentum), int(nesterov), int(self._steps == 0),
                               float(d), scratch.data_ptr(), found.data_ptr(), ops.stream_ptr()),
                 "y3_sgd_step",
             )
         if ema is not None:
-            ema.after_step(d, stepped)
+            ema.after_step(found)
         self._steps += 1
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
 
     def state_dict(self):
         """torch.optim.SGD's format: a checkpoint written here loads into torch.optim.SGD(momentum, nesterov) and the other way round"""
-        extra = {"momentum": self.momentum, "dampening": 0, "nesterov": self.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
+        extra = {"dampening": 0, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
         return _pack_state_dict(self.param_groups, extra, lambda p: {"momentum_buffer": self.state[p]} if p in self.state else None)
 
     def load_state_dict(self, sd):
@@ -244,11 +311,9 @@ class FusedSGD:
             raise ValueError(f"FusedSGD keeps one momentum for all groups, the checkpoint has {sorted(mus)}")
         if any(g.get("dampening", 0) != 0 or g.get("maximize", False) for g in saved):
             raise ValueError("FusedSGD does not support dampening / maximize")
-        if mus:
-            self.momentum = mus.pop()
-        if saved and "nesterov" in saved[0]:
-            self.nesterov = bool(saved[0]["nesterov"])
-        _load_groups(self.param_groups, saved, ("lr", "weight_decay"))
+        if len({bool(g["nesterov"]) for g in saved if "nesterov" in g}) > 1:
+            raise ValueError("FusedSGD keeps one nesterov for all groups, the checkpoint's groups differ")
+        _load_groups(self.param_groups, saved, ("lr", "weight_decay", "momentum", "nesterov"))
         self.state = {}
         for p, st in _saved_state(self.param_groups, sd):
             if st.get("momentum_buffer") is not None:
@@ -340,7 +405,7 @@ class _FusedMoment:
     @torch.no_grad()
     def step(self, grad_scale=1.0, max_norm: float = 0.0, ema: ModelEMA | None = None):
         """One fused update; the arguments are FusedSGD.step's."""
-        recs, keep, n_chunks, stepped = [], [], 0, set()
+        recs, keep, n_chunks = [], [], 0
         dev = None
         for g in self.param_groups:
             for p in g["params"]:
@@ -353,12 +418,10 @@ class _FusedMoment:
                 s1, s2, h0, h1 = self._record(g, p)
                 grad = p.grad.contiguous()
                 keep.append(grad)
-                e = ema.shadow[p] if ema is not None else None
                 recs.append(struct.pack("<QQQQQqdddddii", p.data_ptr(), grad.data_ptr(), s1.data_ptr(), s2.data_ptr() if s2 is not None else 0,
-                                        e.data_ptr() if e is not None else 0, p.numel(), float(g["lr"]), float(g["weight_decay"]), float(h0), float(h1), float(g["eps"]),
+                                        0, p.numel(), float(g["lr"]), float(g["weight_decay"]), float(h0), float(h1), float(g["eps"]),
                                         n_chunks, 0))
                 n_chunks += (p.numel() + CHUNK - 1) // CHUNK
-                stepped.add(id(p))
         if not recs:
             return
         L = _lib.lib()
@@ -371,7 +434,7 @@ class _FusedMoment:
             self._step_dev = torch.full((1,), self._step_init, dtype=torch.int32, device=dev)
         tab, scratch, found = self._dev_bufs
         tab[: host.numel()].copy_(host, non_blocking=True)
-        d = ema.next_decay() if ema is not None else 0.0
+        d = 0.0   # (as in FusedSGD.step: ModelEMA.after_step makes the average's update)
         if isinstance(grad_scale, torch.Tensor):
             if grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != dev:
                 raise TypeError("a dynamic loss scale must be a 1-element fp32 tensor on the parameters' device")
@@ -381,7 +444,7 @@ class _FusedMoment:
         self._launch(L, tab.data_ptr(), len(recs), n_chunks, inv, scale_ptr, float(max_norm), float(d), self._step_dev.data_ptr(), scratch.data_ptr(), found.data_ptr(),
                      ops.stream_ptr())
         if ema is not None:
-            ema.after_step(d, stepped)
+            ema.after_step(found)
         self.last_norm, self.found_inf = scratch[0:1], found  # device tensors; reading them is the caller's (optional) sync
 
     def _torch_group_extra(self) -> dict:
