@@ -265,6 +265,26 @@ int y3_confusion_matrix(const float* dets, int64_t img_stride, int32_t row_strid
 int y3_labels_to_native(const float* targets, int32_t nl, int32_t bs, float width, float height, const float* params, float* labels_out,
                         int32_t* offsets_out, void* stream);
 
+/* Autoanchor, device-resident (csrc/autoanchor.hip): reference utils/autoanchor.py -- check_anchors.metric, anchor_fitness, print_results, the genetic loop
+ * of kmean_anchors and the scipy.cluster.vq.kmeans call ahead of it.  Nothing here allocates or synchronises.  wh / pts are DEVICE (N, 2) fp32; k, f, v, codes,
+ * dist and totals are DEVICE fp64 (8-byte aligned).  Limits: 1 <= n <= 64, 1 <= N < 2^31, R <= 64.  The per-point ratio metric x_j = min(min(r0, 1 / r0),
+ * min(r1, 1 / r1)), r = wh / float(k_j), best = max_j x_j is fp32 with correctly rounded divisions; every sum is fp64 in a fixed order (bit-identical runs).
+ * thr is the already inverted threshold 1 / anchor_t, compared in fp32 as torch compares a tensor with a Python scalar.
+ * workspace_bytes: 8-byte aligned scratch of any of the three calls (R = 0: metrics / evolve alone); 0 and a message for a geometry out of range.
+ * metrics: totals[0] sum of best over best > thr, [1] #(best > thr), [2] #(x > thr) over all N n, [3] sum x, [4] sum best, [5] sum of x over x > thr.
+ * evolve: f = mean(best [best > thr]) of k, then for g in [0, gen): kg = max(k * v[g], 2.0) in fp64; if its fitness exceeds f (strict) k = kg, f = fg and
+ *   accepted[g] = 1, else 0.  One launch per generation, stream-ordered, nothing read back; v is (gen, n, 2).
+ * kmeans_step: one Lloyd iteration of R independent restarts (grid.y).  codes (R, n, 2) and live (R, n) int32 are read and rewritten: every point joins its
+ *   nearest live code (Euclidean, ties to the lowest index), dist[r] = mean distance under the OLD codes (scipy.cluster.vq.vq), the codes become the means of
+ *   their members, a live code without members goes dead for good (scipy's code_book[has_members]).  Restart r is skipped when bit r of `frozen` is set. */
+size_t y3_anchor_workspace_bytes(int64_t N, int32_t n, int32_t R);
+int y3_anchor_metrics(const float* wh, int64_t N, const double* k, int32_t n, float thr, double* totals, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int y3_anchor_evolve(const float* wh, int64_t N, double* k, double* f, int32_t n, const double* v, int32_t gen, float thr, int32_t* accepted,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int y3_kmeans_step(const float* pts, int64_t N, int32_t n, int32_t R, double* codes, int32_t* live, uint64_t frozen, double* dist, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -10,6 +10,7 @@ Public surface mirrors the reference's own Python signatures:
     ComputeLoss                          (reference utils/loss.py)
     FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update; ema.ema is the averaged model)
     smart_optimizer / FusedAdam / FusedAdamW / FusedRMSProp   (reference utils/torch_utils.py:207-237, train.py --optimizer; torch-format state dicts)
+    check_anchors / kmean_anchors / anchor_metrics / check_anchor_order   (reference utils/autoanchor.py, train.py:255: metric, k-means and genetic loop on the device)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
     save_checkpoint / smart_resume / strip_optimizer   (reference train.py:470-488, utils/torch_utils.py smart_resume, utils/general.py strip_optimizer)
     DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py)
@@ -20,6 +21,7 @@ from .general import non_max_suppression, non_max_suppression_batched, scale_box
 from .val import detect_batches, process_batch, process_batch_batched, run_batches  # noqa: F401
 from .metrics import ConfusionMatrix, ValStats, ap_per_class, ap_per_class_device, compute_ap, fitness  # noqa: F401
 from .backend import DetectMultiBackend  # noqa: F401
+from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401
 from .loss import ComputeLoss  # noqa: F401

@@ -28,6 +28,7 @@ SOURCES = [
     ("detect_nms.hip", ["-ffp-contract=off"]),
     ("val_edge.hip", ["-ffp-contract=off"]),
     ("val_stats.hip", ["-ffp-contract=off"]),
+    ("autoanchor.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("optim.hip", ["-ffp-contract=off"]),

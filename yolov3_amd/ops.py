@@ -724,3 +724,68 @@ def pack_filter_pair(w_oihw: torch.Tensor, cout: int, cin: int, dtype: torch.dty
 def shard_mean(parts: torch.Tensor, n_parts: int, n: int, scale: float, out: torch.Tensor):
     """out[i] = scale * (parts[0][i] + ... + parts[n_parts - 1][i]), fp32, summed in part order (parallel.GradBuckets: the owner's mean of its gradient shard)"""
     check(_lib.lib().y3_shard_mean(parts.data_ptr(), int(n_parts), int(n), float(scale), out.data_ptr(), stream_ptr()), "y3_shard_mean")
+
+
+_anchor_ws: dict = {}
+
+
+def _anchor_workspace(dev: torch.device, N: int, n: int, R: int) -> torch.Tensor:
+    need = int(_lib.lib().y3_anchor_workspace_bytes(int(N), int(n), int(R)))
+    if need == 0:
+        check(-1, "y3_anchor_workspace_bytes")
+    ws = _anchor_ws.get(dev.index)
+    if ws is None or ws.numel() < need:
+        ws = _anchor_ws[dev.index] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _anchor_points(wh: torch.Tensor, what: str) -> torch.Tensor:
+    require_gpu(wh, what)
+    if wh.dtype != torch.float32 or wh.dim() != 2 or wh.shape[1] != 2 or not wh.is_contiguous():
+        raise TypeError(f"{what} expects a contiguous (N, 2) fp32 table of label sizes")
+    return wh
+
+
+def anchor_metrics(wh: torch.Tensor, k: torch.Tensor, thr: float) -> torch.Tensor:
+    """the six fp64 totals of y3_anchor_metrics for the (N, 2) fp32 sizes `wh` against the (n, 2) fp64 anchors `k`, both on the device; thr = 1 / anchor_t -> DEVICE (6,)"""
+    wh = _anchor_points(wh, "anchor_metrics")
+    require_gpu(k, "anchor_metrics")
+    if k.dtype != torch.float64 or k.dim() != 2 or k.shape[1] != 2 or not k.is_contiguous():
+        raise TypeError("anchor_metrics expects contiguous (n, 2) fp64 anchors")
+    N, n = int(wh.shape[0]), int(k.shape[0])
+    ws = _anchor_workspace(wh.device, max(N, 1), n, 0)
+    totals = torch.empty(6, dtype=torch.float64, device=wh.device)
+    check(_lib.lib().y3_anchor_metrics(wh.data_ptr(), N, k.data_ptr(), n, float(thr), totals.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_anchor_metrics")
+    return totals
+
+
+def anchor_evolve(wh: torch.Tensor, k: torch.Tensor, v: torch.Tensor, thr: float):
+    """the genetic loop of kmean_anchors on the device (y3_anchor_evolve): k (n, 2) fp64 is evolved IN PLACE through the (gen, n, 2) fp64 mutations `v`
+    -> (f (1,) fp64, accepted (gen,) int32), both on the device; nothing is read back"""
+    wh = _anchor_points(wh, "anchor_evolve")
+    require_gpu(k, "anchor_evolve")
+    require_gpu(v, "anchor_evolve")
+    if k.dtype != torch.float64 or v.dtype != torch.float64 or k.dim() != 2 or k.shape[1] != 2 or v.dim() != 3 or tuple(v.shape[1:]) != tuple(k.shape) or not k.is_contiguous() or not v.is_contiguous():
+        raise TypeError("anchor_evolve expects contiguous fp64 anchors (n, 2) and mutations (gen, n, 2)")
+    N, n, gen = int(wh.shape[0]), int(k.shape[0]), int(v.shape[0])
+    ws = _anchor_workspace(wh.device, max(N, 1), n, 0)
+    f = torch.zeros(1, dtype=torch.float64, device=wh.device)
+    accepted = torch.zeros(max(gen, 1), dtype=torch.int32, device=wh.device)
+    check(_lib.lib().y3_anchor_evolve(wh.data_ptr(), N, k.data_ptr(), f.data_ptr(), n, v.data_ptr() if gen else None, gen, float(thr), accepted.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      stream_ptr()), "y3_anchor_evolve")
+    return f, accepted[:gen]
+
+
+def kmeans_step(pts: torch.Tensor, codes: torch.Tensor, live: torch.Tensor, frozen: int, dist: torch.Tensor):
+    """one Lloyd iteration of the R restarts that bit mask `frozen` leaves running (y3_kmeans_step): codes (R, n, 2) fp64 and live (R, n) int32 are updated in place,
+    dist (R,) fp64 receives the mean distance under the old codes"""
+    pts = _anchor_points(pts, "kmeans_step")
+    for t in (codes, live, dist):
+        require_gpu(t, "kmeans_step")
+    R, n = int(codes.shape[0]), int(codes.shape[1])
+    if codes.dtype != torch.float64 or dist.dtype != torch.float64 or live.dtype != torch.int32 or tuple(codes.shape) != (R, n, 2) or tuple(live.shape) != (R, n) or dist.numel() != R \
+            or not (codes.is_contiguous() and live.is_contiguous() and dist.is_contiguous()):
+        raise TypeError("kmeans_step expects contiguous codes (R, n, 2) fp64, live (R, n) int32 and dist (R,) fp64")
+    N = int(pts.shape[0])
+    ws = _anchor_workspace(pts.device, max(N, 1), n, R)
+    check(_lib.lib().y3_kmeans_step(pts.data_ptr(), N, n, R, codes.data_ptr(), live.data_ptr(), int(frozen), dist.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_kmeans_step")
