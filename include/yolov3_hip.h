@@ -445,12 +445,15 @@ int y3_conv2d_dgrad_s2(int32_t dtype, const y3_tensor* du, const void* packed4, 
 /* filter gradient (and optional bias gradient = per-channel sum of du) of the conv described by `desc`
  * (dtype, ksize, stride, cin, cout = padded sizes of x / du); dw is (cout_real, cin_real, k, k) fp32, overwritten. */
 size_t y3_conv2d_wgrad_workspace_bytes(const y3_conv_desc* desc, const y3_tensor* x);
-/* dry run: the geometry y3_conv2d_wgrad launches for (desc, x) -- tile edge (128 / 256; 0 = direct fp32 kernel), number of pixel
- * slices (split-K over n*ho*wo) and whether a slice's tiles are grouped per XCD (knob "wgrad_xcd"); tile 3 = the 3x3 strip kernel (csrc/wgrad_strip.h),
- * slices = its persistent blocks */
+/* dry run: the decision y3_conv2d_wgrad takes for (desc, x) WITH du->pitch == cout, real channel counts equal to the padded ones and no bias gradient --
+ * tile edge (128 / 256; 0 = direct fp32 kernel), number of pixel slices (split-K over n*ho*wo) and whether a slice's tiles are grouped per XCD (knob
+ * "wgrad_xcd"); tile 3 = the 3x3 strip kernel (csrc/wgrad_strip.h), slices = its persistent blocks; tile 4 = the padded-position kernel (csrc/wgrad_patch.h).
+ * A launch with a bias gradient, real subsets or a wider du may take another form: y3_conv2d_wgrad_last_plan reports the one it took */
 int y3_conv2d_wgrad_plan(const y3_conv_desc* desc, const y3_tensor* x, int32_t* tile, int64_t* slices, int32_t* xcd_grouped);
 int y3_conv2d_wgrad(const y3_conv_desc* desc, const y3_tensor* x, const y3_tensor* du, int32_t cout_real, int32_t cin_real,
                     float* dw_oihw, float* dbias /* may be NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* the decision (as y3_conv2d_wgrad_plan reports one) of the last successful y3_conv2d_wgrad of this thread; fails before the first */
+int y3_conv2d_wgrad_last_plan(int32_t* tile, int64_t* slices, int32_t* xcd_grouped);
 /* backward of nn.Upsample(x2, nearest) / nn.MaxPool2d (+ZeroPad2d) / Detect's view+permute (models/yolo.py:98) */
 int y3_upsample2x_bwd(const y3_tensor* dy, const y3_tensor* dx, int32_t dtype, int32_t accumulate, void* stream);
 int y3_maxpool2d_bwd(const y3_tensor* x, const y3_tensor* dy, const y3_tensor* dx, int32_t dtype, int32_t k, int32_t stride,

@@ -1354,6 +1354,7 @@ def test_conv_wgrad_strip_vs_autograd(dev, tune, dtype, name, shape, per):
     tile, blocks, _ = ops.conv2d_wgrad_plan(xv, cout, k, s)
     assert tile == 3 and blocks >= 1, (tile, blocks)
     dw, _ = ops.conv2d_wgrad(xv, gv, k, s, cout, cin)
+    assert ops.conv2d_wgrad_last_plan() == ops.conv2d_wgrad_plan(xv, cout, k, s), "the launch did not take the planned form"
     dw2, _ = ops.conv2d_wgrad(xv, gv, k, s, cout, cin)
     tune("wgrad_strip", 0)
     assert ops.conv2d_wgrad_plan(xv, cout, k, s)[0] == 128
@@ -1496,6 +1497,7 @@ def test_conv_wgrad_patch_vs_autograd(dev, tune, dtype, name, shape, sliced):
     tile, slices, _ = ops.conv2d_wgrad_plan(xv, cout, 3, 1)
     assert tile == 4 and slices >= 1, (tile, slices)
     dw, _ = ops.conv2d_wgrad(xv, gv, 3, 1, cout, cin)
+    assert ops.conv2d_wgrad_last_plan() == ops.conv2d_wgrad_plan(xv, cout, 3, 1), "the launch did not take the planned form"
     dw2, _ = ops.conv2d_wgrad(xv, gv, 3, 1, cout, cin)
     tune("wgrad_patch", 0)
     assert ops.conv2d_wgrad_plan(xv, cout, 3, 1)[0] in (128, 256)
@@ -2706,6 +2708,7 @@ def test_conv_wgrad_benchmark_shapes_fp16(dev, name, shape, plan):
     assert (tile, xg) == plan, f"{name}: dispatcher picked tile {tile}, xcd-grouped {xg}"
     assert slices >= 2, f"{name}: one pixel slice -- the split-K sum is not exercised"
     dw, _ = ops.conv2d_wgrad(xv, gv, k, s, cout, cin)
+    assert ops.conv2d_wgrad_last_plan() == (tile, slices, xg), "the launch did not take the planned form"
     dw2, _ = ops.conv2d_wgrad(xv, gv, k, s, cout, cin)
     torch.cuda.synchronize()
     assert torch.equal(dw, dw2), "filter gradient is not run-to-run deterministic"

@@ -324,7 +324,9 @@ WGRAD_PATCH_SLICES = {"patch_many_slices": lambda s: s > 1, "patch_one_slice": l
                          ids=[f"{c[0]}-{str(dt).split('.')[-1]}" for c in WGRAD_SLICED for dt in c[3]])
 def test_conv_wgrad_on_sliced_views(dev, tune, name, shape, knobs, dtype, tile, bound):
     """y3_conv2d_wgrad on every plan with x AND du channel slices of NaN-filled buffers: dW and the bias gradient are finite, within the plan's own bound of fp32 autograd on the
-    same rounded operands, and the bits of the launch on pitch == c tensors (same plan: tile, slices, grouping); x and du are not written"""
+    same rounded operands, and the bits of the launch on pitch == c tensors (same plan: tile, slices, grouping); x and du are not written.  The form that RAN is asserted
+    (y3_conv2d_wgrad_last_plan): the dry run's, except that the strip kernel refuses a bias gradient -- those launches take what the dry run plans with wgrad_strip = 0, and
+    the strip cases launch once more without a bias gradient, with the same checks on dW"""
     _lib, ops = _ops()
     for key, val in knobs.items():
         tune(key, val)
@@ -338,16 +340,30 @@ def test_conv_wgrad_on_sliced_views(dev, tune, name, shape, knobs, dtype, tile, 
     ho, wo = y.shape[2], y.shape[3]
     lp = (4, 12) if dtype == torch.float32 else PX
     rp = (8, 16) if dtype == torch.float32 else PR
-    res = {}
+    res, strip = {}, {}
     for form, (px, pg) in (("sliced", (lp, rp)), ("flat", (None, None))):
         xb = Buf(ops, dev, dtype, (n, h, w, cin), px, NAN, x.permute(0, 2, 3, 1)).snap()
         gb = Buf(ops, dev, dtype, (n, ho, wo, cout), pg, NAN, gy.permute(0, 2, 3, 1)).snap()
         plan = ops.conv2d_wgrad_plan(xb.v, cout, k, s)
         dw, db = ops.conv2d_wgrad(xb.v, gb.v, k, s, cout, cin, want_bias=True)
+        launched = ops.conv2d_wgrad_last_plan()
         torch.cuda.synchronize()
         xb.check("wgrad x")
         gb.check("wgrad du")
         res[form] = (plan, dw.clone(), db.clone())
+        if tile == 3:
+            tune("wgrad_strip", 0)
+            without_strip = ops.conv2d_wgrad_plan(xb.v, cout, k, s)
+            tune("wgrad_strip", knobs["wgrad_strip"])
+            assert launched == without_strip and launched[0] != 3, f"the launch with a bias gradient took {launched}, without the strip kernel the library plans {without_strip}"
+            dw_s, _ = ops.conv2d_wgrad(xb.v, gb.v, k, s, cout, cin, want_bias=False)
+            assert ops.conv2d_wgrad_last_plan() == plan, f"the launch without a bias gradient took {ops.conv2d_wgrad_last_plan()}, planned {plan}"
+            torch.cuda.synchronize()
+            xb.check("strip wgrad x")
+            gb.check("strip wgrad du")
+            strip[form] = dw_s.clone()
+        else:
+            assert launched == plan, f"the launch took {launched}, planned {plan}"
     plan, dw, db = res["sliced"]
     assert plan[0] == tile, f"the library plans tile {plan[0]} for this view, the case is written for {tile}"
     assert plan == res["flat"][0], f"sliced plan {plan} differs from the contiguous plan {res['flat'][0]}"
@@ -359,6 +375,69 @@ def test_conv_wgrad_on_sliced_views(dev, tune, name, shape, knobs, dtype, tile, 
     print(f"[wgrad views {name} {dtype}] plan {plan}: dW {e_w:.2e}, bias {e_b:.2e}")
     assert e_w < bound and e_b < max(bound, 2e-3), f"{name} {dtype}: wgrad {e_w:.2e} bias {e_b:.2e}"   # (bias bound: test_conv_wgrad_and_dgrad_vs_autograd)
     assert torch.equal(dw, res["flat"][1]) and torch.equal(db, res["flat"][2]), "sliced and contiguous filter gradients differ"
+    if tile == 3:   # the strip kernel itself (no bias gradient) on pitch != c
+        assert torch.isfinite(strip["sliced"]).all(), "the strip kernel read poisoned memory outside its slices"
+        e_s = (strip["sliced"].cpu() - wt.grad).abs().max().item() / wt.grad.abs().max().item()
+        print(f"[wgrad views {name} {dtype}] strip launch, plan {plan}: dW {e_s:.2e}")
+        assert e_s < bound, f"{name} {dtype}: strip wgrad {e_s:.2e}"
+        assert torch.equal(strip["sliced"], strip["flat"]), "sliced and contiguous filter gradients of the strip kernel differ"
+
+
+WGRAD_FORMS = [
+    # id, the smallest (n,h,w,cin,cout,k,s) that reaches the form, its knobs, dtypes, tile of the dry run, the knob that takes the form away where it refuses a request
+    ("strip", (1, 3, 70, 32, 64, 3, 1), {"wgrad_strip": 7}, HALVES, 3, "wgrad_strip"),   # (refuses a bias gradient and real channel subsets)
+    ("patch", (1, 2, 3, 64, 128, 3, 1), {"wgrad_patch": 2}, HALVES, 4, None),
+    ("tile256", (1, 16, 16, 128, 256, 3, 1), {"wgrad": 3, "wgrad_patch": 0}, HALVES, 256, None),
+    ("tile128", (2, 20, 20, 64, 128, 3, 1), {"wgrad_patch": 0, "wgrad_strip": 0}, HALVES, 128, None),
+    ("direct_fp32", (2, 8, 8, 8, 32, 3, 1), {}, [torch.float32], 0, None),
+]
+
+
+def _wgrad_form_bound(tile, dtype):
+    """the bounds of WGRAD_SLICED, by the form that ran: the tile kernels 2e-3 / 1.5e-2, strip / patch / direct 2e-5"""
+    return {torch.float16: 2e-3, torch.bfloat16: 1.5e-2}[dtype] if tile in (128, 256) else 2e-5
+
+
+@pytest.mark.parametrize("name,shape,knobs,dtype,tile,refusing", [(c[0], c[1], c[2], dt, c[4], c[5]) for c in WGRAD_FORMS for dt in c[3]],
+                         ids=[f"{c[0]}-{str(dt).split('.')[-1]}" for c in WGRAD_FORMS for dt in c[3]])
+def test_conv_wgrad_launches_the_planned_form(dev, tune, name, shape, knobs, dtype, tile, refusing):
+    """every form of the filter-gradient dispatch, launched plain, with a bias gradient and with cout_real = cout - 1 on sliced x and du: the form that ran
+    (y3_conv2d_wgrad_last_plan) is the dry run's -- where the form refuses the request (strip: bias gradient, real subset) the dry run's with that form's knob at 0 --
+    and dW / the bias gradient are within the bound of the form that ran of fp32 autograd on the same rounded operands"""
+    _lib, ops = _ops()
+    for key, val in knobs.items():
+        tune(key, val)
+    n, h, w, cin, cout, k, s = shape
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(n, cin, h, w, generator=g).to(dtype).float()
+    wt = torch.zeros(cout, cin, k, k, requires_grad=True)
+    y = F.conv2d(x, wt, None, stride=s, padding=k // 2)
+    gy = torch.randn(y.shape, generator=g).to(dtype).float()
+    y.backward(gy)
+    xb = Buf(ops, dev, dtype, (n, h, w, cin), (4, 12) if dtype == torch.float32 else PX, NAN, x.permute(0, 2, 3, 1)).snap()
+    gb = Buf(ops, dev, dtype, (n, y.shape[2], y.shape[3], cout), (8, 16) if dtype == torch.float32 else PR, NAN, gy.permute(0, 2, 3, 1)).snap()
+    plan = ops.conv2d_wgrad_plan(xb.v, cout, k, s)
+    assert plan[0] == tile, f"the library plans tile {plan[0]} for this view, the case is written for {tile}"
+    fallback = plan
+    if refusing:
+        tune(refusing, 0)
+        fallback = ops.conv2d_wgrad_plan(xb.v, cout, k, s)
+        tune(refusing, knobs[refusing])
+        assert fallback[0] != tile
+    scale = wt.grad.abs().max().item()
+    for what, cout_real, want_bias, want in (("plain", cout, False, plan), ("bias", cout, True, fallback), ("real_subset", cout - 1, False, fallback)):
+        dw, db = ops.conv2d_wgrad(xb.v, gb.v, k, s, cout_real, cin, want_bias=want_bias)
+        launched = ops.conv2d_wgrad_last_plan()
+        torch.cuda.synchronize()
+        xb.check(f"wgrad x ({what})")
+        gb.check(f"wgrad du ({what})")
+        assert launched == want, f"{name} {what}: the launch took {launched}, expected {want} (dry run {plan})"
+        bound = _wgrad_form_bound(launched[0], dtype)
+        assert dw.shape[0] == cout_real and torch.isfinite(dw).all()
+        e_w = (dw.cpu() - wt.grad[:cout_real]).abs().max().item() / scale
+        e_b = (db.cpu() - gy.sum((0, 2, 3))).abs().max().item() / gy.sum((0, 2, 3)).abs().max().item() if want_bias else 0.0
+        print(f"[wgrad forms {name} {dtype} {what}] launched {launched}: dW {e_w:.2e}, bias {e_b:.2e}")
+        assert e_w < bound and e_b < max(bound, 2e-3), f"{name} {dtype} {what}: wgrad {e_w:.2e} bias {e_b:.2e}"   # (bias bound: test_conv_wgrad_and_dgrad_vs_autograd)
 
 
 # ------------------------------------------------------------------------------------------------ data gradient

@@ -575,6 +575,68 @@ def test_wgrad_geometry_fills_whole_rounds():
     assert L.y3_conv2d_wgrad_plan(C.byref(_desc(_lib.Y3_F16, 3, 1, 32, 64)), C.byref(x), C.byref(tile), C.byref(slices), C.byref(xg)) == 0 and tile.value == 128
 
 
+def test_wgrad_dispatch_table_is_unchanged(lib, golden_dir):
+    """y3_conv2d_wgrad_plan and y3_conv2d_wgrad_workspace_bytes answer, row for row, what the commit before the single-source dispatch answered
+    (tests/golden/wgrad_dispatch.json, written by make_wgrad_dispatch_golden.py from THAT commit's library): every model conv at three batch sizes and two map
+    sizes, both sides of every threshold, three dtypes, every filter-gradient knob on rows it changes, all five forms."""
+    import json
+
+    from yolov3_amd import _lib
+
+    table = json.loads((golden_dir / "wgrad_dispatch.json").read_text())
+    rows = table["rows"]
+    assert len(rows) >= 500 and all(sum(1 for r in rows if r[9] == form) >= 10 for form in (0, 3, 4, 128, 256))
+    tile, slices, xg = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+    wrong, current = [], None
+    try:
+        for ki, dtype, k, s, cin, cout, n, h, w, *want in rows:
+            if ki != current:
+                lib.y3_tune_reset()
+                for key, val in table["knob_sets"][ki].items():
+                    assert lib.y3_tune_set(key.encode(), val) == 0, key
+                current = ki
+            d, x = _lib.Y3ConvDesc(dtype, k, s, 0, 0, 0, cin, cout, 0), _lib.Y3Tensor(4096, n, h, w, cin, cin)
+            assert lib.y3_conv2d_wgrad_plan(C.byref(d), C.byref(x), C.byref(tile), C.byref(slices), C.byref(xg)) == 0
+            got = [tile.value, slices.value, xg.value, lib.y3_conv2d_wgrad_workspace_bytes(C.byref(d), C.byref(x))]
+            if got != want:
+                wrong.append((table["knob_sets"][ki], dtype, (k, s, cin, cout, n, h, w), want, got))
+    finally:
+        lib.y3_tune_reset()
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ, the first: {wrong[:3]}"
+
+
+def test_wgrad_last_plan_is_declared_bound_exported_and_fails_before_a_launch(lib):
+    """y3_conv2d_wgrad_last_plan (the decision of the thread's last successful y3_conv2d_wgrad): in the header, the bindings and the library; on a thread that has
+    launched nothing it fails and says so under its own name; null outputs are refused"""
+    import threading
+
+    from yolov3_amd import _lib, ops
+
+    header = (ROOT / "include" / "yolov3_hip.h").read_text()
+    assert re.search(r"\by3_conv2d_wgrad_last_plan\s*\(", header) and "y3_conv2d_wgrad_last_plan" in _lib.exported_symbols()
+    assert "y3_conv2d_wgrad_last_plan" in _lib._QUERIES and callable(ops.conv2d_wgrad_last_plan)
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], text=True)
+    assert re.search(r" T y3_conv2d_wgrad_last_plan\b", nm)
+    seen = []
+
+    def fresh():
+        tile, slices, xg = C.c_int32(7), C.c_int64(7), C.c_int32(7)
+        seen.append((lib.y3_conv2d_wgrad_last_plan(C.byref(tile), C.byref(slices), C.byref(xg)), lib.y3_last_error(), tile.value))
+        seen.append((lib.y3_conv2d_wgrad_last_plan(None, C.byref(slices), C.byref(xg)), lib.y3_last_error(), tile.value))
+        try:
+            ops.conv2d_wgrad_last_plan()
+        except _lib.Y3Error as e:
+            seen.append(str(e))
+
+    t = threading.Thread(target=fresh)
+    t.start()
+    t.join()
+    (rc, msg, tile), (rc0, msg0, _), raised = seen
+    assert rc != 0 and msg.startswith(b"y3_conv2d_wgrad_last_plan") and b"no y3_conv2d_wgrad" in msg and tile == 7, (rc, msg, tile)
+    assert rc0 != 0 and msg0.startswith(b"y3_conv2d_wgrad_last_plan") and b"null" in msg0, (rc0, msg0)
+    assert "y3_conv2d_wgrad_last_plan" in raised
+
+
 def test_map_parity_helpers_on_cpu():
     """tests/map_parity.py (the mAP-parity experiment of the GPU suite): the scene generator is seeded and emits the reference's label
     format with boxes that match the painted rectangles; the oracle evaluation runs end to end (random weights: no assertion on the value)

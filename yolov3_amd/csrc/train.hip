@@ -381,15 +381,6 @@ __global__ __launch_bounds__(256) void wgrad_direct_reduce_kernel(const float* _
     dw[idx] = a;
 }
 
-// pixel slices of the direct filter-gradient kernel: enough to fill the machine when the filter is small
-static long long wgrad_direct_slices(long long total, long long M) {
-    long long want = (256LL * 8 * 256 + total - 1) / total;
-    if (want > M / 64) want = M / 64;
-    if (want < 1) want = 1;
-    if (want > 4096) want = 4096;
-    return want;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Filter gradient on MFMA:  dW[co][(tap,ci)] = sum_m du[m][co] * x[m@tap][ci]  -- a GEMM whose reduction axis (pixels)
 // is the SLOW axis of both NHWC operands.  Each loader thread therefore fetches 4 consecutive pixels x 8 channels
@@ -946,9 +937,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* __restr
 }
 
 // slice groups per block for a slab sum of `units` 16-byte units over `slices` slabs: enough threads to fill the chip, at least 8 slabs per group
+constexpr int SLAB_SUM_MAX_GROUPS = 32;   // the reduce kernels split a block's 256 threads into 256 / G units x G groups: G doubles from 1, so the cap bounds every G
+static_assert((SLAB_SUM_MAX_GROUPS & (SLAB_SUM_MAX_GROUPS - 1)) == 0 && SLAB_SUM_MAX_GROUPS <= 32, "slice groups: a power of two, at most 32");
+static_assert(256 % SLAB_SUM_MAX_GROUPS == 0, "slice groups: a divisor of the 256 threads of a reduce block");
 static int slab_sum_groups(long long units, long long slices) {
     int G = 1;
-    while (G < 32 && units * G < 65536 && slices >= 16LL * G) G *= 2;
+    while (G < SLAB_SUM_MAX_GROUPS && units * G < 65536 && slices >= 16LL * G) G *= 2;
     return G;
 }
 
@@ -1961,27 +1955,45 @@ extern "C" int y3_fold_pack_jobs(const y3_fold_pack_job* jobs_device, int32_t n_
 
 // knob "wgrad": 0 per shape; 2 the 128x128 kernel; 3 the 256x256 kernel whenever the shape allows it (tests); 4 the direct fp32 kernel
 static int wgrad_mode() { return (int)y3_knob(Y3K_WGRAD); }
-// 256x256 tiles (one 8-wave block per CU): whole 256-filter tiles, a long reduction and enough columns to fill the tile
-static bool wgrad_use_big(const y3_conv_desc* d, long long M) {
-    const int mode = wgrad_mode();
-    if (d->dtype == Y3_F32 || mode == 2 || mode == 4) return false;
-    const bool shape_ok = (d->cout % 256) == 0 && d->ksize * d->ksize * d->cin >= 1024 && M >= 256;
-    if (mode == 3) return shape_ok;
-    return shape_ok && d->ksize * d->ksize * d->cin >= 1152 && M >= 16384;
+// ---- the filter-gradient dispatch: ONE decision (wgrad_decide), read by the dry run, the workspace query and the launch ----
+struct WgradQuery {   // the question: x geometry and pitch (d->cin channels), du pitch (d->cout channels), real counts, bias gradient wanted; wgrad_query derives Ho, Wo, M
+    const y3_conv_desc* d;
+    int n, h, w, xpitch, dpitch, cout_real, cin_real;
+    bool want_dbias;
+    int Ho, Wo;
+    long long M;   // output map, pixels
+};
+static WgradQuery wgrad_query(const y3_conv_desc* d, const y3_tensor* x, int dpitch, int cout_real, int cin_real, bool want_dbias) {
+    const int pad = d->ksize / 2, Ho = (x->h + 2 * pad - d->ksize) / d->stride + 1, Wo = (x->w + 2 * pad - d->ksize) / d->stride + 1;
+    return WgradQuery{d, x->n, x->h, x->w, x->pitch, dpitch, cout_real, cin_real, want_dbias, Ho, Wo, (long long)x->n * Ho * Wo};
 }
 #include "wgrad_strip.h"
 #include "wgrad_patch.h"
+struct WgradPlan {   // the answer
+    int form;                      // the tile codes of y3_conv2d_wgrad_plan: 0 direct, 3 strip (wgrad_strip.h), 4 padded positions (wgrad_patch.h), 128 / 256 tiles
+    long long slices;              // as y3_conv2d_wgrad_plan reports them (strip: blocks; direct: 0)
+    int xcd_grouped;
+    size_t ws_bytes;               // workspace the form needs (direct: 0 when one slice serves)
+    StripPlan strip; PatchPlan patch;   // the form's own geometry: forms 3 and 4
+    int n_ct, n_nt, tsh;           // forms 128 / 256
+    long long per, direct_slices;  // forms 128 / 256; form 0
+    long long x_bytes, du_bytes;   // reach of the two buffer descriptors (half precision)
+};
 
-static void wgrad_geometry(const y3_conv_desc* d, long long M, int& n_ct, int& n_nt, long long& slices, long long& per, int& tsh) {
-    if (wgrad_use_big(d, M)) {
-        tsh = 8;
-        n_ct = y3_ceil_div(d->cout, 256);
-        n_nt = y3_ceil_div(d->ksize * d->ksize * d->cin, 256);
-        const long long tiles = (long long)n_ct * n_nt;
+// The tile kernels.  256x256 (one 8-wave block per CU): whole 256-filter tiles, a long reduction and enough columns to fill the tile
+static void plan_tiles(const WgradQuery& q, WgradPlan& p) {
+    const y3_conv_desc* d = q.d;
+    const int mode = wgrad_mode(), K = d->ksize * d->ksize * d->cin;
+    const long long M = q.M;   // pixels
+    const bool shape_ok = d->dtype != Y3_F32 && mode != 2 && mode != 4 && (d->cout % 256) == 0 && K >= 1024 && M >= 256;
+    const bool big = shape_ok && (mode == 3 || (K >= 1152 && M >= 16384));
+    p.tsh = big ? 8 : 7; p.form = 1 << p.tsh;
+    p.n_ct = y3_ceil_div(d->cout, p.form); p.n_nt = y3_ceil_div(K, p.form);
+    const long long tiles = (long long)p.n_ct * p.n_nt;
+    if (big) {
         // one block per CU: pick the slice count with the fewest (rounds of 256 blocks) x (pixels per block + a fixed
         // prologue/epilogue cost of ~8 K-steps); every slice writes a 256 KiB partial tile, so ties go to fewer slices
         long long smax = M / 256;   // at least 8 K-steps (of 32 pixels) per block
-        if (smax < 1) smax = 1;
         if (smax > 512) smax = 512;
         long long best = 1, best_cost = -1;
         for (long long sl = 1; sl <= smax; ++sl) {
@@ -1990,208 +2002,179 @@ static void wgrad_geometry(const y3_conv_desc* d, long long M, int& n_ct, int& n
             const long long cost = rounds * len;
             if (best_cost < 0 || cost < best_cost) { best = sl; best_cost = cost; }
         }
-        slices = best;
-        per = (M + slices - 1) / slices;
-        per = (per + 31) / 32 * 32;
-        slices = (M + per - 1) / per;
-        return;
+        p.slices = best;
+    } else {
+        const long long want_blocks = y3_knob(Y3K_WGRAD_BLOCKS) > 0 ? y3_knob(Y3K_WGRAD_BLOCKS) : 512;
+        p.slices = (want_blocks + tiles - 1) / tiles;              // knob "wgrad_blocks": one round of resident blocks (2 per CU); 1024 = two rounds wrote twice the slabs for no gain (profiles/r06_wgrad_blocks_ab.txt)
+        const long long max_slices = (M + 511) / 512;              // at least 8 K-steps (of 64 pixels) per block
+        if (p.slices > max_slices) p.slices = max_slices;
+        if (p.slices < 1) p.slices = 1;
     }
-    tsh = 7;
-    n_ct = y3_ceil_div(d->cout, 128);
-    n_nt = y3_ceil_div(d->ksize * d->ksize * d->cin, 128);
-    const long long tiles = (long long)n_ct * n_nt;
-    const long long want_blocks = y3_knob(Y3K_WGRAD_BLOCKS) > 0 ? y3_knob(Y3K_WGRAD_BLOCKS) : 512;
-    slices = (want_blocks + tiles - 1) / tiles;                // knob "wgrad_blocks": one round of resident blocks (2 per CU); 1024 = two rounds wrote twice the slabs for no gain (profiles/r06_wgrad_blocks_ab.txt)
-    const long long max_slices = (M + 511) / 512;              // at least 8 K-steps (of 64 pixels) per block
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    per = (M + slices - 1) / slices;
-    per = (per + 63) / 64 * 64;
-    slices = (M + per - 1) / per;
+    const int kstep = big ? 32 : 64;
+    p.per = ((M + p.slices - 1) / p.slices + kstep - 1) / kstep * kstep;
+    p.slices = (M + p.per - 1) / p.per;
+    // wgrad_block: a slice's tiles back to back on one XCD.  Measured at batch 64 (profiles/r02_wgrad_xcd.txt): 64 -> 128 layers 0.60 -> 0.48 and 0.52 -> 0.45 ms, the 256-tile
+    // kernel slightly better, but the narrow (<= 64-filter, 3 column tiles) launches of the 320x320 maps lose 10-15 %, so those keep the dispatch order.
+    // Knob "wgrad_xcd" = 0: never; 1: 128-tile kernels only; 2 (default): + the 256-tile kernel; 3: all
+    const int xcd_need = big ? 2 : (d->cout <= 64 ? 3 : 1);
+    p.xcd_grouped = (tiles > 1 && p.slices > 1 && (int)y3_knob(Y3K_WGRAD_XCD) >= xcd_need) ? 1 : 0;
+    p.ws_bytes = ((size_t)p.slices * tiles * sizeof(float)) << (2 * p.tsh);
+}
+static void plan_direct(const WgradQuery& q, WgradPlan& p) {
+    const long long total = (long long)q.cout_real * q.cin_real * q.d->ksize * q.d->ksize;
+    p.form = 0; p.slices = 0; p.xcd_grouped = 0;
+    p.direct_slices = total > 0 ? (256LL * 8 * 256 + total - 1) / total : 1;   // pixel slices: enough to fill the machine when the filter is small
+    if (p.direct_slices > q.M / 64) p.direct_slices = q.M / 64;
+    if (p.direct_slices < 1) p.direct_slices = 1;
+    if (p.direct_slices > 4096) p.direct_slices = 4096;
+    p.ws_bytes = p.direct_slices > 1 ? (size_t)p.direct_slices * total * sizeof(float) : 0;
+}
+// The decision.  Preference: direct (knob "wgrad" = 4, fp32, or an operand beyond the 2 GB reach of a buffer descriptor) -> strip -> patch -> 256 -> 128
+static void wgrad_decide(const WgradQuery& q, WgradPlan& p) {
+    p.x_bytes = (((long long)q.n * q.h * q.w - 1) * q.xpitch + q.d->cin) * 2;
+    p.du_bytes = ((q.M - 1) * q.dpitch + q.d->cout) * 2;
+    if (q.d->dtype == Y3_F32 || wgrad_mode() == 4 || p.x_bytes >= 0x7fffffffLL || p.du_bytes >= 0x7fffffffLL) plan_direct(q, p);
+    else if (strip_plan(q, p.strip)) { p.form = 3; p.slices = p.strip.blocks; p.xcd_grouped = 0; p.ws_bytes = p.strip.ws_bytes; }
+    else if (patch_plan(q, p.patch)) { p.form = 4; p.slices = p.patch.slices; p.xcd_grouped = 1; p.ws_bytes = p.patch.ws_bytes; }
+    else plan_tiles(q, p);
 }
 
-static int wgrad_xcd_grouped(const y3_conv_desc* d, long long tiles, long long slices, int tsh) {
-    const int xcd_mode = (int)y3_knob(Y3K_WGRAD_XCD);
-    const bool narrow = tsh == 7 && d->cout <= 64;
-    return (tiles > 1 && slices > 1 && (narrow ? xcd_mode >= 3 : (tsh == 8 ? xcd_mode >= 2 : xcd_mode >= 1))) ? 1 : 0;
-}
-
-// geometry y3_conv2d_wgrad would launch for (desc, x): tile edge (128 / 256; 0 = the direct fp32 kernel), pixel slices, and whether a
-// slice's tiles are placed back to back on one XCD -- so that tests can assert WHICH form a shape exercises
+// The decision for (desc, x) with du->pitch == cout, real channel counts equal to the padded ones and NO bias gradient (nothing is launched): tile code (WgradPlan::form),
+// pixel slices, and whether a slice's tiles are placed back to back on one XCD.  A launch that differs in one of the three may take another form (the strip kernel
+// refuses a bias gradient and real subsets): y3_conv2d_wgrad_last_plan reports what a launch took
 extern "C" int y3_conv2d_wgrad_plan(const y3_conv_desc* d, const y3_tensor* x, int32_t* tile, int64_t* slices_out, int32_t* xcd_grouped) {
     if (!d || !x || !tile || !slices_out || !xcd_grouped) Y3_FAIL("y3_conv2d_wgrad_plan: null argument");
-    const int pad = d->ksize / 2;
-    const int Ho = (x->h + 2 * pad - d->ksize) / d->stride + 1, Wo = (x->w + 2 * pad - d->ksize) / d->stride + 1;
-    const long long M = (long long)x->n * Ho * Wo;
-    const long long xb = (((long long)x->n * x->h * x->w - 1) * x->pitch + x->c) * 2, db_ = ((M - 1) * d->cout + d->cout) * 2;
-    if (d->dtype == Y3_F32 || wgrad_mode() == 4 || xb >= 0x7fffffffLL || db_ >= 0x7fffffffLL) {
-        *tile = 0; *slices_out = 0; *xcd_grouped = 0;
-        return 0;
-    }
-    StripPlan sp;
-    if (strip_plan(d, x->n, x->h, x->w, d->cout, d->cin, false, sp)) {   // (the query has no real channel counts: the padded ones, which is what these layers have)
-        *tile = 3; *slices_out = sp.blocks; *xcd_grouped = 0;             // tile 3 = the 3x3 strip kernel (wgrad_strip.h)
-        return 0;
-    }
-    PatchPlan pp;
-    if (patch_plan(d, x->n, x->h, x->w, pp)) {
-        *tile = 4; *slices_out = pp.slices; *xcd_grouped = 1;             // tile 4 = the padded-position kernel (wgrad_patch.h)
-        return 0;
-    }
-    int n_ct, n_nt, tsh;
-    long long slices, per;
-    wgrad_geometry(d, M, n_ct, n_nt, slices, per, tsh);
-    *tile = 1 << tsh;
-    *slices_out = slices;
-    *xcd_grouped = wgrad_xcd_grouped(d, (long long)n_ct * n_nt, slices, tsh);
+    WgradPlan p;
+    wgrad_decide(wgrad_query(d, x, d->cout, d->cout, d->cin, false), p);
+    *tile = p.form; *slices_out = p.slices; *xcd_grouped = p.xcd_grouped;
     return 0;
 }
 
+// The LARGEST need over all forms whose shape test passes, not the decision's: a caller sizes one buffer per slot and knobs may change the decision afterwards
 extern "C" size_t y3_conv2d_wgrad_workspace_bytes(const y3_conv_desc* d, const y3_tensor* x) {
     if (!d || !x) return 256;
-    const int pad = d->ksize / 2;
-    const int Ho = (x->h + 2 * pad - d->ksize) / d->stride + 1, Wo = (x->w + 2 * pad - d->ksize) / d->stride + 1;
-    // the direct kernel's partials (fp32 always; f16 / bf16 when it is forced or an operand passes the reach of a buffer descriptor): real sizes <= padded sizes
-    const long long total_d = (long long)d->cout * d->cin * d->ksize * d->ksize;
-    const long long slices_d = total_d > 0 ? wgrad_direct_slices(total_d, (long long)x->n * Ho * Wo) : 1;
-    const size_t need_d = slices_d > 1 ? (size_t)slices_d * total_d * sizeof(float) : 256;
-    if (d->dtype == Y3_F32) return need_d;
-    int n_ct, n_nt, tsh;
-    long long slices, per;
-    wgrad_geometry(d, (long long)x->n * Ho * Wo, n_ct, n_nt, slices, per, tsh);
-    size_t need = ((size_t)slices * n_ct * n_nt * sizeof(float)) << (2 * tsh);
-    StripPlan sp;
-    if (strip_plan(d, x->n, x->h, x->w, d->cout, d->cin, false, sp) && sp.ws_bytes > need) need = sp.ws_bytes;
-    PatchPlan pp;
-    if (patch_plan(d, x->n, x->h, x->w, pp) && pp.ws_bytes > need) need = pp.ws_bytes;
-    return need > need_d ? need : need_d;
+    const WgradQuery q = wgrad_query(d, x, d->cout, d->cout, d->cin, false);   // (real sizes <= padded sizes)
+    WgradPlan p;
+    plan_direct(q, p);   // fp32 always; f16 / bf16 when it is forced or an operand passes the reach of a buffer descriptor
+    size_t need = p.direct_slices > 1 ? p.ws_bytes : 256;
+    if (d->dtype == Y3_F32) return need;
+    plan_tiles(q, p);
+    if (p.ws_bytes > need) need = p.ws_bytes;
+    if (strip_plan(q, p.strip) && p.strip.ws_bytes > need) need = p.strip.ws_bytes;
+    if (patch_plan(q, p.patch) && p.patch.ws_bytes > need) need = p.patch.ws_bytes;
+    return need;
 }
+
+template <typename T> static void launch_tiles_t(const WgradArgs& a, int tsh, dim3 grid, hipStream_t st) {
+    if (tsh == 8) hipLaunchKernelGGL((wgrad_big_kernel<T>), grid, dim3(512), 0, st, a);
+    else if (a.Cout <= 32) hipLaunchKernelGGL((wgrad_dma_kernel<T, 1>), grid, dim3(256), 0, st, a);   // narrow filter tiles for the <= 64-filter layers (one filter tile, n_ct == 1)
+    else if (a.Cout <= 64) hipLaunchKernelGGL((wgrad_dma_kernel<T, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((wgrad_dma_kernel<T, 4>), grid, dim3(256), 0, st, a);
+}
+static int launch_tiles(const WgradQuery& q, const WgradPlan& p, const y3_tensor* x, const y3_tensor* du, float* dw, void* ws, hipStream_t st) {
+    const y3_conv_desc* d = q.d;
+    WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x->data; a.du = du->data; a.dw = dw; a.part = (float*)ws;
+    a.N = q.n; a.H = q.h; a.W = q.w; a.Cin = d->cin; a.xpitch = q.xpitch; a.Ho = q.Ho; a.Wo = q.Wo; a.Cout = d->cout; a.dpitch = q.dpitch;
+    a.ks = d->ksize; a.stride = d->stride; a.pad = d->ksize / 2; a.cin_real = q.cin_real; a.cout_real = q.cout_real; a.M = q.M;
+    a.x_bytes = (unsigned)p.x_bytes; a.du_bytes = (unsigned)p.du_bytes; a.dv_hw = y3_make_divisor(q.Ho * q.Wo); a.dv_w = y3_make_divisor(q.Wo);
+    a.step_n = 32 / (q.Ho * q.Wo); a.step_q = (32 % (q.Ho * q.Wo)) / q.Wo; a.step_r = (32 % (q.Ho * q.Wo)) % q.Wo;
+    a.n_nt = p.n_nt; a.per_slice = (int)p.per; a.xcd_group = p.xcd_grouped;
+    const int tsh = p.tsh, tiles = p.n_ct * p.n_nt, slices = (int)p.slices;
+    const dim3 grid((unsigned)tiles, (unsigned)slices);
+    if (d->dtype == Y3_F16) launch_tiles_t<f16_t>(a, tsh, grid, st); else launch_tiles_t<bf16_t>(a, tsh, grid, st);
+    Y3_CHECK_LAUNCH();
+    if ((((uintptr_t)ws) & 15) == 0) {   // (the one-element kernel serves workspaces that are not 16-byte aligned)
+        const long long units = ((long long)tiles << (2 * tsh)) / 4;
+        const int G = slab_sum_groups(units, slices);
+        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((units * G + 255) / 256)), dim3(256), 0, st, (const float*)ws, tiles, p.n_nt, slices, d->cin, d->ksize, q.cin_real,
+                           q.cout_real, dw, tsh, G);
+    } else
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nblk((long long)tiles << (2 * tsh))), dim3(256), 0, st, (const float*)ws, tiles, p.n_nt, slices, d->cin, d->ksize, q.cin_real,
+                           q.cout_real, dw, tsh);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+static int launch_direct(const WgradQuery& q, const y3_tensor* x, const y3_tensor* du, float* dw, int slices, float* part, hipStream_t st) {
+    const y3_conv_desc* d = q.d;
+    const long long total = (long long)q.cout_real * q.cin_real * d->ksize * d->ksize;
+    Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((wgrad_direct_kernel<T>), dim3(nblk(total), (unsigned)slices), dim3(256), 0, st, (const T*)x->data, q.n, q.h, q.w, d->cin, q.xpitch,
+                                               (const T*)du->data, q.Ho, q.Wo, d->cout, q.dpitch, d->ksize, d->stride, d->ksize / 2, q.cin_real, q.cout_real, dw, slices, part));
+    Y3_CHECK_LAUNCH();
+    if (part) hipLaunchKernelGGL(wgrad_direct_reduce_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float*)part, total, slices, dw);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+// bias gradient = per-channel sum of du.  The filter-gradient workspace is idle again (stream order): it holds the per-block partial rows of the BN reduction
+// kernel, summed in a fixed order (one strided block per channel ran at 0.35 ms per head on batch 64)
+static int launch_dbias(const WgradQuery& q, const y3_tensor* du, float* dbias, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const y3_conv_desc* d = q.d;
+    const int esz = esize(d->dtype);
+    unsigned grid = 0;
+    const size_t row_bytes = (size_t)2 * d->cout * sizeof(double);
+    // (fp32 keeps the one-block-per-channel sum it always ran: its workspace held 256 bytes until the direct kernel's partials moved into it)
+    if (d->dtype != Y3_F32 && vec_ok(du, esz) && d->cout / (16 / esz) <= 256 && workspace && workspace_bytes >= 3 * row_bytes && (((uintptr_t)workspace) & 7) == 0) {
+        if (reduce_geometry(d->cout, esz, q.M, grid)) return -1;
+        const size_t fit = workspace_bytes / row_bytes - 1;
+        if (grid > fit) grid = (unsigned)fit;
+    }
+    if (grid) {
+        double* sums = (double*)workspace;
+        Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((channel_reduce_kernel<T, 0>), dim3(grid), dim3(256), 0, st, (const T*)du->data, du->pitch, (const T*)nullptr, 0, q.M, d->cout,
+                                                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, sums));
+        Y3_CHECK_LAUNCH();
+        hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3((2 * d->cout + 15) / 16), dim3(256), 0, st, sums, 2 * d->cout, (int)grid, BnFinalizeArgs{}, dbias, (float*)nullptr,
+                           q.cout_real);
+    } else
+        Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((channel_sum_kernel<T>), dim3((unsigned)q.cout_real), dim3(256), 0, st, (const T*)du->data, du->pitch, q.M, d->cout, dbias));
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+static thread_local WgradPlan g_wgrad_last = {-1};   // the decision of the last successful y3_conv2d_wgrad of this thread (form -1: none yet)
 
 extern "C" int y3_conv2d_wgrad(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* du, int32_t cout_real, int32_t cin_real, float* dw_oihw, float* dbias,
                                void* workspace, size_t workspace_bytes, void* stream) {
     if (!d || !x || !du || !dw_oihw) Y3_FAIL("y3_conv2d_wgrad: null argument");
     if (x->c != d->cin || du->c != d->cout) Y3_FAIL("y3_conv2d_wgrad: channel mismatch");
-    const int pad = d->ksize / 2;
-    const int Ho = (x->h + 2 * pad - d->ksize) / d->stride + 1, Wo = (x->w + 2 * pad - d->ksize) / d->stride + 1;
-    if (du->n != x->n || du->h != Ho || du->w != Wo) Y3_FAIL("y3_conv2d_wgrad: gradient is (%d,%d,%d), expected (%d,%d,%d)", du->n, du->h, du->w, x->n, Ho, Wo);
+    const WgradQuery q = wgrad_query(d, x, du->pitch, cout_real, cin_real, dbias != nullptr);
+    if (du->n != x->n || du->h != q.Ho || du->w != q.Wo) Y3_FAIL("y3_conv2d_wgrad: gradient is (%d,%d,%d), expected (%d,%d,%d)", du->n, du->h, du->w, x->n, q.Ho, q.Wo);
     if (cout_real > d->cout || cin_real > d->cin) Y3_FAIL("y3_conv2d_wgrad: real sizes exceed padded sizes");
     hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)cout_real * cin_real * d->ksize * d->ksize;
-    const long long M = (long long)x->n * Ho * Wo;
-    const bool force_direct = wgrad_mode() == 4;
-    const long long xb = (((long long)x->n * x->h * x->w - 1) * x->pitch + x->c) * 2, db_ = ((M - 1) * du->pitch + du->c) * 2;
-    StripPlan sp;
-    if (!force_direct && xb < 0x7fffffffLL && db_ < 0x7fffffffLL && strip_plan(d, x->n, x->h, x->w, cout_real, cin_real, dbias != nullptr, sp)) {
-        if (!workspace || workspace_bytes < sp.ws_bytes || (((uintptr_t)workspace) & 15)) Y3_FAIL("y3_conv2d_wgrad: workspace too small or not 16-byte aligned");
-        StripArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = x->data; a.du = du->data; a.part = (float*)workspace;
-        a.N = x->n; a.H = x->h; a.W = x->w; a.xpitch = x->pitch; a.Ho = Ho; a.Wo = Wo; a.dpitch = du->pitch;
-        a.x_bytes = (unsigned)xb; a.du_bytes = (unsigned)db_;
-        a.strips = sp.strips; a.T = sp.T; a.per = sp.per;
-        a.dv_ho = y3_make_divisor(Ho); a.dv_strips = y3_make_divisor(sp.strips);
-        if (d->dtype == Y3_F16) launch_strip_t<f16_t>(d, a, sp.blocks, st); else launch_strip_t<bf16_t>(d, a, sp.blocks, st);
-        Y3_CHECK_LAUNCH();
-        {
-            const long long units = (long long)9 * d->cin * d->cout / 4;
-            const int G = slab_sum_groups(units, sp.blocks);
-            hipLaunchKernelGGL(wgrad_strip_reduce_kernel, dim3((unsigned)((units * G + 255) / 256)), dim3(256), 0, st, (const float*)workspace, sp.blocks, d->cin, d->cout, dw_oihw, G);
-        }
-        Y3_CHECK_LAUNCH();
-        return 0;
-    }
-    PatchPlan pp;
-    if (!force_direct && xb < 0x7fffffffLL && db_ < 0x7fffffffLL && patch_plan(d, x->n, x->h, x->w, pp)) {
-        if (!workspace || workspace_bytes < pp.ws_bytes || (((uintptr_t)workspace) & 15)) Y3_FAIL("y3_conv2d_wgrad: workspace too small or not 16-byte aligned");
-        if (launch_patch(d, x, du, cout_real, cin_real, dw_oihw, workspace, pp, (unsigned)xb, (unsigned)db_, st)) return -1;
-    } else if (d->dtype != Y3_F32 && !force_direct && xb < 0x7fffffffLL && db_ < 0x7fffffffLL) {
-        WgradArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = x->data; a.du = du->data; a.dw = dw_oihw; a.part = (float*)workspace;
-        a.N = x->n; a.H = x->h; a.W = x->w; a.Cin = d->cin; a.xpitch = x->pitch; a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.dpitch = du->pitch;
-        a.ks = d->ksize; a.stride = d->stride; a.pad = pad; a.cin_real = cin_real; a.cout_real = cout_real; a.M = M;
-        a.x_bytes = (unsigned)xb; a.du_bytes = (unsigned)db_;
-        a.dv_hw = y3_make_divisor(Ho * Wo); a.dv_w = y3_make_divisor(Wo);
-        a.step_n = 32 / (Ho * Wo); a.step_q = (32 % (Ho * Wo)) / Wo; a.step_r = (32 % (Ho * Wo)) % Wo;
-        if (M > 0x7fffffffLL) Y3_FAIL("y3_conv2d_wgrad: too many pixels");
-        int n_ct, tsh;
-        long long slices, per;
-        wgrad_geometry(d, M, n_ct, a.n_nt, slices, per, tsh);
-        const long long tiles = (long long)n_ct * a.n_nt;
-        if (!workspace || workspace_bytes < (((size_t)slices * tiles * sizeof(float)) << (2 * tsh))) Y3_FAIL("y3_conv2d_wgrad: workspace too small");
-        a.per_slice = (int)per;
-        const dim3 grid((unsigned)tiles, (unsigned)slices);
-        // wgrad_block: a slice's tiles back to back on one XCD.  Measured at batch 64 (profiles/r02_wgrad_xcd.txt): 64 -> 128 layers 0.60 -> 0.48 and
-        // 0.52 -> 0.45 ms, the 256-tile kernel slightly better, but the narrow (<= 64-filter, 3 column tiles) launches of the 320x320 maps lose
-        // 10-15 %, so those keep the dispatch order.  Knob "wgrad_xcd" = 0: never; 1: 128-tile kernels only; 2 (default): + the 256-tile kernel; 3: all
-        a.xcd_group = wgrad_xcd_grouped(d, tiles, slices, tsh);
-        if (tsh == 8) {
-            if (d->dtype == Y3_F16) hipLaunchKernelGGL((wgrad_big_kernel<f16_t>), grid, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((wgrad_big_kernel<bf16_t>), grid, dim3(512), 0, st, a);
-        } else {
-            const int co32 = d->cout <= 32 ? 1 : (d->cout <= 64 ? 2 : 4);   // narrow filter tiles for the <= 64-filter layers (one filter tile, n_ct == 1)
-            if (d->dtype == Y3_F16) {
-                if (co32 == 1) hipLaunchKernelGGL((wgrad_dma_kernel<f16_t, 1>), grid, dim3(256), 0, st, a);
-                else if (co32 == 2) hipLaunchKernelGGL((wgrad_dma_kernel<f16_t, 2>), grid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((wgrad_dma_kernel<f16_t, 4>), grid, dim3(256), 0, st, a);
-            } else {
-                if (co32 == 1) hipLaunchKernelGGL((wgrad_dma_kernel<bf16_t, 1>), grid, dim3(256), 0, st, a);
-                else if (co32 == 2) hipLaunchKernelGGL((wgrad_dma_kernel<bf16_t, 2>), grid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((wgrad_dma_kernel<bf16_t, 4>), grid, dim3(256), 0, st, a);
-            }
-        }
-        Y3_CHECK_LAUNCH();
-        if ((((uintptr_t)workspace) & 15) == 0)   // (the one-element kernel serves workspaces that are not 16-byte aligned)
-        {
-            const long long units = (tiles << (2 * tsh)) / 4;
-            const int G = slab_sum_groups(units, slices);
-            hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((units * G + 255) / 256)), dim3(256), 0, st, (const float*)workspace, (int)tiles, a.n_nt, (int)slices, d->cin,
-                               d->ksize, cin_real, cout_real, dw_oihw, tsh, G);
-        }
-        else
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nblk(tiles << (2 * tsh))), dim3(256), 0, st, (const float*)workspace, (int)tiles, a.n_nt, (int)slices, d->cin, d->ksize, cin_real,
-                               cout_real, dw_oihw, tsh);
-        Y3_CHECK_LAUNCH();
-    } else {
-        long long want = wgrad_direct_slices(total, M);
-        // without room for the partials (a caller that did not size its workspace with y3_conv2d_wgrad_workspace_bytes): one slice, still deterministic
-        if (want > 1 && (!workspace || workspace_bytes < (size_t)want * total * sizeof(float) || (((uintptr_t)workspace) & 3))) want = 1;
-        float* part = want > 1 ? (float*)workspace : nullptr;
-        const dim3 grid(nblk(total), (unsigned)want);
-        Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((wgrad_direct_kernel<T>), grid, dim3(256), 0, st, (const T*)x->data, x->n, x->h, x->w, d->cin, x->pitch,
-                                                   (const T*)du->data, Ho, Wo, d->cout, du->pitch, d->ksize, d->stride, pad, cin_real, cout_real, dw_oihw, (int)want, part));
-        Y3_CHECK_LAUNCH();
-        if (part) {
-            hipLaunchKernelGGL(wgrad_direct_reduce_kernel, dim3(nblk(total)), dim3(256), 0, st, (const float*)part, total, (int)want, dw_oihw);
-            Y3_CHECK_LAUNCH();
+    WgradPlan p{};   // (the members of the forms not chosen stay zero: the whole answer is kept for y3_conv2d_wgrad_last_plan)
+    wgrad_decide(q, p);
+    const bool fits = workspace && workspace_bytes >= p.ws_bytes;
+    int rc;
+    switch (p.form) {
+        case 3:
+        case 4:
+            if (!fits || (((uintptr_t)workspace) & 15)) Y3_FAIL("y3_conv2d_wgrad: workspace too small or not 16-byte aligned");
+            rc = p.form == 3 ? launch_strip(d, x, du, dw_oihw, workspace, p.strip, (unsigned)p.x_bytes, (unsigned)p.du_bytes, st)
+                             : launch_patch(d, x, du, cout_real, cin_real, dw_oihw, workspace, p.patch, (unsigned)p.x_bytes, (unsigned)p.du_bytes, st);
+            break;
+        case 128:
+        case 256:
+            if (q.M > 0x7fffffffLL) Y3_FAIL("y3_conv2d_wgrad: too many pixels");
+            if (!fits) Y3_FAIL("y3_conv2d_wgrad: workspace too small");
+            rc = launch_tiles(q, p, x, du, dw_oihw, workspace, st);
+            break;
+        default: {
+            // without room for the partials (a caller that did not size its workspace with y3_conv2d_wgrad_workspace_bytes): one slice, still deterministic
+            const bool sliced = p.direct_slices > 1 && fits && (((uintptr_t)workspace) & 3) == 0;
+            rc = launch_direct(q, x, du, dw_oihw, sliced ? (int)p.direct_slices : 1, sliced ? (float*)workspace : nullptr, st);
         }
     }
-    if (dbias) {
-        // bias gradient = per-channel sum of du.  The filter-gradient workspace is idle again (stream order): it holds the
-        // per-block partial rows of the BN reduction kernel, summed in a fixed order (one strided block per channel ran
-        // at 0.35 ms per head on batch 64)
-        const int esz = esize(d->dtype);
-        unsigned grid = 0;
-        const size_t row_bytes = (size_t)2 * d->cout * sizeof(double);
-        // (fp32 keeps the one-block-per-channel sum it always ran: its workspace held 256 bytes until the direct kernel's partials moved into it)
-        if (d->dtype != Y3_F32 && vec_ok(du, esz) && d->cout / (16 / esz) <= 256 && workspace && workspace_bytes >= 3 * row_bytes && (((uintptr_t)workspace) & 7) == 0) {
-            if (reduce_geometry(d->cout, esz, M, grid)) return -1;
-            const size_t fit = workspace_bytes / row_bytes - 1;
-            if (grid > fit) grid = (unsigned)fit;
-        }
-        if (grid) {
-            double* sums = (double*)workspace;
-            Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((channel_reduce_kernel<T, 0>), dim3(grid), dim3(256), 0, st, (const T*)du->data, du->pitch, (const T*)nullptr, 0, M, d->cout,
-                                                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, sums));
-            Y3_CHECK_LAUNCH();
-            hipLaunchKernelGGL(reduce_partials_kernel<3>, dim3((2 * d->cout + 15) / 16), dim3(256), 0, st, sums, 2 * d->cout, (int)grid, BnFinalizeArgs{}, dbias, (float*)nullptr,
-                               cout_real);
-            Y3_CHECK_LAUNCH();
-        } else {
-            Y3_DISPATCH_T(d->dtype, hipLaunchKernelGGL((channel_sum_kernel<T>), dim3((unsigned)cout_real), dim3(256), 0, st, (const T*)du->data, du->pitch, M, d->cout, dbias));
-            Y3_CHECK_LAUNCH();
-        }
-    }
+    if (rc || (dbias && launch_dbias(q, du, dbias, workspace, workspace_bytes, st))) return -1;
+    g_wgrad_last = p;
+    return 0;
+}
+
+// tile code, slices and grouping (as y3_conv2d_wgrad_plan reports them) of the LAST successful y3_conv2d_wgrad of this thread: tests assert the form that ran
+extern "C" int y3_conv2d_wgrad_last_plan(int32_t* tile, int64_t* slices, int32_t* xcd_grouped) {
+    if (!tile || !slices || !xcd_grouped) Y3_FAIL("y3_conv2d_wgrad_last_plan: null argument");
+    if (g_wgrad_last.form < 0) Y3_FAIL("y3_conv2d_wgrad_last_plan: no y3_conv2d_wgrad has succeeded on this thread");
+    *tile = g_wgrad_last.form; *slices = g_wgrad_last.slices; *xcd_grouped = g_wgrad_last.xcd_grouped;
     return 0;
 }
 

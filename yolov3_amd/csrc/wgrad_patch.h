@@ -368,8 +368,9 @@ struct PatchPlan {
 };
 
 // knob "wgrad_patch": 1 the shapes wgrad_big served (>= 16384 pixels); 0 never; 2 every eligible shape (tests)
-static bool patch_plan(const y3_conv_desc* d, int n, int h, int w, PatchPlan& pl) {
-    const int mode = (int)y3_knob(Y3K_WGRAD_PATCH);
+static bool patch_plan(const WgradQuery& q, PatchPlan& pl) {
+    const y3_conv_desc* d = q.d;
+    const int n = q.n, h = q.h, w = q.w, mode = (int)y3_knob(Y3K_WGRAD_PATCH);
     if (mode == 0 || d->dtype == Y3_F32 || d->ksize != 3 || d->stride != 1) return false;
     if ((d->cin % 64) || (d->cout % 128) || w < 2 || h < 1) return false;
     const int back16 = (w + 3 + 15) / 16 * 16;

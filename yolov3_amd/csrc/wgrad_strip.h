@@ -307,15 +307,15 @@ struct StripPlan {
 };
 // the layers this kernel serves: 3x3, pad 1, stride 1 / 2, (32 -> 64) or (64 -> 128) unpadded channels, half precision, no bias gradient, enough K-steps
 // for every block to amortise its partial tile (knob "wgrad_strip": 1 on, 0 off, 2 also small launches, N > 2 also small launches with N K-steps per block -- tests)
-static bool strip_plan(const y3_conv_desc* d, int n, int h, int w, int cout_real, int cin_real, bool want_dbias, StripPlan& pl) {
+static bool strip_plan(const WgradQuery& q, StripPlan& pl) {
+    const y3_conv_desc* d = q.d;
     const long long mode = y3_knob(Y3K_WGRAD_STRIP);
-    if (mode == 0 || wgrad_mode() != 0 || want_dbias) return false;
+    if (mode == 0 || wgrad_mode() != 0 || q.want_dbias) return false;
     if (d->dtype != Y3_F16 && d->dtype != Y3_BF16) return false;
     if (d->ksize != 3 || (d->stride != 1 && d->stride != 2)) return false;
-    if (!((d->cin == 32 && d->cout == 64) || (d->cin == 64 && d->cout == 128)) || cin_real != d->cin || cout_real != d->cout) return false;
-    const int Ho = (h + 2 - 3) / d->stride + 1, Wo = (w + 2 - 3) / d->stride + 1;
-    const int strips = (Wo + 63) / 64;
-    const long long T = (long long)n * strips * Ho;
+    if (!((d->cin == 32 && d->cout == 64) || (d->cin == 64 && d->cout == 128)) || q.cin_real != d->cin || q.cout_real != d->cout) return false;
+    const int strips = (q.Wo + 63) / 64;
+    const long long T = (long long)q.n * strips * q.Ho;
     if (T > 0x3fffffffLL || T < 1) return false;
     const int halves = d->cout / 64;
     const int per_cu = d->cin == 32 ? (d->stride == 1 ? 3 : 2) : (d->stride == 1 ? 2 : 1);   // blocks the LDS of a CU holds (StripGeom::LDS)
@@ -340,4 +340,20 @@ template <typename T> static void launch_strip_t(const y3_conv_desc* d, const St
         if (d->stride == 1) hipLaunchKernelGGL((wgrad_strip_kernel<T, 64, 1>), grid, dim3(StripGeom<64, 1>::NW * 64), 0, st, a);
         else hipLaunchKernelGGL((wgrad_strip_kernel<T, 64, 2>), grid, dim3(StripGeom<64, 2>::NW * 64), 0, st, a);
     }
+}
+
+static int launch_strip(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* du, float* dw, void* ws, const StripPlan& pl, unsigned x_bytes, unsigned du_bytes,
+                        hipStream_t st) {
+    StripArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x->data; a.du = du->data; a.part = (float*)ws;
+    a.N = x->n; a.H = x->h; a.W = x->w; a.xpitch = x->pitch; a.Ho = du->h; a.Wo = du->w; a.dpitch = du->pitch; a.x_bytes = x_bytes; a.du_bytes = du_bytes;
+    a.strips = pl.strips; a.T = pl.T; a.per = pl.per; a.dv_ho = y3_make_divisor(a.Ho); a.dv_strips = y3_make_divisor(pl.strips);
+    if (d->dtype == Y3_F16) launch_strip_t<f16_t>(d, a, pl.blocks, st); else launch_strip_t<bf16_t>(d, a, pl.blocks, st);
+    Y3_CHECK_LAUNCH();
+    const long long units = (long long)9 * d->cin * d->cout / 4;
+    const int G = slab_sum_groups(units, pl.blocks);
+    hipLaunchKernelGGL(wgrad_strip_reduce_kernel, dim3((unsigned)((units * G + 255) / 256)), dim3(256), 0, st, (const float*)ws, pl.blocks, d->cin, d->cout, dw, G);
+    Y3_CHECK_LAUNCH();
+    return 0;
 }

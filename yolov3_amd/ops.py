@@ -255,11 +255,19 @@ def conv2d_wgrad(x: View, du: View, k: int, stride: int, cout_real: int, cin_rea
 
 
 def conv2d_wgrad_plan(x: View, cout: int, k: int, stride: int):
-    """(tile edge, pixel slices, xcd-grouped) of the filter-gradient launch for this shape (y3_conv2d_wgrad_plan: dry run)"""
+    """(tile edge, pixel slices, xcd-grouped) of the filter-gradient launch for this shape with pitch == c gradients, no channel padding and no bias gradient
+    (y3_conv2d_wgrad_plan: dry run)"""
     d = Y3ConvDesc(dtype_code(x.buf.dtype), k, stride, 0, 0, 0, x.c, cout, 0)
     xt = x.y3()
     tile, slices, xg = C.c_int32(0), C.c_int64(0), C.c_int32(0)
     check(_lib.lib().y3_conv2d_wgrad_plan(C.byref(d), C.byref(xt), C.byref(tile), C.byref(slices), C.byref(xg)), "y3_conv2d_wgrad_plan")
+    return int(tile.value), int(slices.value), int(xg.value)
+
+
+def conv2d_wgrad_last_plan():
+    """(tile edge, pixel slices, xcd-grouped) of the last conv2d_wgrad launch of this thread (y3_conv2d_wgrad_last_plan): the form that ran, not a re-derivation (tests)"""
+    tile, slices, xg = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+    check(_lib.lib().y3_conv2d_wgrad_last_plan(C.byref(tile), C.byref(slices), C.byref(xg)), "y3_conv2d_wgrad_last_plan")
     return int(tile.value), int(slices.value), int(xg.value)
 
 
