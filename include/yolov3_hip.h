@@ -227,6 +227,19 @@ int y3_scale_img(const void* src, int32_t dtype, int32_t n, int32_t c, int32_t h
                  int32_t flip_lr, float pad_value, void* dst, void* stream);
 int y3_descale_pred(const void* src, int32_t dtype, int32_t bs, int32_t src_rows, int32_t no, int32_t row0, int32_t nrows, float scale,
                     int32_t flip, float img_h, float img_w, void* dst, int32_t dst_rows, int32_t dst_row0, void* stream);
+/* The batch between the loader and model(imgs) in the reference's train loop (train.py:380, 394-399; utils/dataloaders.py:833-858), csrc/batch_edge.hip.
+ * y3_resize_bilinear: NCHW (n, c, h, w) in Y3_U8 / Y3_F32 / Y3_F16 / Y3_BF16 -> NCHW (n, c, oh, ow) in Y3_F32 / Y3_F16 / Y3_BF16 (a uint8 output is unsupported):
+ * F.interpolate(size=(oh, ow), mode="bilinear", align_corners=False) of to_f32(src) / divisor -- every tap divided (IEEE fp32) before the lerp, the
+ * coordinate / weight arithmetic of y3_scale_img, one rounding to dst_dtype at the end.  divisor > 0; 255 with a uint8 source is `imgs.float() / 255` followed by
+ * the --multi-scale resize, 1 leaves a floating batch as it is.  oh == h and ow == w give to_f32(src) / divisor exactly.  src != dst.
+ * Stores are 16 bytes per lane when ow % 8 == 0 and dst is 16-byte aligned (every --multi-scale size is a multiple of 32); any other launch stores element by
+ * element, with the same results.
+ * y3_quad_collate_u8: collate_fn4 (--quad) on a uint8 batch (bs, c, h, w), bs % 4 == 0, -> uint8 (bs / 4, c, 2h, 2w) in one launch.  upsample_flags: bs / 4
+ * bytes in device memory; group g with a non-zero flag is F.interpolate(im[4g].float(), scale_factor=2.0, mode="bilinear") truncated to uint8, the others are
+ * images 4g / 4g+1 stacked top / bottom in the left half and 4g+2 / 4g+3 in the right half.  Bit-identical to torch.  src != dst. */
+int y3_resize_bilinear(const void* src, int32_t src_dtype, int32_t n, int32_t c, int32_t h, int32_t w, void* dst, int32_t dst_dtype, int32_t oh,
+                       int32_t ow, float divisor, void* stream);
+int y3_quad_collate_u8(const uint8_t* src, int32_t bs, int32_t c, int32_t h, int32_t w, const uint8_t* upsample_flags, uint8_t* dst, void* stream);
 int y3_scale_boxes(float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows,
                    const float* params, void* stream);
 int y3_match_detections(const float* dets, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs,

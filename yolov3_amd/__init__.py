@@ -11,6 +11,8 @@ Public surface mirrors the reference's own Python signatures:
     FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update; ema.ema is the averaged model)
     smart_optimizer / FusedAdam / FusedAdamW / FusedRMSProp   (reference utils/torch_utils.py:207-237, train.py --optimizer; torch-format state dicts)
     check_anchors / kmean_anchors / anchor_metrics / check_anchor_order   (reference utils/autoanchor.py, train.py:255: metric, k-means and genetic loop on the device)
+    multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
+                                         resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
     save_checkpoint / smart_resume / strip_optimizer   (reference train.py:470-488, utils/torch_utils.py smart_resume, utils/general.py strip_optimizer)
     DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py)
@@ -22,6 +24,7 @@ from .val import detect_batches, process_batch, process_batch_batched, run_batch
 from .metrics import ConfusionMatrix, ValStats, ap_per_class, ap_per_class_device, compute_ap, fitness  # noqa: F401
 from .backend import DetectMultiBackend  # noqa: F401
 from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
+from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401
 from .loss import ComputeLoss  # noqa: F401

@@ -27,6 +27,7 @@ SOURCES = [
     ("layout_pool.hip", []),
     ("detect_nms.hip", ["-ffp-contract=off"]),
     ("val_edge.hip", ["-ffp-contract=off"]),
+    ("batch_edge.hip", ["-ffp-contract=off"]),
     ("val_stats.hip", ["-ffp-contract=off"]),
     ("autoanchor.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),

@@ -6,6 +6,7 @@
 //     thresholds) "correct" matrix behind mAP --
 // for the whole batch in one launch each, reading the batched NMS output (bs, max_det, 6) + counts where it lies.
 // fp32 arithmetic in the reference's operation order (built with -ffp-contract=off; IEEE division as torch's CPU kernels).
+#include "y3_bilinear.h"
 #include "y3_common.h"
 
 namespace {
@@ -155,13 +156,8 @@ template <typename T> __global__ __launch_bounds__(256) void scale_img_kernel(co
     int y0 = 0, x0 = 0, y1 = 0, x1 = 0;
     float ly = 0.f, lx = 0.f;
     if (inside) {
-        // scale * (o + 0.5) - 0.5 as ONE fused multiply-add, like torch's kernels (the file is built with -ffp-contract=off; two roundings move the
-        // weights by an ulp of the index: 1.7e-6 on the goldens instead of 1.2e-7)
-        const float sy = fmaxf(fmaf(a.rh, (float)oy + 0.5f, -0.5f), 0.0f), sx = fmaxf(fmaf(a.rw, (float)ox + 0.5f, -0.5f), 0.0f);
-        y0 = (int)sy; x0 = (int)sx;
-        y1 = y0 + (y0 < a.h - 1 ? 1 : 0);
-        x1 = x0 + (x0 < a.w - 1 ? 1 : 0);
-        ly = sy - (float)y0; lx = sx - (float)x0;
+        y3_bilinear_tap(a.rh, oy, a.h, y0, y1, ly);   // (y3_bilinear.h: the one definition of torch's source index and weight)
+        y3_bilinear_tap(a.rw, ox, a.w, x0, x1, lx);
         if (a.flip) { x0 = a.w - 1 - x0; x1 = a.w - 1 - x1; }   // the mirrored image's column j is column w - 1 - j of the source
     }
     const float hy = 1.0f - ly, hx = 1.0f - lx;
@@ -173,7 +169,7 @@ template <typename T> __global__ __launch_bounds__(256) void scale_img_kernel(co
             const T* s = src + (long long)pl * a.h * a.w;
             const float v00 = to_f32<T>(s[(long long)y0 * a.w + x0]), v01 = to_f32<T>(s[(long long)y0 * a.w + x1]);
             const float v10 = to_f32<T>(s[(long long)y1 * a.w + x0]), v11 = to_f32<T>(s[(long long)y1 * a.w + x1]);
-            v = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+            v = y3_bilinear_mix(hy, hx, ly, lx, v00, v01, v10, v11);
         }
         dst[((long long)pl * a.oh + oy) * a.ow + ox] = from_f32<T>(v);
     }

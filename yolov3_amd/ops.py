@@ -569,6 +569,45 @@ def scale_img(img: torch.Tensor, ratio: float = 1.0, same_shape: bool = False, g
     return out
 
 
+def resize_bilinear(x: torch.Tensor, size, out_dtype: torch.dtype | None = None, div: float = 1.0) -> torch.Tensor:
+    """F.interpolate(x.float() / div, size=size, mode="bilinear", align_corners=False) rounded once to out_dtype, in one launch (reference train.py:380 + 399):
+    (n, c, h, w) uint8 / float32 / float16 / bfloat16 -> (n, c, size[0], size[1]) in out_dtype (default: x's dtype, float32 for uint8)."""
+    require_gpu(x, "resize_bilinear")
+    if x.dim() != 4 or x.dtype not in (torch.uint8, torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError("resize_bilinear expects a uint8 or floating (n, c, h, w) batch")
+    if out_dtype is None:
+        out_dtype = torch.float32 if x.dtype == torch.uint8 else x.dtype
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"resize_bilinear writes float32 / float16 / bfloat16, not {out_dtype}")
+    oh, ow = (int(s) for s in size)
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    out = torch.empty(n, c, oh, ow, dtype=out_dtype, device=x.device)
+    if n == 0:   # (an empty tensor has no address to hand over)
+        return out
+    check(_lib.lib().y3_resize_bilinear(x.data_ptr(), dtype_code(x.dtype), n, c, h, w, out.data_ptr(), dtype_code(out_dtype), oh, ow, float(div), stream_ptr()), "y3_resize_bilinear")
+    return out
+
+
+def quad_collate_u8(x: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """The image half of the reference's collate_fn4 (utils/dataloaders.py:842-853) in one launch: uint8 (bs, c, h, w), bs % 4 == 0, and bs / 4 uint8 flags on the
+    device -> uint8 (bs / 4, c, 2h, 2w); group g is the bilinear x2 upsample of image 4g where flags[g] is set, the 2x2 tile of images 4g .. 4g+3 otherwise."""
+    require_gpu(x, "quad_collate_u8")
+    require_gpu(flags, "quad_collate_u8")
+    if x.dim() != 4 or x.dtype != torch.uint8:
+        raise TypeError("quad_collate_u8 expects a uint8 (bs, c, h, w) batch")
+    bs, c, h, w = x.shape
+    if bs % 4:
+        raise ValueError(f"quad_collate_u8: batch size {bs} is not a multiple of 4")
+    if flags.dtype != torch.uint8 or flags.dim() != 1 or flags.numel() != bs // 4 or flags.device != x.device:
+        raise TypeError(f"quad_collate_u8 expects {bs // 4} uint8 flags on {x.device}")
+    x, flags = x.contiguous(), flags.contiguous()
+    out = torch.empty(bs // 4, c, 2 * h, 2 * w, dtype=torch.uint8, device=x.device)
+    if bs:
+        check(_lib.lib().y3_quad_collate_u8(x.data_ptr(), bs, c, h, w, flags.data_ptr(), out.data_ptr(), stream_ptr()), "y3_quad_collate_u8")
+    return out
+
+
 def descale_pred_into(pred: torch.Tensor, row0: int, nrows: int, scale: float, flip, img_size, out: torch.Tensor, out_row0: int):
     """rows [row0, row0 + nrows) of the decoded prediction (bs, rows, no) of one augmentation pass, de-scaled / de-mirrored (reference models/yolo.py:253-267),
     into rows [out_row0, ...) of the concatenated result."""
