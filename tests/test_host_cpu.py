@@ -605,6 +605,51 @@ def test_wgrad_dispatch_table_is_unchanged(lib, golden_dir):
     assert not wrong, f"{len(wrong)} of {len(rows)} rows differ, the first: {wrong[:3]}"
 
 
+def test_conv_dispatch_table_is_unchanged(lib, golden_dir):
+    """y3_conv2d_fwd_variant, y3_conv2d_fwd_stats_rows[_ws], y3_conv_v10_tiles and y3_conv2d_fwd_bnin_rows answer, row for row, what the commit before the
+    single-source conv dispatch answered (tests/golden/conv_dispatch.json, written by make_conv_dispatch_golden.py from THAT commit's library): every model conv and
+    its data gradient at four batch sizes and two map sizes, both sides of every threshold, a batch launched as several image ranges, fp32, every conv knob on rows
+    it changes, all thirteen variant names."""
+    import json
+
+    from yolov3_amd import _lib
+
+    table = json.loads((golden_dir / "conv_dispatch.json").read_text())
+    rows, names = table["rows"], table["variants"]
+    assert len(rows) >= 1000 and len(names) == 13 and all(sum(1 for r in rows if r[13] == v) >= 5 for v in range(13))
+    assert all(any(r[0] == ki for r in rows) for ki in range(len(table["knob_sets"])))
+    ws_bytes = lib.y3_conv_workspace_bytes()
+    name, nt, cb, gb = C.create_string_buffer(64), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    wrong, current = [], None
+    try:
+        for ki, dtype, k, s, cin, cout, n, h, w, dil, ups, res, ws, *want in rows:
+            if ki != current:
+                lib.y3_tune_reset()
+                for key, val in table["knob_sets"][ki].items():
+                    assert lib.y3_tune_set(key.encode(), val) == 0, key
+                current = ki
+            if dil == 2:   # the data gradient of a stride-2 layer: (h, w) is the output, x its stride-2 image
+                x, y = _lib.Y3Tensor(4096, n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, cin, cin), _lib.Y3Tensor(8192, n, h, w, cout, cout)
+            else:
+                ho, wo = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
+                x, y = _lib.Y3Tensor(4096, n, h, w, cin, cin), _lib.Y3Tensor(8192, n, ho * (2 if ups else 1), wo * (2 if ups else 1), cout, cout)
+            d, wsb = _lib.Y3ConvDesc(dtype, k, s, 0, ups, 0, cin, cout, dil), ws_bytes if ws else 0
+            assert lib.y3_conv2d_fwd_variant(C.byref(d), C.byref(x), C.byref(y), res, wsb, name, 64) == 0, lib.y3_last_error()
+            got = [names.index(name.value.decode()), lib.y3_conv2d_fwd_stats_rows_ws(C.byref(d), C.byref(x), C.byref(y), wsb) if ws else
+                   lib.y3_conv2d_fwd_stats_rows(C.byref(d), C.byref(x), C.byref(y)), None, None]
+            if want[2] is not None:
+                assert lib.y3_conv_v10_tiles(C.byref(d), C.byref(x), C.byref(y), wsb, None, 0, C.byref(nt), C.byref(cb), C.byref(gb)) == 0, lib.y3_last_error()
+                got[2] = [nt.value, cb.value, gb.value]
+            if want[3] is not None:
+                yin = _lib.Y3Tensor(12288, n, h, w, cin, cin)
+                got[3] = [lib.y3_conv2d_fwd_bnin_rows(C.byref(d), C.byref(x), C.byref(yin), C.byref(y), sc) for sc in (0, 1)]
+            if got != want:
+                wrong.append((table["knob_sets"][ki], dtype, (k, s, cin, cout, n, h, w, dil, ups, res, ws), want, got))
+    finally:
+        lib.y3_tune_reset()
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ, the first: {wrong[:3]}"
+
+
 def test_wgrad_last_plan_is_declared_bound_exported_and_fails_before_a_launch(lib):
     """y3_conv2d_wgrad_last_plan (the decision of the thread's last successful y3_conv2d_wgrad): in the header, the bindings and the library; on a thread that has
     launched nothing it fails and says so under its own name; null outputs are refused"""

@@ -56,7 +56,6 @@ struct ConvArgs {
     // pixel-wave index) of `stats` ([rows][Cout][2] fp32); a fixed-order fp64 sum over the rows follows (train.hip)
     float* stats;
     int stat_wp;   // waves along the pixel axis of the launched variant
-    int dry;       // geometry only (y3_conv2d_fwd_stats_rows): fill n_pt / stat_wp, launch nothing
     void* ws;      // the caller's scratch (y3_conv2d_fwd_ws): fp32 slabs of the K-split form of conv_v10.h; may be null
     size_t ws_bytes;
     int v10_S;     // conv_v10.h SPLIT form: slices of the channel blocks
@@ -85,7 +84,7 @@ static unsigned long long* g_timeline = nullptr;
 #define Y3_STAMP(i) do { } while (0)
 #endif
 
-static thread_local const char* g_last_variant = "";   // kernel variant the last dispatch on this thread chose (y3_conv2d_fwd_variant)
+static thread_local const char* g_last_variant = "";   // kernel variant of the last launch on this thread (y3_conv_last_variant); written by launch_begin and the two quad launches only
 
 template <typename T> struct Mfma;
 template <> struct Mfma<f16_t> {
@@ -897,55 +896,38 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v6_kernel(const ConvArgs p)
 #endif
 }
 
-template <typename T> int launch_v6(ConvArgs& a, hipStream_t st) {
-    a.n_ct = y3_ceil_div(a.Cout, 256);
-    a.n_pt = y3_ceil_div(a.M, 256);
+// The launch helpers (this file, conv_v10.h, conv_strip.h, conv_1x1s.h) run on a ConvArgs whose n_ct / n_pt / stat_wp conv_launch has copied from the plan: they fill
+// the rest of the kernel-visible geometry and launch.  None of them plans.
+static void tile_fill(ConvArgs& a, int bk) {   // the uniform-tap tile kernels (v6, v3, v2 with Cin % BK == 0)
     set_divisors(a);
-    a.cin_blocks = a.Cin / 32;
+    a.cin_blocks = a.Cin / bk;
     a.nk = a.ntaps * a.cin_blocks;
-    const long long nb = (long long)a.n_ct * a.n_pt;
-    if (nb > 0x7fffffffLL) Y3_FAIL("conv grid too large");
-    a.stat_wp = 2;
-    g_last_variant = "v6";
-    if (a.dry) return 0;
-    if (y3_knob(Y3K_CONV_AHEAD) == 2) hipLaunchKernelGGL((conv_igemm_v6_kernel<T, 2>), dim3((unsigned)nb), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv_igemm_v6_kernel<T, 3>), dim3((unsigned)nb), dim3(512), 0, st, a);
+}
+template <typename T> int launch_v6(ConvArgs& a, hipStream_t st) {
+    tile_fill(a, 32);
+    const dim3 grid((unsigned)(a.n_ct * a.n_pt));
+    if (y3_knob(Y3K_CONV_AHEAD) == 2) hipLaunchKernelGGL((conv_igemm_v6_kernel<T, 2>), grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((conv_igemm_v6_kernel<T, 3>), grid, dim3(512), 0, st, a);
     Y3_CHECK_LAUNCH();
     return 0;
 }
-
-// set by y3_conv2d_dgrad_s2 around the dispatch of its last class: the four classes' arguments (same Cout, M and channel counts;
-// only the filter bank, the tap table and the output parity differ) go out as ONE launch of the variant picked for that class
-static thread_local ConvArgs* g_quad = nullptr;
-static thread_local bool g_quad_done = false;
-
-template <typename T, int BK, int MC, int MP> void geometry_v3(ConvArgs& a) {
-    constexpr int TC = 2 * MC * 32, TP = 2 * MP * 32;
-    a.n_ct = y3_ceil_div(a.Cout, TC);
-    a.n_pt = y3_ceil_div(a.M, TP);
-    set_divisors(a);
-    a.cin_blocks = a.Cin / BK;
-    a.nk = a.ntaps * a.cin_blocks;
-    a.stat_wp = 2;
-}
-template <typename T, int BK, int MC, int MP> int launch_v3(ConvArgs& a, hipStream_t st) {
-    geometry_v3<T, BK, MC, MP>(a);
-    const long long nb = (long long)a.n_ct * a.n_pt;
-    if (nb > 0x7fffffffLL) Y3_FAIL("conv grid too large");
-    g_last_variant = BK == 64 ? "v3_bk64_128x128" : (MC == 1 ? "v3_bk32_64x256" : (MP == 4 ? "v3_bk32_128x256" : "v3_bk32_128x128"));
-    if (a.dry) return 0;
-    if (g_quad && (nb + 7) / 8 * 32 <= 0x7fffffffLL) {
+// `quad`: the four parity classes of a stride-2 data gradient (same Cout, M and channel counts; only the filter bank, the tap table and the output parity differ) go
+// out as ONE launch on the tile grid of `a`, the class with the most taps
+template <typename T, int BK, int MC, int MP> int launch_v3(ConvArgs& a, const ConvArgs* quad, hipStream_t st) {
+    if (quad) {
         ConvArgs4 q;
         for (int i = 0; i < 4; ++i) {
-            q.a[i] = g_quad[i];
-            geometry_v3<T, BK, MC, MP>(q.a[i]);
+            q.a[i] = quad[i];
+            q.a[i].n_ct = a.n_ct; q.a[i].n_pt = a.n_pt; q.a[i].stat_wp = a.stat_wp;
+            tile_fill(q.a[i], BK);
         }
+        const long long nb = (long long)a.n_ct * a.n_pt;
         hipLaunchKernelGGL((conv_igemm_v3_quad_kernel<T, BK, MC, MP>), dim3((unsigned)((nb + 7) / 8 * 32)), dim3(256), 0, st, q, (int)nb);
         Y3_CHECK_LAUNCH();
-        g_quad_done = true;
         return 0;
     }
-    hipLaunchKernelGGL((conv_igemm_v3_kernel<T, BK, MC, MP>), dim3((unsigned)nb), dim3(256), 0, st, a);
+    tile_fill(a, BK);
+    hipLaunchKernelGGL((conv_igemm_v3_kernel<T, BK, MC, MP>), dim3((unsigned)(a.n_ct * a.n_pt)), dim3(256), 0, st, a);
     Y3_CHECK_LAUNCH();
     return 0;
 }
@@ -1010,23 +992,12 @@ __global__ void pack_filter_kernel(const float* __restrict__ src, int cout_src, 
 
 template <typename T, int BK, int WAVES_C, int WAVES_P, int MC, int MP, bool SMALLC>
 int launch_igemm(ConvArgs& a, hipStream_t st) {
-    constexpr int TC = WAVES_C * MC * 32, TP = WAVES_P * MP * 32;
-    a.n_ct = y3_ceil_div(a.Cout, TC);
-    a.n_pt = y3_ceil_div(a.M, TP);
-    set_divisors(a);
+    tile_fill(a, BK);
     if (SMALLC) {
         a.nk = y3_ceil_div(a.ntaps * a.Cin, BK);
         a.cin_blocks = 1;
-    } else {
-        a.cin_blocks = a.Cin / BK;
-        a.nk = a.ntaps * a.cin_blocks;
     }
-    const long long nb = (long long)a.n_ct * a.n_pt;
-    if (nb > 0x7fffffffLL) Y3_FAIL("conv grid too large");
-    a.stat_wp = WAVES_P;
-    g_last_variant = SMALLC ? "v2_smallc" : "v2";
-    if (a.dry) return 0;
-    hipLaunchKernelGGL((conv_igemm_v2_kernel<T, BK, WAVES_C, WAVES_P, MC, MP, SMALLC>), dim3((unsigned)nb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_v2_kernel<T, BK, WAVES_C, WAVES_P, MC, MP, SMALLC>), dim3((unsigned)(a.n_ct * a.n_pt)), dim3(256), 0, st, a);
     Y3_CHECK_LAUNCH();
     return 0;
 }
@@ -1041,57 +1012,84 @@ template <int N, typename F> Y3_DEV void static_for(F&& f) { static_for_impl(f, 
 #include "conv_strip.h"
 #include "conv_1x1s.h"
 
-template <typename T> int dispatch_igemm(ConvArgs& a, hipStream_t st) {
+// ---- the dispatch: ONE decision (conv_decide), read by the queries and the launch ----
+// The question is the filled ConvArgs of one image range (geometry and tap table, byte extents, presence of bias / residual / workspace, the input transform); the
+// answer is a ConvPlan.  conv_decide is pure: it reads the arguments, the knobs and y3_cu_count() and writes nothing but the plan.
+enum ConvForm { CF_DIRECT, CF_V2, CF_V3_BK64, CF_V3_128X128, CF_V3_128X256, CF_V3_64X256, CF_V6, CF_V10, CF_V10K, CF_STRIP, CF_S1 };
+struct V3Tile { const char* name; int tc, tp; };   // filters x pixels of the block tile, by form - CF_V3_BK64
+constexpr V3Tile V3_TILES[4] = {{"v3_bk64_128x128", 128, 128}, {"v3_bk32_128x128", 128, 128}, {"v3_bk32_128x256", 128, 256}, {"v3_bk32_64x256", 64, 256}};
+struct V2Tile { int wc, wp, mc, mp; };   // waves and 32-wide MFMA tiles per wave along filters / pixels: > 64, > 32 and <= 32 filters
+constexpr V2Tile V2_TILES[3] = {{2, 2, 2, 2}, {1, 4, 2, 1}, {1, 4, 1, 2}};
+struct ConvPlan {
+    ConvForm form;             // (the four v3 tiles are four forms)
+    const char* name;          // what y3_conv2d_fwd_variant and y3_conv_last_variant report
+    int tile;                  // CF_V2: 3 * (index into V2_TILES) + (0: BK 64, 1: BK 32, 2: BK 32 with Cin % 32 != 0)
+    int n_pt, n_ct, stat_wp;   // the launch writes n_pt * stat_wp statistics rows
+    CsPlan cs;                 // the form's own plan: CF_STRIP, CF_S1, CF_V10 / CF_V10K
+    S1Plan s1;
+    V10Plan v10;
+    int64_t rows() const { return (int64_t)n_pt * stat_wp; }
+    bool is_v3() const { return form >= CF_V3_BK64 && form <= CF_V3_64X256; }
+};
+
+static int plan_set(ConvPlan& p, ConvForm form, const char* name, int n_ct, int n_pt, int stat_wp, int tile = 0) {
+    p.form = form; p.name = name; p.tile = tile;
+    p.n_ct = n_ct; p.n_pt = n_pt; p.stat_wp = stat_wp;
+    return 0;
+}
+static int plan_tile(const ConvArgs& a, ConvPlan& p, ConvForm form, const char* name, int tc, int tp, int stat_wp, int tile = 0) {   // tc filters x tp pixels per block
+    if ((long long)y3_ceil_div(a.Cout, tc) * y3_ceil_div(a.M, tp) > 0x7fffffffLL) Y3_FAIL("conv grid too large");
+    return plan_set(p, form, name, y3_ceil_div(a.Cout, tc), y3_ceil_div(a.M, tp), stat_wp, tile);
+}
+static int s1_in(const ConvArgs& a) { return a.in_scale ? (a.in_res ? 2 : 1) : 0; }
+// the s1 form of a plan whose p.s1 is filled: stages along the pixels, one statistics row per (pixel wave, epilogue pass) of a stage
+static int plan_s1(const ConvArgs& a, ConvPlan& p) { return plan_set(p, CF_S1, p.s1.in ? "s1x1_bn" : "s1x1", p.s1.n_ct, y3_ceil_div(a.M, p.s1.sp), p.s1.wp * p.s1.npass); }
+
+static int conv_decide(const ConvArgs& a, ConvPlan& p, bool direct = false) {
+    if (direct) return plan_set(p, CF_DIRECT, "direct", 0, 0, 0);   // fp32 / Y3_ALGO_DIRECT: one thread per output element
     const bool c64 = (a.Cin % 64) == 0, c32 = (a.Cin % 32) == 0;
     const int var = conv_variant();
+    auto v3 = [&](ConvForm f) { return plan_tile(a, p, f, V3_TILES[f - CF_V3_BK64].name, V3_TILES[f - CF_V3_BK64].tc, V3_TILES[f - CF_V3_BK64].tp, 2); };
+    auto v6 = [&]() { return plan_tile(a, p, CF_V6, "v6", 256, 256, 2); };
     if (!(a.x_bytes && a.w_bytes && a.y_bytes && (!a.res || a.r_bytes)))
         Y3_FAIL("conv: a tensor exceeds the 2 GiB reach of a buffer descriptor (split the batch)");
-    {
-        CsPlan cs;
-        if (var == 3 && cs_plan(a, cs)) return launch_cs<T>(a, st);
+    if (var == 3 && cs_plan(a, p.cs)) return plan_set(p, CF_STRIP, "strip", 1, p.cs.blocks, p.cs.mt * (a.Cin > 64 ? 2 : 1));   // one statistics row per block, pixel tile and K-split wave
+    if (var == 3 && s1_plan(a, p.s1, s1_in(a))) return plan_s1(a, p);   // HBM-bound 1x1 layers: persistent blocks, filters in registers (conv_1x1s.h)
+    if (var == 3 && v10_shape_ok(a)) {
+        // conv_v10.h: a quarter round of tiles or more takes the tile form (statistics rows per tile: one per 64-pixel epilogue pass of the widest body, narrower bodies
+        // write zero rows), smaller launches with a workspace the K-split form (one row per 64-pixel block of the slab sum); knob v10_ksplit = 2: the K-split form on
+        // any eligible launch (tests)
+        const long long ksplit = y3_knob(Y3K_V10_KSPLIT);
+        const bool big = v10_big_enough(a);
+        if (ksplit == 2 && v10k_plan(a, p.v10)) return plan_set(p, CF_V10K, "v10k", a.Cout / 256, y3_ceil_div(a.M, 64), 1);
+        if (big && v10_plan(a, p.v10)) return plan_set(p, CF_V10, p.v10.half ? "v10h" : "v10", a.Cout / 256, p.v10.n_tiles, 4);
+        if (ksplit != 0 && ksplit != 2 && !big && v10k_plan(a, p.v10)) return plan_set(p, CF_V10K, "v10k", a.Cout / 256, y3_ceil_div(a.M, 64), 1);
     }
-    {
-        S1Plan s1;
-        if (var == 3 && s1_plan(a, s1)) return launch_s1<T>(a, s1, st);   // HBM-bound 1x1 layers: persistent blocks, filters in registers (conv_1x1s.h)
-    }
-    if (var == 3 && y3_knob(Y3K_V10_KSPLIT) == 2 && v10k_eligible(a)) return launch_v10k<T>(a, st);   // (tests: the K-split form on any eligible launch)
-    if (var == 3 && v10_eligible(a)) return launch_v10<T>(a, st);
-    if (var == 3 && v10k_eligible(a)) return launch_v10k<T>(a, st);
     if (var >= 3 && a.Cout > 64 && c32) {
         // forced tiles (knob "conv", A/B runs)
-        if (var == 4) return launch_v3<T, 32, 2, 4>(a, st);   // 128c x 256p, BK 32
-        if (var == 5) return launch_v3<T, 32, 2, 2>(a, st);   // 128c x 128p, BK 32 (4 blocks / CU)
-        if (var == 6) return c64 ? launch_v3<T, 64, 2, 2>(a, st) : launch_v3<T, 32, 2, 2>(a, st);
-        if (var == 15 && a.Cout >= 256) return launch_v6<T>(a, st);
+        if (var == 4) return v3(CF_V3_128X256);   // 128c x 256p, BK 32
+        if (var == 5) return v3(CF_V3_128X128);   // 128c x 128p, BK 32 (4 blocks / CU)
+        if (var == 6) return v3(c64 ? CF_V3_BK64 : CF_V3_128X128);
+        if (var == 15 && a.Cout >= 256) return v6();
         // auto (measured on MI355X, profiles/r01_conv_variants.md, r02_conv_variant_sweep.txt): long-K layers with >= 512 filters want
         // the 8-wave 256x256 tile (v6), short K loops want 4 resident blocks per CU (BK 32), small pixel counts with long K the
         // 128x256 tile, the rest the BK 64 128x128 tile.
         const int K = a.ntaps * a.Cin;
-        if (K >= 2304 && a.Cout >= 512) return launch_v6<T>(a, st);
-        if (K >= 4608 && a.Cout >= 256 && a.M >= 65536) return launch_v6<T>(a, st);   // data gradient of the 256 -> 512 layers (one filter tile)
-        if (c64 && a.ntaps == 1 && a.Cout >= 256 && a.M > 16384 && a.M <= 65536) return launch_v6<T>(a, st);   // 1x1 @40x40
-        if (c64 && ((a.ntaps > 1 && K >= 1152) || (a.ntaps == 1 && K >= 256 && a.M <= 16384))) return launch_v3<T, 64, 2, 2>(a, st);
+        if (K >= 2304 && a.Cout >= 512) return v6();
+        if (K >= 4608 && a.Cout >= 256 && a.M >= 65536) return v6();   // data gradient of the 256 -> 512 layers (one filter tile)
+        if (c64 && a.ntaps == 1 && a.Cout >= 256 && a.M > 16384 && a.M <= 65536) return v6();   // 1x1 @40x40
+        if (c64 && ((a.ntaps > 1 && K >= 1152) || (a.ntaps == 1 && K >= 256 && a.M <= 16384))) return v3(CF_V3_BK64);
         // 64 -> 128 3x3 @160x160 runs 5 % faster on the 128c x 256p tile, the stride-2 64 -> 128 layer 3 % faster with BK 64
-        if (c64 && a.ntaps > 1 && K == 576 && a.Cout == 128 && a.M >= 262144) return a.stride == 1 ? launch_v3<T, 32, 2, 4>(a, st) : launch_v3<T, 64, 2, 2>(a, st);
-        return launch_v3<T, 32, 2, 2>(a, st);
+        if (c64 && a.ntaps > 1 && K == 576 && a.Cout == 128 && a.M >= 262144) return v3(a.stride == 1 ? CF_V3_128X256 : CF_V3_BK64);
+        return v3(CF_V3_128X128);
     }
     // <= 64-filter layers with Cin % 32 == 0 also go to the LDS-DMA kernel (64c x 256p tile): measured 0.42 -> 0.36 ms on
     // 32->64 s2 @640x640 and 0.44 -> 0.38 ms on 32->64 @320x320 (bs 32)
-    if (var != 2 && a.Cout <= 64 && c32) return launch_v3<T, 32, 1, 4>(a, st);   // 64c x 256p, wave 32c x 128p
+    if (var != 2 && a.Cout <= 64 && c32) return v3(CF_V3_64X256);   // 64c x 256p, wave 32c x 128p
     // register-staged fallback: Cin % 32 != 0 (layer 0 when the stem kernel is not eligible)
-    if (a.Cout > 64) {
-        if (c64) return launch_igemm<T, 64, 2, 2, 2, 2, false>(a, st);
-        if (c32) return launch_igemm<T, 32, 2, 2, 2, 2, false>(a, st);
-        return launch_igemm<T, 32, 2, 2, 2, 2, true>(a, st);
-    } else if (a.Cout > 32) {
-        if (c64) return launch_igemm<T, 64, 1, 4, 2, 1, false>(a, st);
-        if (c32) return launch_igemm<T, 32, 1, 4, 2, 1, false>(a, st);
-        return launch_igemm<T, 32, 1, 4, 2, 1, true>(a, st);
-    } else {
-        if (c64) return launch_igemm<T, 64, 1, 4, 1, 2, false>(a, st);
-        if (c32) return launch_igemm<T, 32, 1, 4, 1, 2, false>(a, st);
-        return launch_igemm<T, 32, 1, 4, 1, 2, true>(a, st);
-    }
+    const int fc = a.Cout > 64 ? 0 : (a.Cout > 32 ? 1 : 2), kc = c64 ? 0 : (c32 ? 1 : 2);
+    const V2Tile& t = V2_TILES[fc];
+    return plan_tile(a, p, CF_V2, kc == 2 ? "v2_smallc" : "v2", t.wc * t.mc * 32, t.wp * t.mp * 32, t.wp, 3 * fc + kc);
 }
 
 template <typename T> int launch_direct(ConvArgs& a, hipStream_t st) {
@@ -1099,6 +1097,37 @@ template <typename T> int launch_direct(ConvArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((conv_direct_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
     Y3_CHECK_LAUNCH();
     return 0;
+}
+template <typename T, int F, int BK, bool SMALLC> int launch_v2(ConvArgs& a, hipStream_t st) {
+    return launch_igemm<T, BK, V2_TILES[F].wc, V2_TILES[F].wp, V2_TILES[F].mc, V2_TILES[F].mp, SMALLC>(a, st);
+}
+
+// the launch of a decided plan (f16 / bf16; the direct form: conv_launch_as): a switch into one helper per form.  Never plans.
+template <typename T> int conv_launch(ConvArgs& a, const ConvPlan& p, hipStream_t st, const ConvArgs* quad = nullptr) {
+    switch (p.form) {
+        case CF_STRIP: return launch_cs<T>(a, p.cs, st);
+        case CF_S1: return launch_s1<T>(a, p.s1, st);
+        case CF_V10K: return launch_v10k<T>(a, p.v10, st);
+        case CF_V10: return launch_v10<T>(a, p.v10, st);
+        case CF_V3_128X256: return launch_v3<T, 32, 2, 4>(a, quad, st);
+        case CF_V3_128X128: return launch_v3<T, 32, 2, 2>(a, quad, st);
+        case CF_V3_BK64: return launch_v3<T, 64, 2, 2>(a, quad, st);
+        case CF_V6: return launch_v6<T>(a, st);
+        case CF_V3_64X256: return launch_v3<T, 32, 1, 4>(a, quad, st);
+        case CF_V2:
+            switch (p.tile) {
+                case 0: return launch_v2<T, 0, 64, false>(a, st);
+                case 1: return launch_v2<T, 0, 32, false>(a, st);
+                case 2: return launch_v2<T, 0, 32, true>(a, st);
+                case 3: return launch_v2<T, 1, 64, false>(a, st);
+                case 4: return launch_v2<T, 1, 32, false>(a, st);
+                case 5: return launch_v2<T, 1, 32, true>(a, st);
+                case 6: return launch_v2<T, 2, 64, false>(a, st);
+                case 7: return launch_v2<T, 2, 32, false>(a, st);
+                default: return launch_v2<T, 2, 32, true>(a, st);
+            }
+        default: Y3_FAIL("conv: no launch for form %d (internal)", (int)p.form);
+    }
 }
 
 }  // namespace
@@ -1126,8 +1155,16 @@ extern "C" int y3_pack_filter(const float* w, int32_t cout_src, int32_t cin_src,
     return 0;
 }
 
-static int conv_fwd_impl(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* res, const y3_tensor* y, float* stats,
-                         int64_t stat_capacity_rows, int64_t* stat_rows, int dry, void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
+// ---- step 1: validate the call and fill the arguments of the whole batch and the image ranges it is launched as ----
+struct ConvProblem {
+    ConvArgs a;                     // the whole batch
+    const y3_tensor *x, *y, *res;   // (res may be null)
+    int dtype, esz, chunk;          // element bytes, images per range
+    bool direct;                    // fp32 / Y3_ALGO_DIRECT: the one-thread-per-element kernel
+    long long opx_img, img_x, img_y, img_r, wb;   // per image: output pixels, bytes of x / y / residual; bytes of the filter bank
+};
+static int conv_problem(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* res, const y3_tensor* y, bool stats, void* ws,
+                        size_t ws_bytes, ConvProblem& pb) {
     if (!d || !x || !filt || !bias || !y) Y3_FAIL("y3_conv2d_fwd: null argument");
     if (d->ksize != 1 && d->ksize != 3) Y3_FAIL("y3_conv2d_fwd: ksize %d unsupported", d->ksize);
     if (d->stride != 1 && d->stride != 2) Y3_FAIL("y3_conv2d_fwd: stride %d unsupported", d->stride);
@@ -1164,11 +1201,10 @@ static int conv_fwd_impl(const y3_conv_desc* d, const y3_tensor* x, const void* 
                 (long long)d->filter_elems, d->cout, d->cin, d->ksize, (unsigned long long)y3_packed_filter_elems(d->cout, d->cin, d->ksize));
     if ((long long)x->n * Ho * Wo * (d->upsample2x ? 4 : 1) > 0x7fffffffLL) Y3_FAIL("y3_conv2d_fwd: too many output pixels");
 
-    ConvArgs a;
+    ConvArgs& a = pb.a;
     memset(&a, 0, sizeof(a));
     a.x = x->data; a.w = filt; a.bias = bias; a.res = res ? res->data : nullptr; a.y = y->data;
     a.ws = ws; a.ws_bytes = ws ? ws_bytes : 0;
-    a.dry = dry && !stat_rows ? 1 : 0;
     a.N = x->n; a.H = x->h; a.W = x->w; a.Cin = d->cin; a.xpitch = x->pitch;
     a.Ho = Ho; a.Wo = Wo; a.Cout = d->cout; a.ypitch = y->pitch; a.rpitch = res ? res->pitch : 0;
     a.ks = d->ksize; a.stride = d->stride; a.pad = pad; a.act = d->act; a.ups = d->upsample2x ? 1 : 0;
@@ -1178,13 +1214,12 @@ static int conv_fwd_impl(const y3_conv_desc* d, const y3_tensor* x, const void* 
     a.oH = Ho; a.oW = Wo; a.omul = 1; a.ooh = 0; a.oow = 0;
     a.M = x->n * Ho * Wo;
     a.Kpad = y3_filter_kpad(d->cin, d->ksize);
-    hipStream_t st = (hipStream_t)stream;
 #ifdef Y3_TIMELINE
     a.tl = g_timeline;
 #endif
     int algo = d->algo;
     if (algo == Y3_ALGO_AUTO) algo = (d->dtype == Y3_F32) ? Y3_ALGO_DIRECT : Y3_ALGO_MFMA;
-    if (stat_rows) {
+    if (stats) {
         if (algo != Y3_ALGO_MFMA || d->dtype == Y3_F32) Y3_FAIL("y3_conv2d_fwd_stats: the epilogue statistics need the f16/bf16 MFMA path");
         if (d->upsample2x) Y3_FAIL("y3_conv2d_fwd_stats: upsample2x unsupported");
     }
@@ -1204,57 +1239,75 @@ static int conv_fwd_impl(const y3_conv_desc* d, const y3_tensor* x, const void* 
         while (chunk > 1 && ((long long)chunk * img_x >= LIM || (long long)chunk * img_y >= LIM || (long long)chunk * img_r >= LIM))
             chunk = (chunk + 1) / 2;
     }
+    pb.x = x; pb.y = y; pb.res = res;
+    pb.dtype = d->dtype; pb.esz = esz; pb.chunk = chunk; pb.direct = algo != Y3_ALGO_MFMA;
+    pb.opx_img = opx_img; pb.img_x = img_x; pb.img_y = img_y; pb.img_r = img_r; pb.wb = wb;
+    return 0;
+}
+// the arguments of the image range that starts at image n0
+static ConvArgs conv_range(const ConvProblem& pb, int n0) {
+    const y3_tensor *x = pb.x, *y = pb.y, *res = pb.res;
+    const int esz = pb.esz;
+    const ConvArgs& a = pb.a;
+    ConvArgs c = a;
+    c.N = x->n - n0 < pb.chunk ? x->n - n0 : pb.chunk;
+    c.M = c.N * a.Ho * a.Wo;
+    c.x = (const char*)a.x + (long long)n0 * pb.img_x;
+    c.y = (char*)a.y + (long long)n0 * pb.img_y;
+    if (res) c.res = (const char*)a.res + (long long)n0 * pb.img_r;
+    const long long xb = (((long long)c.N * x->h * x->w - 1) * x->pitch + x->c) * esz;
+    const long long yb = (((long long)c.N * pb.opx_img - 1) * y->pitch + y->c) * esz, rb = res ? (((long long)c.N * pb.opx_img - 1) * res->pitch + res->c) * esz : 0;
+    c.x_bytes = xb < 0x7fffffffLL ? (unsigned)xb : 0u;   // only the fp32 direct kernel (64-bit indexing) ever sees a 0 here
+    c.w_bytes = (unsigned)pb.wb;
+    c.y_bytes = yb < 0x7fffffffLL ? (unsigned)yb : 0u;
+    c.r_bytes = rb < 0x7fffffffLL ? (unsigned)rb : 0u;
+    return c;
+}
+
+// ---- step 3: the launch of a plan.  Every launch starts here: the plan's geometry into the kernel arguments, its name into the record behind y3_conv_last_variant
+static void launch_begin(ConvArgs& a, const ConvPlan& p) {
+    a.n_ct = p.n_ct; a.n_pt = p.n_pt; a.stat_wp = p.stat_wp;
+    g_last_variant = p.name;
+}
+static int conv_launch_as(int dtype, ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    launch_begin(a, p);
+    if (p.form != CF_DIRECT) {
+        if (dtype == Y3_F16) return conv_launch<f16_t>(a, p, st);
+        if (dtype == Y3_BF16) return conv_launch<bf16_t>(a, p, st);
+        Y3_FAIL("y3_conv2d_fwd: MFMA path needs f16/bf16");
+    }
+    switch (dtype) {
+        case Y3_F16: return launch_direct<f16_t>(a, st);
+        case Y3_BF16: return launch_direct<bf16_t>(a, st);
+        case Y3_F32: return launch_direct<float>(a, st);
+        default: Y3_FAIL("y3_conv2d_fwd: bad dtype %d", dtype);
+    }
+}
+
+// validate and fill; per image range decide ONCE (step 2: a statistics launch takes its rows from that plan) and launch that plan
+static int conv_fwd_impl(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* res, const y3_tensor* y, float* stats,
+                         int64_t stat_capacity_rows, int64_t* stat_rows, void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
+    ConvProblem pb;
+    if (const int rc = conv_problem(d, x, filt, bias, res, y, stat_rows != nullptr, ws, ws_bytes, pb)) return rc;
     if (stat_rows) *stat_rows = 0;
-    int64_t rows_done = 0;
-    for (int n0 = 0; n0 < x->n; n0 += chunk) {
-        ConvArgs c = a;
-        c.N = x->n - n0 < chunk ? x->n - n0 : chunk;
-        c.M = c.N * Ho * Wo;
-        c.x = (const char*)a.x + (long long)n0 * img_x;
-        c.y = (char*)a.y + (long long)n0 * img_y;
-        if (res) c.res = (const char*)a.res + (long long)n0 * img_r;
-        const long long xb = (((long long)c.N * x->h * x->w - 1) * x->pitch + x->c) * esz;
-        const long long yb = (((long long)c.N * opx_img - 1) * y->pitch + y->c) * esz, rb = res ? (((long long)c.N * opx_img - 1) * res->pitch + res->c) * esz : 0;
-        c.x_bytes = xb < 0x7fffffffLL ? (unsigned)xb : 0u;   // only the fp32 direct kernel (64-bit indexing) ever sees a 0 here
-        c.w_bytes = (unsigned)wb;
-        c.y_bytes = yb < 0x7fffffffLL ? (unsigned)yb : 0u;
-        c.r_bytes = rb < 0x7fffffffLL ? (unsigned)rb : 0u;
-        if (stat_rows) {   // BatchNorm statistics in the epilogue: a dry pass of the dispatcher decides the rows of this launch
-            ConvArgs g = c;
-            g.dry = 1;
-            const int rc = d->dtype == Y3_F16 ? dispatch_igemm<f16_t>(g, st) : dispatch_igemm<bf16_t>(g, st);
-            if (rc) return rc;
-            const int64_t rows = (int64_t)g.n_pt * g.stat_wp;
-            *stat_rows += rows;
-            if (dry) continue;
-            if (!stats || stat_capacity_rows < rows_done + rows)
-                Y3_FAIL("y3_conv2d_fwd_stats: statistics buffer holds %lld rows, the launch writes %lld", (long long)stat_capacity_rows, (long long)(rows_done + rows));
-            c.stats = stats + rows_done * (int64_t)d->cout * 2;
-            rows_done += rows;
+    for (int n0 = 0; n0 < pb.a.N; n0 += pb.chunk) {
+        ConvArgs c = conv_range(pb, n0);
+        ConvPlan p;
+        if (const int rc = conv_decide(c, p, pb.direct)) return rc;
+        if (stat_rows) {   // BatchNorm statistics in the epilogue
+            const int64_t rows_done = *stat_rows;
+            *stat_rows += p.rows();
+            if (!stats || stat_capacity_rows < *stat_rows)
+                Y3_FAIL("y3_conv2d_fwd_stats: statistics buffer holds %lld rows, the launch writes %lld", (long long)stat_capacity_rows, (long long)*stat_rows);
+            c.stats = stats + rows_done * (int64_t)c.Cout * 2;
         }
-        int rc;
-        if (algo == Y3_ALGO_MFMA) {
-            if (d->dtype == Y3_F16) rc = dispatch_igemm<f16_t>(c, st);
-            else if (d->dtype == Y3_BF16) rc = dispatch_igemm<bf16_t>(c, st);
-            else Y3_FAIL("y3_conv2d_fwd: MFMA path needs f16/bf16");
-        } else {
-            g_last_variant = "direct";
-            if (c.dry) return 0;
-            switch (d->dtype) {
-                case Y3_F16: rc = launch_direct<f16_t>(c, st); break;
-                case Y3_BF16: rc = launch_direct<bf16_t>(c, st); break;
-                case Y3_F32: rc = launch_direct<float>(c, st); break;
-                default: Y3_FAIL("y3_conv2d_fwd: bad dtype %d", d->dtype);
-            }
-        }
-        if (rc) return rc;
-        if (c.dry) return 0;   // variant query: the first image range decides
+        if (const int rc = conv_launch_as(pb.dtype, c, p, (hipStream_t)stream)) return rc;
     }
     return 0;
 }
 
 extern "C" int y3_conv2d_fwd(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* res, const y3_tensor* y, void* stream) {
-    return conv_fwd_impl(d, x, filt, bias, res, y, nullptr, 0, nullptr, 0, stream);
+    return conv_fwd_impl(d, x, filt, bias, res, y, nullptr, 0, nullptr, stream);
 }
 
 // ---- the same convolution with a scratch buffer: unlocks the K-split form of conv_v10.h for small launches ----
@@ -1264,34 +1317,53 @@ extern "C" size_t y3_conv_workspace_bytes(void) { return Y3_CONV_WS_BYTES; }
 extern "C" int y3_conv2d_fwd_ws(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* res, const y3_tensor* y, void* workspace,
                                 size_t workspace_bytes, void* stream) {
     if (workspace && ((uintptr_t)workspace & 255)) Y3_FAIL("y3_conv2d_fwd_ws: the workspace must be 256-byte aligned");
-    return conv_fwd_impl(d, x, filt, bias, res, y, nullptr, 0, nullptr, 0, stream, workspace, workspace_bytes);
+    return conv_fwd_impl(d, x, filt, bias, res, y, nullptr, 0, nullptr, stream, workspace, workspace_bytes);
 }
 
-// name of the kernel variant the dispatcher picks for this problem (nothing is launched): "v7", "v6", "v3_bk64_128x128", ...
+// ---- the queries: validate, fill and decide as the launch does, then read the plan (nothing is launched, nothing recorded) ----
+alignas(256) static const float g_dummy[64] = {0.0f};   // stands for filter bank, bias, residual and workspace: never dereferenced
+// the plan (and arguments) of the first image range; with `rows`, the statistics rows summed over all ranges
+static int conv_query(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y, int32_t has_residual, size_t ws_bytes, ConvArgs& c0, ConvPlan& p0, int64_t* rows) {
+    y3_tensor r;
+    if (has_residual && y) { r = *y; if (d && d->upsample2x) { r.h /= 2; r.w /= 2; } r.data = (void*)g_dummy; }
+    ConvProblem pb;
+    if (const int rc = conv_problem(d, x, (const void*)g_dummy, g_dummy, has_residual ? &r : nullptr, y, rows != nullptr, ws_bytes ? (void*)g_dummy : nullptr, ws_bytes, pb)) return rc;
+    if (rows) *rows = 0;
+    if (pb.a.N < 1) return plan_set(p0, CF_DIRECT, "direct", 0, 0, 0);   // an empty batch launches nothing
+    c0 = conv_range(pb, 0);
+    if (const int rc = conv_decide(c0, p0, pb.direct)) return rc;
+    if (!rows) return 0;
+    *rows = p0.rows();
+    for (int n0 = pb.chunk; n0 < pb.a.N; n0 += pb.chunk) {
+        ConvPlan p;
+        if (const int rc = conv_decide(conv_range(pb, n0), p, pb.direct)) return rc;
+        *rows += p.rows();
+    }
+    return 0;
+}
+
+// name of the kernel variant the dispatcher picks for this problem: "direct", "v2", "v2_smallc", "v3_bk64_128x128", "v6", "v10", "v10h", "v10k", "strip", "s1x1", ...
+// (a batch launched as several image ranges: the first range's)
 extern "C" int y3_conv2d_fwd_variant(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y, int32_t has_residual, size_t workspace_bytes, char* name, size_t name_cap) {
     if (!name || name_cap < 2) Y3_FAIL("y3_conv2d_fwd_variant: no room for the name");
-    alignas(256) static const float dummy[64] = {0.0f};   // geometry only: never dereferenced
-    y3_tensor r;
-    if (has_residual && y) { r = *y; if (d && d->upsample2x) { r.h /= 2; r.w /= 2; } r.data = (void*)dummy; }
-    g_last_variant = "direct";
-    const int rc = conv_fwd_impl(d, x, (const void*)dummy, dummy, has_residual ? &r : nullptr, y, nullptr, 0, nullptr, 1, nullptr, workspace_bytes ? (void*)dummy : nullptr, workspace_bytes);
-    if (rc) return rc;
-    strncpy(name, g_last_variant, name_cap - 1);
+    ConvArgs a;
+    ConvPlan p;
+    if (const int rc = conv_query(d, x, y, has_residual, workspace_bytes, a, p, nullptr)) return rc;
+    strncpy(name, p.name, name_cap - 1);
     name[name_cap - 1] = 0;
     return 0;
 }
 
-// The tiles of the persistent 3x3 kernel for this problem, as its blocks compute them (nothing is launched): one record (block of the filter tile, tile of the block,
+// The tiles of the persistent 3x3 kernel for this problem, as its blocks compute them: one record (block of the filter tile, tile of the block,
 // first 32-pixel column block, column blocks) per tile of ONE filter tile, from the very functions the kernel runs (v10_share / v10_tile_cols, conv_v10.h)
 extern "C" int y3_conv_v10_tiles(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y, size_t workspace_bytes, int32_t* records, int64_t capacity, int64_t* n_tiles,
                                  int32_t* column_blocks, int32_t* group_blocks) {
     if (!n_tiles) Y3_FAIL("y3_conv_v10_tiles: null argument");
-    alignas(256) static const float dummy[64] = {0.0f};   // geometry only: never dereferenced
-    g_v10_dry_valid = false;
-    const int rc = conv_fwd_impl(d, x, (const void*)dummy, dummy, nullptr, y, nullptr, 0, nullptr, 1, nullptr, workspace_bytes ? (void*)dummy : nullptr, workspace_bytes);
-    if (rc) return rc;
-    if (!g_v10_dry_valid) Y3_FAIL("y3_conv_v10_tiles: the dispatcher picks '%s' for this problem, not conv_v10.h", g_last_variant);
-    const ConvArgs& a = g_v10_dry;
+    ConvArgs a;
+    ConvPlan p;
+    if (const int rc = conv_query(d, x, y, 0, workspace_bytes, a, p, nullptr)) return rc;
+    if (p.form != CF_V10 && p.form != CF_V10K) Y3_FAIL("y3_conv_v10_tiles: the dispatcher picks '%s' for this problem, not conv_v10.h", p.name);
+    v10_fill_args(a, p.v10);
     int64_t n = 0;
     for (int bi = 0; bi < a.v10_B; ++bi) {
         const V10Share sh = v10_share(a, bi, bi / a.v10_g);
@@ -1317,32 +1389,27 @@ extern "C" int y3_conv_last_variant(char* name, size_t name_cap) {
 }
 
 // rows of the statistics buffer the launch described by (desc, x, y) would write (depends on the tile variant dispatched)
-extern "C" int64_t y3_conv2d_fwd_stats_rows(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y) {
-    int64_t rows = 0;
-    alignas(16) static const float dummy[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // geometry only: never dereferenced
-    if (conv_fwd_impl(d, x, (const void*)dummy, dummy, nullptr, y, nullptr, 0, &rows, 1, nullptr)) return -1;
-    return rows;
-}
+extern "C" int64_t y3_conv2d_fwd_stats_rows(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y) { return y3_conv2d_fwd_stats_rows_ws(d, x, y, 0); }
 
 extern "C" int y3_conv2d_fwd_stats(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* y, float* stat_rows, int64_t capacity_rows,
                                    int64_t* n_rows, void* stream) {
     if (!n_rows) Y3_FAIL("y3_conv2d_fwd_stats: null row count");
-    return conv_fwd_impl(d, x, filt, bias, nullptr, y, stat_rows, capacity_rows, n_rows, 0, stream);
+    return conv_fwd_impl(d, x, filt, bias, nullptr, y, stat_rows, capacity_rows, n_rows, stream);
 }
 
 // the two calls above with the stream-K workspace of y3_conv2d_fwd_ws (the persistent kernel writes 4 statistic rows per pixel tile)
 extern "C" int64_t y3_conv2d_fwd_stats_rows_ws(const y3_conv_desc* d, const y3_tensor* x, const y3_tensor* y, size_t workspace_bytes) {
     int64_t rows = 0;
-    alignas(256) static const float dummy[64] = {0.0f};   // geometry only: never dereferenced
-    if (conv_fwd_impl(d, x, (const void*)dummy, dummy, nullptr, y, nullptr, 0, &rows, 1, nullptr, workspace_bytes ? (void*)dummy : nullptr, workspace_bytes)) return -1;
-    return rows;
+    ConvArgs a;
+    ConvPlan p;
+    return conv_query(d, x, y, 0, workspace_bytes, a, p, &rows) ? -1 : rows;
 }
 
 extern "C" int y3_conv2d_fwd_stats_ws(const y3_conv_desc* d, const y3_tensor* x, const void* filt, const float* bias, const y3_tensor* y, float* stat_rows,
                                       int64_t capacity_rows, int64_t* n_rows, void* workspace, size_t workspace_bytes, void* stream) {
     if (!n_rows) Y3_FAIL("y3_conv2d_fwd_stats_ws: null row count");
     if (workspace && ((uintptr_t)workspace & 255)) Y3_FAIL("y3_conv2d_fwd_stats_ws: the workspace must be 256-byte aligned");
-    return conv_fwd_impl(d, x, filt, bias, nullptr, y, stat_rows, capacity_rows, n_rows, 0, stream, workspace, workspace_bytes);
+    return conv_fwd_impl(d, x, filt, bias, nullptr, y, stat_rows, capacity_rows, n_rows, stream, workspace, workspace_bytes);
 }
 
 
@@ -1350,7 +1417,7 @@ extern "C" int y3_conv2d_fwd_stats_ws(const y3_conv_desc* d, const y3_tensor* x,
 // way in (conv_1x1s.h IN form).  `u_in` is the producer's pre-BatchNorm tensor, `y_in` receives the normalised / activated tensor (the other consumers read it), `y` this
 // conv's own pre-BatchNorm output.  Shapes the form does not cover are refused (y3_conv2d_fwd_bnin_rows returns -1: the caller keeps the separate passes).
 static int bnin_fill(const y3_conv_desc* d, const y3_tensor* u_in, const float* in_scale, const float* in_shift, int32_t in_act, const y3_tensor* in_res, const y3_tensor* y_in,
-                     const void* filt, const float* bias, const y3_tensor* y, ConvArgs& a, S1Plan& pl) {
+                     const void* filt, const float* bias, const y3_tensor* y, ConvArgs& a, ConvPlan& p) {
     if (!d || !u_in || !y_in || !y) Y3_FAIL("y3_conv2d_fwd_bnin: null argument");
     if (d->ksize != 1 || d->stride != 1 || d->upsample2x || d->in_dilation > 1 || (d->dtype != Y3_F16 && d->dtype != Y3_BF16)) Y3_FAIL("y3_conv2d_fwd_bnin: 1x1 / stride 1 / f16 or bf16 only");
     if (u_in->c != d->cin || y->c != d->cout || y_in->c != d->cin) Y3_FAIL("y3_conv2d_fwd_bnin: channel mismatch");
@@ -1377,20 +1444,17 @@ static int bnin_fill(const y3_conv_desc* d, const y3_tensor* u_in, const float* 
     a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
     a.in_res = in_res ? in_res->data : nullptr; a.in_rpitch = in_res ? in_res->pitch : 0; a.in_r_bytes = in_res ? (unsigned)ext(in_res) : 0u;
     a.in_y = y_in->data; a.in_ypitch = y_in->pitch; a.in_y_bytes = (unsigned)ext(y_in);
-    if (!s1_plan(a, pl, in_res ? 2 : 1)) Y3_FAIL("y3_conv2d_fwd_bnin: shape not covered (cin %d, cout %d)", d->cin, d->cout);
-    return 0;
+    if (!s1_plan(a, p.s1, s1_in(a))) Y3_FAIL("y3_conv2d_fwd_bnin: shape not covered (cin %d, cout %d)", d->cin, d->cout);
+    return plan_s1(a, p);
 }
 
 extern "C" int64_t y3_conv2d_fwd_bnin_rows(const y3_conv_desc* d, const y3_tensor* u_in, const y3_tensor* y_in, const y3_tensor* y, int32_t has_shortcut) {
-    alignas(256) static const float dummy[64] = {0.0f};   // geometry only: never dereferenced
     y3_tensor r;
-    if (has_shortcut && y_in) { r = *y_in; r.data = (void*)dummy; }
+    if (has_shortcut && y_in) { r = *y_in; r.data = (void*)g_dummy; }
     ConvArgs a;
-    S1Plan pl;
-    if (bnin_fill(d, u_in, dummy, dummy, Y3_ACT_NONE, has_shortcut ? &r : nullptr, y_in, (const void*)dummy, dummy, y, a, pl)) return -1;
-    a.dry = 1;
-    if (d->dtype == Y3_F16 ? launch_s1<f16_t>(a, pl, nullptr) : launch_s1<bf16_t>(a, pl, nullptr)) return -1;
-    return (int64_t)a.n_pt * a.stat_wp;
+    ConvPlan p;
+    if (bnin_fill(d, u_in, g_dummy, g_dummy, Y3_ACT_NONE, has_shortcut ? &r : nullptr, y_in, (const void*)g_dummy, g_dummy, y, a, p)) return -1;
+    return p.rows();
 }
 
 extern "C" int y3_conv2d_fwd_bnin_stats(const y3_conv_desc* d, const y3_tensor* u_in, const float* in_scale, const float* in_shift, int32_t in_act, const y3_tensor* in_shortcut,
@@ -1398,15 +1462,16 @@ extern "C" int y3_conv2d_fwd_bnin_stats(const y3_conv_desc* d, const y3_tensor* 
                                         void* stream) {
     if (!in_scale || !in_shift || !filt || !bias || !n_rows) Y3_FAIL("y3_conv2d_fwd_bnin_stats: null argument");
     ConvArgs a;
-    S1Plan pl;
-    if (bnin_fill(d, u_in, in_scale, in_shift, in_act, in_shortcut, y_in, filt, bias, y, a, pl)) return -1;
-    const int64_t rows = (int64_t)y3_ceil_div(a.M, pl.sp) * pl.wp * pl.npass;
+    ConvPlan p;
+    if (bnin_fill(d, u_in, in_scale, in_shift, in_act, in_shortcut, y_in, filt, bias, y, a, p)) return -1;
+    const int64_t rows = p.rows();
     *n_rows = rows;
     if (stat_rows) {
         if (capacity_rows < rows) Y3_FAIL("y3_conv2d_fwd_bnin_stats: statistics buffer holds %lld rows, the launch writes %lld", (long long)capacity_rows, (long long)rows);
         a.stats = stat_rows;
     }
-    return d->dtype == Y3_F16 ? launch_s1<f16_t>(a, pl, (hipStream_t)stream) : launch_s1<bf16_t>(a, pl, (hipStream_t)stream);
+    launch_begin(a, p);
+    return d->dtype == Y3_F16 ? launch_s1<f16_t>(a, p.s1, (hipStream_t)stream) : launch_s1<bf16_t>(a, p.s1, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1427,6 +1492,14 @@ S2Class s2_class(int ph, int pw) {
     return c;
 }
 size_t s2_bank_elems(int cout, int cin, int ntaps) { return (size_t)y3_filter_rows(cin) * y3_round_up((size_t)ntaps * cout, 64); }
+
+// the four classes as one launch of the v3 tile that the plan of class `big`, the one with the most taps, chose
+template <typename T> int launch_v3_quad(const ConvArgs* cls, int big, const ConvPlan& p, hipStream_t st) {
+    ConvArgs lead = cls[big];
+    launch_begin(lead, p);
+    g_last_variant = "v3_quad";
+    return conv_launch<T>(lead, p, st, cls);
+}
 
 template <typename T>
 __global__ void pack_dgrad_s2_kernel(const float* __restrict__ src, int cout_src, int cin_src, int cout, int rows, int kpad, int nh, int nw, int kh0, int kh1, int kw0,
@@ -1527,32 +1600,19 @@ extern "C" int y3_conv2d_dgrad_s2(int32_t dtype, const y3_tensor* du, const void
     bool quad = quad_on && live[0] && live[1] && live[2] && live[3] && cls[0].M == cls[3].M && cls[1].M == cls[3].M && cls[2].M == cls[3].M;
     if (quad) {
         CsPlan sp;
-        if (cq_plan(cls, sp)) return dtype == Y3_F16 ? launch_cq<f16_t>(cls, st) : launch_cq<bf16_t>(cls, st);   // conv_strip.h: du rows staged once for the nine (tap, class) pairs
+        if (cq_plan(cls, sp)) return dtype == Y3_F16 ? launch_cq<f16_t>(cls, sp, st) : launch_cq<bf16_t>(cls, sp, st);   // conv_strip.h: du rows staged once for the nine (tap, class) pairs
         int big = 0;
         for (int i = 1; i < 4; ++i)
             if (cls[i].ntaps > cls[big].ntaps) big = i;
-        ConvArgs probe = cls[big];
-        probe.dry = 1;
-        const int rc0 = dtype == Y3_F16 ? dispatch_igemm<f16_t>(probe, st) : dispatch_igemm<bf16_t>(probe, st);
-        if (rc0) return rc0;
-        if (strncmp(g_last_variant, "v3_", 3) == 0) {
-            g_quad = cls;
-            g_quad_done = false;
-            ConvArgs lead = cls[big];
-            const int rc = dtype == Y3_F16 ? dispatch_igemm<f16_t>(lead, st) : dispatch_igemm<bf16_t>(lead, st);
-            g_quad = nullptr;
-            if (rc) return rc;
-            if (g_quad_done) {
-                g_last_variant = "v3_quad";
-                return 0;
-            }
-            Y3_FAIL("y3_conv2d_dgrad_s2: the fused launch was not taken");
-        }
+        ConvPlan p;
+        if (const int rc = conv_decide(cls[big], p)) return rc;
+        if (p.is_v3() && ((long long)p.n_ct * p.n_pt + 7) / 8 * 32 <= 0x7fffffffLL) return dtype == Y3_F16 ? launch_v3_quad<f16_t>(cls, big, p, st) : launch_v3_quad<bf16_t>(cls, big, p, st);
     }
     for (int i = 0; i < 4; ++i)
         if (live[i]) {
-            const int rc = dtype == Y3_F16 ? dispatch_igemm<f16_t>(cls[i], st) : dispatch_igemm<bf16_t>(cls[i], st);
-            if (rc) return rc;
+            ConvPlan p;
+            if (const int rc = conv_decide(cls[i], p)) return rc;
+            if (const int rc = conv_launch_as(dtype, cls[i], p, st)) return rc;
         }
     return 0;
 }

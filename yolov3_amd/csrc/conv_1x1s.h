@@ -255,12 +255,7 @@ static bool s1_plan(const ConvArgs& a, S1Plan& pl, int in = 0) {   // in: 0 plai
 }
 
 template <typename T> int launch_s1(ConvArgs& a, const S1Plan& pl, hipStream_t st) {
-    a.n_ct = pl.n_ct;
-    a.n_pt = y3_ceil_div(a.M, pl.sp);          // stages
-    a.stat_wp = pl.wp * pl.npass;              // statistics rows per stage: one per (pixel wave, epilogue pass)
     set_divisors(a);
-    g_last_variant = pl.in ? "s1x1_bn" : "s1x1";
-    if (a.dry) return 0;
     const int cus = y3_cu_count();
     int slots = cus / pl.n_ct;                 // blocks per filter tile
     if (slots < 1) slots = 1;

@@ -242,18 +242,11 @@ static bool cs_plan(const ConvArgs& a, CsPlan& pl) {
     return true;
 }
 
-template <typename T> int launch_cs(ConvArgs& a, hipStream_t st) {
-    CsPlan pl;
-    if (!cs_plan(a, pl)) Y3_FAIL("conv strip: no plan (internal)");
+template <typename T> int launch_cs(ConvArgs& a, const CsPlan& pl, hipStream_t st) {
     a.cs_strips = pl.strips; a.cs_T = pl.T; a.cs_per = pl.per;
     set_divisors(a);
     magic_u31(a.Ho, a.dv_pw_mul, a.dv_pw_sh);          // this kernel divides the row index by Ho and by the strips per row
     magic_u31(pl.strips, a.dv_h1_mul, a.dv_h1_sh);
-    a.n_pt = pl.blocks;
-    a.n_ct = 1;
-    a.stat_wp = pl.mt * (a.Cin > 64 ? 2 : 1);   // one statistics row per block, pixel tile and K-split wave
-    g_last_variant = "strip";
-    if (a.dry) return 0;
     const dim3 grid((unsigned)pl.blocks);
     if (a.stride == 2) hipLaunchKernelGGL((conv_strip_kernel<T, 64, 128, 2, 2>), grid, dim3(cs_threads<64, 128, 2>()), 0, st, a);
     else if (a.Cin == 128) hipLaunchKernelGGL((conv_strip_kernel<T, 128, 64, 2>), grid, dim3(cs_threads<128, 64, 2>()), 0, st, a);
@@ -489,9 +482,7 @@ static bool cq_plan(const ConvArgs* cls, CsPlan& pl) {
     return true;
 }
 
-template <typename T> int launch_cq(ConvArgs* cls, hipStream_t st) {
-    CsPlan pl;
-    if (!cq_plan(cls, pl)) Y3_FAIL("conv strip (stride-2 data gradient): no plan (internal)");
+template <typename T> int launch_cq(ConvArgs* cls, const CsPlan& pl, hipStream_t st) {
     CqArgs q;
     for (int i = 0; i < 4; ++i) {
         if (cls[i].ooh != (i >> 1) || cls[i].oow != (i & 1) || cls[i].omul != 2) Y3_FAIL("conv strip (stride-2 data gradient): class order (internal)");

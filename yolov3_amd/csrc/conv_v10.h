@@ -504,9 +504,6 @@ __global__ __launch_bounds__(256) void conv_v10_reduce_kernel(const ConvArgs p) 
 #endif
 }
 
-static thread_local ConvArgs g_v10_dry;              // the arguments a dry run of this kernel filled (y3_conv_v10_tiles)
-static thread_local bool g_v10_dry_valid = false;
-
 // The host's plan: blocks per filter tile (B), column blocks per block (q, + 1 for the first r), the widest body whose worst-case halo patch fits the
 // patch buffer, tiles per block for the two run lengths.
 struct V10Plan {
@@ -574,12 +571,6 @@ static bool v10_shape_ok(const ConvArgs& a) {
 // a quarter round of 256-pixel tiles or more: whole tiles fill the chip
 static bool v10_big_enough(const ConvArgs& a) { return (long long)y3_ceil_div(a.M, 256) * (a.Cout / 256) >= 64 || y3_knob(Y3K_CONV_V10) == 2; }
 
-static bool v10_eligible(const ConvArgs& a) {
-    if (!v10_shape_ok(a) || !v10_big_enough(a)) return false;
-    V10Plan pl;
-    return v10_plan(a, pl);
-}
-
 // SPLIT form (small launches, needs the caller's workspace): the half-size geometry where its patch fits (more, smaller tiles), S slices of the channel blocks so that
 // (filter tiles x blocks x slices) reaches the resident block count; knob v10_slices forces S (tests)
 static bool v10k_plan(const ConvArgs& a, V10Plan& pl) {
@@ -600,15 +591,10 @@ static bool v10k_plan(const ConvArgs& a, V10Plan& pl) {
     pl.S = (int)S;
     return nb1 * S <= 0x7fffffffLL;
 }
-static bool v10k_eligible(const ConvArgs& a) {
-    if (y3_knob(Y3K_V10_KSPLIT) == 0 || !v10_shape_ok(a) || (v10_big_enough(a) && y3_knob(Y3K_V10_KSPLIT) != 2)) return false;
-    V10Plan pl;
-    return v10k_plan(a, pl);
-}
 
+// the kernel-visible geometry of a plan (n_pt and stat_wp are the form's: conv_decide)
 static void v10_fill_args(ConvArgs& a, const V10Plan& pl) {
     a.n_ct = a.Cout / 256;
-    a.n_pt = pl.n_tiles;
     a.v10_B = pl.B; a.v10_q = pl.q; a.v10_r = pl.r; a.v10_nt_hi = pl.nt_hi; a.v10_nt_lo = pl.nt_lo; a.v10_S = pl.S;
     a.v10_tq_h = (pl.q + 1) / pl.nt_hi; a.v10_tr_h = (pl.q + 1) % pl.nt_hi;
     a.v10_tq_l = pl.nt_lo ? pl.q / pl.nt_lo : 0; a.v10_tr_l = pl.nt_lo ? pl.q % pl.nt_lo : 0;
@@ -628,13 +614,8 @@ static void v10_fill_args(ConvArgs& a, const V10Plan& pl) {
     a.nk = 9 * a.cin_blocks;
 }
 
-template <typename T> int launch_v10(ConvArgs& a, hipStream_t st) {
-    V10Plan pl;
-    if (!v10_plan(a, pl)) Y3_FAIL("conv v10: no tile plan (internal)");
+template <typename T> int launch_v10(ConvArgs& a, const V10Plan& pl, hipStream_t st) {
     v10_fill_args(a, pl);
-    a.stat_wp = 4;   // statistics rows per tile: one per 64-pixel epilogue pass of the widest body (narrower bodies write zero rows)
-    g_last_variant = pl.half ? "v10h" : "v10";
-    if (a.dry) { g_v10_dry = a; g_v10_dry_valid = true; return 0; }
     const dim3 grid((unsigned)(a.n_ct * pl.B)), block(256);
 #ifdef Y3_ABLATE
     if (const char* e = getenv("Y3_V10_ABL"); e && std::is_same<T, f16_t>::value && !pl.half) {   // lab build only (f16, one block per CU)
@@ -663,14 +644,8 @@ template <typename T> int launch_v10(ConvArgs& a, hipStream_t st) {
 }
 
 // SPLIT form: the tile kernel over (slice, filter tile, run) blocks, then the slab sum
-template <typename T> int launch_v10k(ConvArgs& a, hipStream_t st) {
-    V10Plan pl;
-    if (!v10k_plan(a, pl)) Y3_FAIL("conv v10k: no plan (internal)");
+template <typename T> int launch_v10k(ConvArgs& a, const V10Plan& pl, hipStream_t st) {
     v10_fill_args(a, pl);
-    a.n_pt = y3_ceil_div(a.M, 64);   // statistics rows: one per 64-pixel block of the slab sum
-    a.stat_wp = 1;
-    g_last_variant = "v10k";
-    if (a.dry) { g_v10_dry = a; g_v10_dry_valid = true; return 0; }
     const dim3 grid((unsigned)(a.n_ct * pl.B * pl.S)), block(256);
     if (pl.half) {
         if (pl.xq == 2) hipLaunchKernelGGL((conv_igemm_v10_kernel<T, 2, true, true>), grid, block, 0, st, a);
