@@ -277,6 +277,14 @@ int y3_confusion_matrix(const float* dets, int64_t img_stride, int32_t row_strid
                         int64_t* matrix, void* stream);
 int y3_labels_to_native(const float* targets, int32_t nl, int32_t bs, float width, float height, const float* params, float* labels_out,
                         int32_t* offsets_out, void* stream);
+/* The a-priori label rows of non_max_suppression(labels=...) / val.py --save-hybrid (utils/general.py:689-695, val.py:371-372), csrc/val_edge.hip: fills rows
+ * [row0, row0 + n_rows) of every image of the (bs, total_rows, no) prediction `pred`.  targets: DEVICE (nl, 6) fp32 [image, class, x, y, w, h] grouped by image through
+ * label_offsets (bs + 1 int32, as y3_labels_to_native writes them; the image column itself is not read).  Label k of image i -> row row0 + k:
+ * xywh = targets[2:6] * (width, height, width, height) (fp32 product, rounded once to dtype), objectness 1, one-hot class 1, every other element 0; rows past the image's
+ * labels are all 0, labels past n_rows are dropped.  A class outside [0, nc = no - 5) writes no one-hot (the reference raises IndexError): the row is never a candidate.
+ * Rows outside the window are not touched.  Any `no` >= 6, any alignment. */
+int y3_label_rows(const float* targets, int32_t nl, const int32_t* label_offsets, int32_t bs, float width, float height, void* pred, int32_t dtype,
+                  int32_t total_rows, int32_t no, int32_t row0, int32_t n_rows, void* stream);
 
 /* Autoanchor, device-resident (csrc/autoanchor.hip): reference utils/autoanchor.py -- check_anchors.metric, anchor_fitness, print_results, the genetic loop
  * of kmean_anchors and the scipy.cluster.vq.kmeans call ahead of it.  Nothing here allocates or synchronises.  wh / pts are DEVICE (N, 2) fp32; k, f, v, codes,

@@ -18,7 +18,11 @@ class DetectMultiBackend(nn.Module):
         if isinstance(weights, nn.Module):
             model = weights.to(device)
         elif Path(w).suffix == ".pt":
-            model = attempt_load(w, device=device, inplace=True, fuse=fuse)  # models/common.py:472
+            bad = [str(v) for v in (weights if isinstance(weights, (list, tuple)) else [weights]) if Path(str(v)).suffix != ".pt"]
+            if bad:
+                raise NotImplementedError(f"{bad[0]}: only PyTorch .pt checkpoints run on the MI355X path (the other backends are foreign runtimes)")
+            # a list goes to attempt_load whole: several weights are an Ensemble (models/common.py:472 `weights if isinstance(weights, list) else w`)
+            model = attempt_load(list(weights) if isinstance(weights, (list, tuple)) else w, device=device, inplace=True, fuse=fuse)
         else:
             raise NotImplementedError(f"{w}: only PyTorch .pt checkpoints run on the MI355X path (the other backends are foreign runtimes)")
         self.stride = max(int(model.stride.max()), 32)

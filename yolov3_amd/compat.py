@@ -29,7 +29,7 @@ import types
 import torch
 from torch import nn
 
-from . import common, yolo
+from . import common, experimental, yolo
 
 _YOLO_NAMES = ("Detect", "DetectionModel", "Model", "BaseModel", "parse_model")
 _COMMON_NAMES = ("Conv", "Bottleneck", "SPP", "Concat", "autopad")
@@ -40,6 +40,7 @@ def _class_map() -> dict:
     """qualified reference name -> the class of this package that stands in for it"""
     table = {("models.yolo", n): getattr(yolo, n) for n in _YOLO_NAMES}
     table.update({("models.common", n): getattr(common, n) for n in _COMMON_NAMES})
+    table[("models.experimental", "Ensemble")] = experimental.Ensemble
     return table
 
 
@@ -110,7 +111,7 @@ def install_aliases(force: bool = False) -> bool:
     from .backend import DetectMultiBackend
 
     m_common.AutoShape, m_common.DetectMultiBackend = AutoShape, DetectMultiBackend   # utils/general.py:432 imports both
-    m_exp.attempt_load = attempt_load
+    m_exp.attempt_load, m_exp.Ensemble = attempt_load, experimental.Ensemble
     for m in (pkg, m_yolo, m_common, m_exp):
         m._yolov3_amd_alias = True
     pkg.yolo, pkg.common, pkg.experimental = m_yolo, m_common, m_exp
@@ -187,22 +188,31 @@ def load_checkpoint(weights):
 
 
 def attempt_load(weights, device=None, inplace=True, fuse=True):
-    """reference models/experimental.py:88-136 for a single ``.pt``: unpickle, take ``ema`` or ``model``, fp32, fuse, eval."""
-    if isinstance(weights, (list, tuple)):
-        if len(weights) != 1:
-            raise NotImplementedError("model ensembles are outside the accelerated hot path")
-        weights = weights[0]
-    ckpt = load_checkpoint(weights)
-    model = ckpt.get("ema") or ckpt["model"] if isinstance(ckpt, dict) else ckpt
-    model = adopt(model).to(device).float()
-    if not hasattr(model, "stride"):
-        model.stride = torch.tensor([32.0])
-    if hasattr(model, "names") and isinstance(model.names, (list, tuple)):
-        model.names = dict(enumerate(model.names))
-    model = model.fuse().eval() if fuse and hasattr(model, "fuse") else model.eval()
+    """reference models/experimental.py:88-136: per ``.pt`` unpickle, take ``ema`` or ``model``, fp32, fuse, eval.  One weight returns that model; several return an
+    ``Ensemble`` with ``names`` / ``nc`` / ``yaml`` of the first member and the ``stride`` of the member whose largest stride is largest.  (``nc``: train.py attaches
+    it to the model it saves; a checkpoint without it answers with its Detect head's.)"""
+    model = experimental.Ensemble()
+    for w in weights if isinstance(weights, (list, tuple)) else [weights]:
+        ckpt = load_checkpoint(w)
+        ckpt = ckpt.get("ema") or ckpt["model"] if isinstance(ckpt, dict) else ckpt
+        ckpt = adopt(ckpt).to(device).float()
+        if not hasattr(ckpt, "stride"):
+            ckpt.stride = torch.tensor([32.0])
+        if hasattr(ckpt, "names") and isinstance(ckpt.names, (list, tuple)):
+            ckpt.names = dict(enumerate(ckpt.names))
+        model.append(ckpt.fuse().eval() if fuse and hasattr(ckpt, "fuse") else ckpt.eval())
     for m in model.modules():
         if isinstance(m, yolo.Detect):
             m.inplace = inplace
+    if len(model) == 1:
+        return model[-1]
+    for m in model:
+        if not hasattr(m, "nc"):
+            m.nc = m.model[-1].nc
+    for k in "names", "nc", "yaml":
+        setattr(model, k, getattr(model[0], k))
+    model.stride = model[int(torch.argmax(torch.tensor([float(m.stride.max()) for m in model])))].stride  # max stride
+    assert all(model[0].nc == m.nc for m in model), f"Models have different class counts: {[m.nc for m in model]}"
     return model
 
 

@@ -913,6 +913,8 @@ extern "C" int y3_detect_decode(const y3_tensor* head, int32_t dtype, int32_t na
     if (!head || !anchors_px) Y3_FAIL("y3_detect_decode: null argument");
     if (na < 1 || na > 5) Y3_FAIL("y3_detect_decode: na=%d unsupported (1..5)", na);
     if (head->c < na * no) Y3_FAIL("y3_detect_decode: head has %d channels, needs %d", head->c, na * no);
+    if (z && (row_offset < 0 || row_offset + (long long)na * head->h * head->w > total_rows))
+        Y3_FAIL("y3_detect_decode: rows [%lld, +%lld) do not fit the %lld rows of z", (long long)row_offset, (long long)na * head->h * head->w, (long long)total_rows);
     float a[10] = {0};
     for (int i = 0; i < na * 2; ++i) a[i] = anchors_px[i];
     const long long total = (long long)head->n * head->h * head->w * na * no;

@@ -194,6 +194,31 @@ template <typename T> __global__ __launch_bounds__(256) void descale_pred_kernel
     dst[((long long)img * dst_rows + dst_row0 + r) * no + col] = from_f32<T>(v);
 }
 
+// The a-priori label rows of non_max_suppression(labels=...) (reference utils/general.py:689-695; val.py:371-372 --save-hybrid): rows [row0, row0 + n_rows) of every image
+// of a (bs, total_rows, no) prediction.  Label k of image i (targets row offs[i] + k: [image, class, x, y, w, h]) becomes [xywh * (w, h, w, h), 1, one-hot class]: the fp32
+// product of val.py:371 rounded once to T; every other element of the window, and every row past the image's labels, is 0 (objectness 0 never passes conf_thres).  A class
+// outside [0, nc) sets no one-hot element: such a row has no class score and is never a candidate.  One thread per element: `no` may be odd, rows are not 16-byte multiples.
+template <typename T> __global__ __launch_bounds__(256) void label_rows_kernel(const float* __restrict__ targets, int nl, const int* __restrict__ offs, float width, float height,
+                                                                                 T* __restrict__ pred, int total_rows, int no, int row0, int n_rows, long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int col = (int)(idx % no);
+    const long long rr = idx / no;
+    const int r = (int)(rr % n_rows), img = (int)(rr / n_rows);
+    float v = 0.0f;
+    const int l0 = offs[img], l = l0 + r;
+    if (l0 >= 0 && l < offs[img + 1] && l < nl) {
+        const float* t = targets + (long long)l * 6;
+        if (col < 4) v = t[2 + col] * ((col & 1) ? height : width);
+        else if (col == 4) v = 1.0f;
+        else {
+            const float c = t[1];
+            v = (c > -1.0f && c < 16777216.0f && (int)c == col - 5) ? 1.0f : 0.0f;   // `.long()`: truncation towards zero
+        }
+    }
+    pred[((long long)img * total_rows + row0 + r) * no + col] = from_f32<T>(v);
+}
+
 }  // namespace
 
 extern "C" int y3_scale_boxes(float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows, const float* params, void* stream) {
@@ -269,6 +294,25 @@ extern "C" int y3_descale_pred(const void* src, int32_t dtype, int32_t bs, int32
         case Y3_F16: hipLaunchKernelGGL(descale_pred_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)src, src_rows, no, row0, nrows, scale, flip, img_h, img_w, (_Float16*)dst, dst_rows, dst_row0, total); break;
         case Y3_BF16: hipLaunchKernelGGL(descale_pred_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, src_rows, no, row0, nrows, scale, flip, img_h, img_w, (bf16_t*)dst, dst_rows, dst_row0, total); break;
         default: Y3_FAIL("y3_descale_pred: unsupported dtype %d", dtype);
+    }
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_label_rows(const float* targets, int32_t nl, const int32_t* label_offsets, int32_t bs, float width, float height, void* pred, int32_t dtype, int32_t total_rows,
+                             int32_t no, int32_t row0, int32_t n_rows, void* stream) {
+    if (!pred || !label_offsets || (nl > 0 && !targets)) Y3_FAIL("y3_label_rows: null argument");
+    if (nl < 0 || bs < 0 || no < 6 || row0 < 0 || n_rows < 0 || total_rows < 0 || (long long)row0 + n_rows > total_rows)
+        Y3_FAIL("y3_label_rows: bad geometry (nl %d, bs %d, no %d, rows [%d, +%d) of %d)", nl, bs, no, row0, n_rows, total_rows);
+    const long long total = (long long)bs * n_rows * no;
+    if (total == 0) return 0;
+    if (total > 0x7fffffffLL * 256) Y3_FAIL("y3_label_rows: window too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    switch (dtype) {
+        case Y3_F32: hipLaunchKernelGGL(label_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, targets, nl, label_offsets, width, height, (float*)pred, total_rows, no, row0, n_rows, total); break;
+        case Y3_F16: hipLaunchKernelGGL(label_rows_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, targets, nl, label_offsets, width, height, (_Float16*)pred, total_rows, no, row0, n_rows, total); break;
+        case Y3_BF16: hipLaunchKernelGGL(label_rows_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, targets, nl, label_offsets, width, height, (bf16_t*)pred, total_rows, no, row0, n_rows, total); break;
+        default: Y3_FAIL("y3_label_rows: unsupported dtype %d", dtype);
     }
     Y3_CHECK_LAUNCH();
     return 0;

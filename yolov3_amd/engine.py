@@ -733,7 +733,10 @@ def _decode_consts(det, dtype):
     return [(anchors_px[l].reshape(-1).tolist(), float(stride[l])) for l in range(det.nl)]
 
 
-def _decode_outputs(plan: Plan, det, heads, n, export=False, training=False):
+def _decode_outputs(plan: Plan, det, heads, n, export=False, training=False, out=None):
+    """`out` = (buffer, row_offset): the levels are decoded into rows [row_offset, row_offset + rows) of the caller's (bs, total_rows, no) buffer -- a window of a
+    prediction several producers share (Ensemble members, the label rows of --save-hybrid) -- no z and no raw tensors are allocated or written, and the row count
+    is returned.  The window was checked by `check_window` before anything was launched."""
     dtype, dev = plan.dtype, plan.device
     na, no = det.na, det.no
     rows = [na * hv.h * hv.w for hv in heads]
@@ -741,18 +744,85 @@ def _decode_outputs(plan: Plan, det, heads, n, export=False, training=False):
     consts = plan.__dict__.get("decode_consts")
     if consts is None:
         consts = plan.decode_consts = _decode_consts(det, dtype)
-    z = None if training else torch.empty(n, total, no, dtype=dtype, device=dev)
+    if out is not None:
+        z, off = out
+        if off < 0 or off + total > z.shape[1]:
+            raise ValueError(f"rows [{off}, {off + total}) do not fit a buffer of {z.shape[1]} rows")
+        export, total = True, z.shape[1]
+    else:
+        z, off = (None if training else torch.empty(n, total, no, dtype=dtype, device=dev)), 0
     raws = []
-    off = 0
     for lvl, hv in enumerate(heads):
         raw = None if export else torch.empty(n, na, hv.h, hv.w, no, dtype=dtype, device=dev)
         apx, stride = consts[lvl]
         ops.detect_decode(hv.real(), na, no, apx, stride, raw, z, off, total)
         raws.append(raw)
         off += rows[lvl]
+    if out is not None:
+        return sum(rows)
     if training:
         return raws
     return (z,) if export else (z, raws)
+
+
+def tta_windows(model, h, w):
+    """The passes of test-time augmentation on an (h, w) batch (reference models/yolo.py:239-276), host arithmetic only: per pass (scale, flip, (ph, pw) of the scaled
+    and padded batch, rows of its decoded prediction, first row kept, rows kept).  _clip_augmented drops the coarsest level of the full-size pass (the last
+    rows // g rows, g = sum 4^k) and the finest level of the smallest one (the first rows // g * 4^(nl - 1))."""
+    import math
+
+    det = model.model[-1]
+    gs = int(model.stride.max())
+    nl = det.nl
+    g = sum(4**k for k in range(nl))
+    scales, flips = [1, 0.83, 0.67], [None, 3, None]
+    passes = []
+    for i, (si, fi) in enumerate(zip(scales, flips)):
+        ph, pw = (h, w) if si == 1 else (math.ceil(h * si / gs) * gs, math.ceil(w * si / gs) * gs)
+        rows = pred_rows(model, ph, pw)
+        lo, hi = 0, rows
+        if i == 0:
+            hi = rows - (rows // g) * 1
+        if i == len(scales) - 1:
+            lo = (rows // g) * 4 ** (nl - 1)
+        passes.append((si, fi, (ph, pw), rows, lo, hi - lo))
+    return passes
+
+
+def pred_rows(model, h, w, augment=False) -> int:
+    """rows of the decoded prediction `model(x, augment)[0]` of an (h, w) batch: na * sum over the Detect levels of ny * nx (graph_hw), under `augment` the rows
+    _clip_augmented keeps of the three passes.  Nothing runs on the device."""
+    if augment:
+        return sum(p[5] for p in tta_windows(model, int(h), int(w)))
+    det = model.model[-1]
+    hw = graph_hw(model, int(h), int(w))
+    return det.na * sum(hw[j][0] * hw[j][1] for j in _sources(len(model.model) - 1, det.f))
+
+
+def check_window(model, x, out, augment=False):
+    """`out` = (buffer, row_offset) for the prediction of `model` on `x`: a contiguous (bs, total_rows, no) tensor of the model's inference dtype on x's device with
+    room for pred_rows(model, h, w, augment) rows behind row_offset.  Raises ValueError otherwise; launches nothing.  Returns (buffer, row_offset, rows)."""
+    try:
+        buf, off = out
+        off = int(off)
+    except (TypeError, ValueError):
+        raise ValueError("out= expects (buffer, row_offset)") from None
+    det = model.model[-1]
+    dtype = getattr(model, "infer_dtype", None) or _engine_dtype(model)
+    if not isinstance(buf, torch.Tensor) or buf.dim() != 3 or not buf.is_contiguous():
+        raise ValueError("out= expects a contiguous (bs, total_rows, no) buffer")
+    if buf.dtype != dtype:
+        raise ValueError(f"out= buffer is {buf.dtype}, the model infers in {dtype}")
+    if buf.device != x.device:
+        raise ValueError(f"out= buffer is on {buf.device}, the batch on {x.device}")
+    if buf.shape[2] != det.no:
+        raise ValueError(f"out= buffer has rows of {buf.shape[2]} elements, the model's have {det.no}")
+    if buf.shape[0] != x.shape[0]:
+        raise ValueError(f"out= buffer holds {buf.shape[0]} images, the batch {x.shape[0]}")
+    rows = pred_rows(model, x.shape[2], x.shape[3], augment)
+    if off < 0 or off + rows > buf.shape[1]:
+        raise ValueError(f"out= rows [{off}, {off + rows}) do not fit a buffer of {buf.shape[1]} rows")
+    return buf, off, rows
 
 
 class PlanCache:
@@ -842,13 +912,19 @@ def drop_plans(model):
         pc.clear()
 
 
-def run_model(model, x: torch.Tensor, profile=False):
+def run_model(model, x: torch.Tensor, profile=False, out=None):
+    """`out` = (buffer, row_offset): eval mode only; the decoded prediction goes into that window of the caller's (bs, total_rows, no) buffer (see _decode_outputs) and
+    the number of rows written is returned instead of (z, raws)."""
     ops.require_gpu(x, "DetectionModel.forward")
     if x.dim() != 4:
         raise ValueError(f"expected a (bs, ch, h, w) image batch, got shape {tuple(x.shape)}")
     ch = model.yaml.get("ch", 3) if isinstance(getattr(model, "yaml", None), dict) else None
     if ch is not None and x.shape[1] != ch:   # the stem kernel is handed the raw pointer: a wrong channel count would read past the buffer
         raise ValueError(f"expected {ch} input channels, got a batch of shape {tuple(x.shape)}")
+    if out is not None:
+        if model.training:
+            raise ValueError("out= is an eval-mode form: a training forward has no decoded prediction")
+        out = check_window(model, x, out)[:2]
     if model.training:
         from .train_engine import run_model_train
 
@@ -909,7 +985,7 @@ def run_model(model, x: torch.Tensor, profile=False):
     else:
         plan.run_body(stream, stem)
     det, heads = plan.detect
-    return _decode_outputs(plan, det, heads, n, export=det.export, training=model.training)
+    return _decode_outputs(plan, det, heads, n, export=det.export, training=model.training, out=out)
 
 
 def _profile(plan: Plan, stream, stem=None):

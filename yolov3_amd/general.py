@@ -94,6 +94,27 @@ def non_max_suppression_batched(prediction, conf_thres=0.25, iou_thres=0.45, cla
     return rows, torch.tensor(counts, dtype=torch.int32).to(rows.device, non_blocking=True), counts
 
 
+def _with_label_rows(prediction, labels):
+    """(bs, rows + max labels per image, no): the prediction followed by the a-priori rows of `labels` (per image a (k, 5) tensor [cls, x, y, w, h] in pixels; a shorter
+    list leaves the later images without labels).  One allocation, one copy of the prediction; the labels travel as one (nl, 6) block and bs + 1 offsets."""
+    bs, n_rows, no = prediction.shape
+    dev = prediction.device
+    per = [labels[i] if i < len(labels) else None for i in range(bs)]
+    counts = [0 if lb is None else len(lb) for lb in per]
+    extra, nl = max(counts), sum(counts)
+    offs = [0]
+    for c in counts:
+        offs.append(offs[-1] + c)
+    block = torch.zeros(nl, 6, dtype=torch.float32, device=next(lb.device for lb in per if lb is not None and len(lb)))
+    for lb, o, c in zip(per, offs, counts):
+        if c:
+            block[o : o + c, 1:] = lb[:, :5]   # (placement, on the labels' own device: column 0, the image index, is not read -- the grouping is the offsets')
+    wide = torch.empty(bs, n_rows + extra, no, dtype=prediction.dtype, device=dev)
+    wide[:, :n_rows].copy_(prediction)
+    ops.label_rows(wide, n_rows, extra, block.to(dev, non_blocking=True), torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True))
+    return wide
+
+
 def non_max_suppression(
     prediction,
     conf_thres=0.25,
@@ -122,17 +143,8 @@ def non_max_suppression(
     bs, n_rows, no = prediction.shape
     nc = no - 5
     if labels and any(len(lb) for lb in labels):
-        # apriori label rows (:689-695) enter the candidate list after the image's own rows: append them as extra
-        # prediction rows (obj=1, one-hot class); images with fewer labels get zero rows (obj=0 never passes).
-        extra = max(len(lb) for lb in labels)
-        v = torch.zeros(bs, extra, no, dtype=prediction.dtype, device=prediction.device)
-        for xi, lb in enumerate(labels):
-            if len(lb):
-                lb = lb.to(prediction.device)
-                k = len(lb)
-                v[xi, :k, :4] = lb[:, 1:5].to(prediction.dtype)
-                v[xi, :k, 4] = 1.0
-                v[xi, torch.arange(k, device=prediction.device), lb[:, 0].long() + 5] = 1.0
-        prediction = torch.cat((prediction, v), 1)
+        # apriori label rows (:689-695) enter the candidate list after the image's own rows: the prediction is copied once into a tensor with a tail window of
+        # max(labels per image) rows, which y3_label_rows fills (obj=1, one-hot class); images with fewer labels get zero rows (obj=0 never passes).
+        prediction = _with_label_rows(prediction, labels)
     rows, counts = ops.nms_raw(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det)
     return [rows[i, :c] for i, c in enumerate(counts)]

@@ -552,6 +552,25 @@ def labels_to_native(targets: torch.Tensor, bs: int, width: int, height: int, pa
     return out, offs
 
 
+def label_rows(pred: torch.Tensor, row0: int, n_rows: int, targets: torch.Tensor, offsets: torch.Tensor, width: float = 1.0, height: float = 1.0):
+    """rows [row0, row0 + n_rows) of every image of the contiguous (bs, rows, no) prediction become the a-priori label rows of non_max_suppression(labels=...):
+    targets (nl, 6) fp32 [image, class, x, y, w, h] on the device, grouped by image through offsets (bs + 1 int32); xywh * (width, height, width, height), objectness 1,
+    one-hot class, zero rows past an image's labels (y3_label_rows).  In place; the rows outside the window are not touched."""
+    require_gpu(pred, "label_rows")
+    if pred.dim() != 3 or not pred.is_contiguous():
+        raise TypeError("label_rows expects a contiguous (bs, rows, no) prediction")
+    bs, total, no = pred.shape
+    if targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[1] != 6 or not targets.is_contiguous() or targets.device != pred.device:
+        raise TypeError("label_rows expects contiguous fp32 (nl, 6) targets [image, class, x, y, w, h] on the prediction's device")
+    if offsets.dtype != torch.int32 or offsets.numel() != bs + 1 or not offsets.is_contiguous() or offsets.device != pred.device:
+        raise TypeError("label_rows expects bs + 1 int32 label offsets on the prediction's device")
+    if row0 < 0 or n_rows < 0 or row0 + n_rows > total:
+        raise ValueError(f"label_rows: rows [{row0}, {row0 + n_rows}) do not fit a prediction of {total} rows")
+    nl = targets.shape[0]
+    check(_lib.lib().y3_label_rows(targets.data_ptr() if nl else None, nl, offsets.data_ptr(), bs, float(width), float(height), pred.data_ptr(), dtype_code(pred.dtype), total, no,
+                                   int(row0), int(n_rows), stream_ptr()), "y3_label_rows")
+
+
 def scale_img(img: torch.Tensor, ratio: float = 1.0, same_shape: bool = False, gs: int = 32, flip_lr: bool = False) -> torch.Tensor:
     """upstream scale_img (the resize + pad of reference models/yolo.py:246), fused with the left-right mirror of the same line: (n, c, h, w) ->
     (n, c, ceil(h ratio / gs) gs, ceil(w ratio / gs) gs).  ratio 1.0 without a mirror returns `img` itself, like upstream."""

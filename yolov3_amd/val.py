@@ -46,40 +46,63 @@ def process_batch_batched(rows, counts, labels, label_offsets, iouv):
     return ops.match_detections_raw(rows, rows.stride(0), rows.stride(1), counts, rows.shape[0], rows.shape[1], lab, offs, thr)
 
 
+def _engine_model(model):
+    """the model the engine runs: `model` itself (a DetectionModel, an Ensemble), or the one a DetectMultiBackend wraps; None if there is none"""
+    from .experimental import Ensemble
+
+    if hasattr(model, "infer_dtype") or isinstance(model, Ensemble):
+        return model
+    inner = getattr(model, "model", None)
+    return inner if hasattr(inner, "infer_dtype") or isinstance(inner, Ensemble) else None
+
+
 class _infer_dtype:
     """``with _infer_dtype(model, half, dtype):`` -- the model's inference plans run in `dtype` (half: float16) inside the block, whatever its parameters are: fp32
     masters are read as they are and rounded once when the filter banks are packed (no ``model.half()`` ... ``model.float()`` round trip, reference val.py).
-    Neither given: the block changes nothing."""
+    Neither given: the block changes nothing.  An Ensemble: set on, and restored for, every member."""
 
     def __init__(self, model, half=False, dtype=None):
+        from .experimental import Ensemble
+
         self.dtype = dtype if dtype is not None else (torch.float16 if half else None)
-        self.target = None
+        self.targets = []
         if self.dtype is not None:
-            self.target = model if hasattr(model, "infer_dtype") else getattr(model, "model", None)   # (DetectMultiBackend wraps the model)
-            if not hasattr(self.target, "infer_dtype"):
-                raise TypeError("half= / dtype= need a yolov3_amd model (DetectionModel, or a DetectMultiBackend around one)")
+            inner = _engine_model(model)   # (DetectMultiBackend wraps the model)
+            self.targets = list(inner) if isinstance(inner, Ensemble) else [inner]
+            if not self.targets or not all(hasattr(t, "infer_dtype") for t in self.targets):
+                raise TypeError("half= / dtype= need a yolov3_amd model (DetectionModel or Ensemble, or a DetectMultiBackend around one)")
 
     def __enter__(self):
-        if self.target is not None:
-            self.saved = self.target.__dict__.get("infer_dtype", self)
-            self.target.infer_dtype = self.dtype
+        self.saved = [t.__dict__.get("infer_dtype", self) for t in self.targets]
+        for t in self.targets:
+            t.infer_dtype = self.dtype
         return self.dtype
 
     def __exit__(self, *exc):
-        if self.target is not None:
-            if self.saved is self:
-                self.target.__dict__.pop("infer_dtype", None)
+        for t, saved in zip(self.targets, self.saved):
+            if saved is self:
+                t.__dict__.pop("infer_dtype", None)
             else:
-                self.target.infer_dtype = self.saved
+                t.infer_dtype = saved
         return False
 
 
-def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, max_det=300, half=False, dtype=None):
+def _plan_dtype(model, scope):
+    """the dtype the forwards inside `scope` run in"""
+    from .experimental import Ensemble
+
+    inner = _engine_model(model)
+    first = inner[0] if isinstance(inner, Ensemble) and len(inner) else model
+    return scope.dtype or getattr(first, "infer_dtype", None) or next(model.parameters()).dtype
+
+
+def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, max_det=300, half=False, dtype=None, augment=False):
     """Throughput form of the `model(im)` -> `non_max_suppression(preds)` pair of reference val.py:364-376 / detect.py:196-200
     over a stream of batches: the NMS of batch i (a chain of small launches ending in the one device->host copy of the counts)
     runs on a second HIP stream while the forward of batch i+1 fills the CUs on the current stream.  Yields, in order and one
     batch late, the list of (n, 6) detections of every batch -- the same tensors the sequential pair returns.  `half` / `dtype`: run the forwards in that
-    precision from the parameters as they are (fp32 masters stay fp32); floating batches are cast to it, as DetectMultiBackend(fp16=True).forward does."""
+    precision from the parameters as they are (fp32 masters stay fp32); floating batches are cast to it, as DetectMultiBackend(fp16=True).forward does.
+    `augment`: ``model(x, augment=True)``, test-time augmentation (detect.py --augment).  `model` may be an Ensemble."""
     from .general import non_max_suppression
 
     cur = torch.cuda.current_stream()
@@ -101,7 +124,7 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
         with scope as dt:   # (per forward: a generator must not leave the model changed between its yields)
             if dt is not None and x.is_floating_point() and x.dtype != dt:
                 x = x.to(dt)
-            out = model(x)
+            out = model(x, augment=True) if augment else model(x)
         pred = out[0] if isinstance(out, (list, tuple)) else out
         ev = torch.cuda.Event()
         ev.record(cur)
@@ -112,17 +135,34 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
         yield finish(pending)
 
 
-def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False, half=False, dtype=None):
+def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False, half=False, dtype=None, augment=False, save_hybrid=False,
+                compute_loss=None):
     """The validation loop of reference val.py:351-428 over ``(im, targets, shapes)`` triples in the reference dataloader's format: im (bs, 3, h, w)
     (uint8 is scaled by 1 / 255 like val.py:358-359), targets (nl, 6) [image, class, x, y, w, h] normalised and grouped by image, shapes[i] =
     ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))).  The post-processing of batch i (NMS, scale_boxes, labels to native space, process_batch, the
     statistics and optionally the confusion matrix) runs on a second HIP stream while the forward of batch i + 1 fills the CUs, as in `detect_batches`;
     its only device->host copy is the NMS counts.  `half` (`dtype`): validate in float16 (that dtype) from the parameters as they are -- the reference's
-    ``validate.run(model=ema.ema, half=amp)`` (train.py:445) without casting the averaged fp32 weights to half and back.  Returns ((mp, mr, map50, map), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
+    ``validate.run(model=ema.ema, half=amp)`` (train.py:445) without casting the averaged fp32 weights to half and back.
+    `augment` (val.py:364): ``model(im, augment=True)``; ignored when `compute_loss` is given, as there.
+    `save_hybrid` (val.py:372): the batch's labels enter NMS as a-priori rows.  The forward writes the prediction straight into a buffer with a tail window
+    (engine.run_model's ``out=``), which y3_label_rows fills with the labels in pixels of the batch; the window is as high as the largest label count of one image when
+    the loader's targets are on the CPU, as the whole batch's otherwise (all-zero rows are never candidates), so nothing more is read back.
+    `compute_loss` (val.py:364-368; train.py:445-456 passes it every epoch): a ``ComputeLoss``; ``compute_loss(train_out, targets)[1]`` of every batch is summed on the
+    device and read back once, and the first element of the result becomes the reference's 7-tuple (mp, mr, map50, map, box, obj, cls): the sums divided by
+    the number of batches (val.py:449).  An Ensemble has no train output (None in the reference): TypeError.
+    Returns ((mp, mr, map50, map[, box, obj, cls]), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
     from . import ops
+    from .experimental import Ensemble
     from .general import _gain_pad, non_max_suppression_batched
     from .metrics import ConfusionMatrix, ValStats
 
+    inner = _engine_model(model)
+    if compute_loss is not None:
+        if isinstance(inner, Ensemble):
+            raise TypeError("compute_loss needs the raw head outputs of one model: an Ensemble's train output is None (reference models/experimental.py:85)")
+        augment = False   # val.py:364: `model(im) if compute_loss else (model(im, augment=augment), None)`
+    if save_hybrid and inner is None:
+        raise TypeError("save_hybrid needs a yolov3_amd model (DetectionModel or Ensemble, or a DetectMultiBackend around one)")
     cur = torch.cuda.current_stream()
     dev = cur.device
     side = torch.cuda.Stream(device=dev)
@@ -130,24 +170,27 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     stats = ValStats(nc, iouv, dev)
     cm = ConfusionMatrix(nc) if confusion else None
     scope = _infer_dtype(model, half, dtype)
-    dtype = scope.dtype or getattr(model, "infer_dtype", None) or next(model.parameters()).dtype
-    pending = None
+    dtype = _plan_dtype(model, scope)
+    loss = torch.zeros(3, device=dev) if compute_loss is not None else None
+    pending, seen = None, 0
 
     def finish(p):
-        pred, ev, targets, shapes, hw = p
+        pred, ev, targets, shapes, hw, tail = p
         bs = pred.shape[0]
         with torch.cuda.stream(side):
             side.wait_event(ev)
-            rows, counts, counts_list = non_max_suppression_batched(pred, conf_thres, iou_thres, None, single_cls, True, max_det)
-            if single_cls:
-                rows[:, :, 5] = 0
             tab = []
             for i in range(bs):
                 gain, px, py = _gain_pad(hw, shapes[i][0], shapes[i][1])
                 tab.append([gain, px, py, float(shapes[i][0][1]), float(shapes[i][0][0])])
             params = torch.tensor(tab, dtype=torch.float32).to(dev, non_blocking=True)
-            ops.scale_boxes_raw(rows, rows.stride(0), rows.stride(1), counts, bs, rows.shape[1], params)
             labels, offs = ops.labels_to_native(targets, bs, hw[1], hw[0], params)
+            if tail is not None:   # the a-priori rows behind the model's own, in pixels of the batch (val.py:371-372)
+                ops.label_rows(pred, tail[0], tail[1], targets, offs, hw[1], hw[0])
+            rows, counts, counts_list = non_max_suppression_batched(pred, conf_thres, iou_thres, None, single_cls, True, max_det)
+            if single_cls:
+                rows[:, :, 5] = 0
+            ops.scale_boxes_raw(rows, rows.stride(0), rows.stride(1), counts, bs, rows.shape[1], params)
             correct = process_batch_batched(rows, counts, labels, offs, iouv)
             stats.update(rows, counts, counts_list, correct, labels, offs)
             if cm is not None:
@@ -160,16 +203,46 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
             im = im.to(dtype) / 255
         elif im.dtype != dtype:
             im = im.to(dtype)
+        extra = 0
+        if save_hybrid and targets.shape[0]:
+            if targets.device.type == "cpu":   # the loader's own tensor: the largest label count of one image, counted on the host
+                extra = int(torch.bincount(targets[:, 0].long().clamp_(0, im.shape[0])).max())
+            else:
+                extra = int(targets.shape[0])
         targets = targets.to(dev, torch.float32, non_blocking=True).contiguous()
+        tail = None
         with scope:
-            out = model(im)
-        pred = out[0] if isinstance(out, (list, tuple)) else out
+            if extra and compute_loss is None:
+                rows = _pred_rows(inner, im, augment)
+                pred = torch.empty(im.shape[0], rows + extra, (inner[0] if isinstance(inner, Ensemble) else inner).model[-1].no, dtype=dtype, device=dev)
+                inner._predict_into(im, (pred, 0), augment)
+                tail = (rows, extra)
+            else:
+                out = model(im, augment=True) if augment else model(im)
+                pred = out[0] if isinstance(out, (list, tuple)) else out
+                if compute_loss is not None:
+                    with torch.no_grad():
+                        loss += compute_loss(out[1], targets)[1]   # box, obj, cls (val.py:368), with the normalised targets
+                if extra:   # (compute_loss keeps the raw tensors, which the windowed forward does not write: the prediction is widened by one copy instead)
+                    wide = torch.empty(pred.shape[0], pred.shape[1] + extra, pred.shape[2], dtype=pred.dtype, device=dev)
+                    wide[:, : pred.shape[1]].copy_(pred)
+                    pred, tail = wide, (pred.shape[1], extra)
         ev = torch.cuda.Event()
         ev.record(cur)
         if pending is not None:
             finish(pending)
-        pending = (pred, ev, targets, shapes, tuple(im.shape[2:]))
+        pending = (pred, ev, targets, shapes, tuple(im.shape[2:]), tail)
+        seen += 1
     if pending is not None:
         finish(pending)
     res = stats.results()
+    if loss is not None:
+        res = (*res, *(loss.cpu() / max(seen, 1)).tolist())
     return (res, stats.maps(nc), stats, cm) if confusion else (res, stats.maps(nc), stats)
+
+
+def _pred_rows(model, im, augment):
+    """rows of `model(im, augment)[0]`, on the host (engine.pred_rows; an Ensemble: the sum over its members)"""
+    from .engine import pred_rows
+
+    return model.pred_rows(im.shape[2], im.shape[3], augment) if hasattr(model, "pred_rows") else pred_rows(model, im.shape[2], im.shape[3], augment)

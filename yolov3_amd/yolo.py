@@ -152,14 +152,14 @@ class BaseModel(nn.Module):
     def forward(self, x, profile=False, visualize=False):
         return self._forward_once(x, profile, visualize)
 
-    def _forward_once(self, x, profile=False, visualize=False):
+    def _forward_once(self, x, profile=False, visualize=False, _out=None):
         """Whole-graph execution on the GPU (reference :135-147 walks modules one by one; here the graph is
-        compiled once per input shape into a static plan of HIP launches)."""
+        compiled once per input shape into a static plan of HIP launches).  `_out` = (buffer, row_offset): engine.run_model's windowed form."""
         if visualize:
             raise NotImplementedError("feature visualisation is outside the accelerated hot path")
         from .engine import run_model
 
-        return run_model(self, x, profile=profile)
+        return run_model(self, x, profile=profile, out=_out)
 
     def fuse(self):
         """Fold every Conv's BatchNorm (reference :163-172)."""
@@ -232,44 +232,40 @@ class DetectionModel(BaseModel):
             return self._forward_augment(x)
         return self._forward_once(x, profile, visualize)
 
-    def _forward_augment(self, x):
+    def _predict_into(self, x, out, augment=False, profile=False):
+        """the decoded prediction of `self(x, augment)` written into rows [row_offset, ...) of out = (buffer, row_offset) (engine.check_window); returns the rows written"""
+        if augment:
+            return self._forward_augment(x, _out=out)
+        return self._forward_once(x, profile, False, _out=out)
+
+    def _forward_augment(self, x, _out=None):
         """Test-time augmentation (reference :239-276): the batch at scales 1 / 0.83 / 0.67, the middle one mirrored left-right, each through the
         engine; the decoded predictions de-scaled / de-mirrored and concatenated without the stride-32 rows of the full-size pass and the stride-8
         rows of the smallest one (_clip_augmented).  The mirror + resize + pad and the de-scale + row selection are one kernel each
-        (csrc/val_edge.hip); the concatenated tensor is written once."""
+        (csrc/val_edge.hip); the concatenated tensor is written once.  `_out` = (buffer, row_offset): the three passes go into that window of the caller's
+        buffer instead (engine.check_window) and the number of rows written is returned."""
         if self.training:
             raise RuntimeError("augmented inference is an eval-mode path (the reference indexes the decoded prediction of eval mode)")
         from . import ops
+        from .engine import check_window, tta_windows
 
         img_size = x.shape[-2:]
-        scales, flips = [1, 0.83, 0.67], [None, 3, None]
         gs = int(self.stride.max())
-        det = self.model[-1]
-        nl, no = det.nl, det.no
-        g = sum(4**k for k in range(nl))
-        strides = [int(v) for v in self.stride.tolist()]
-        # the row windows first (the decoded prediction of an (h, w) pass has na * sum_l (h / s_l)(w / s_l) rows): the result is allocated once and every
-        # pass is de-scaled into its window as soon as it is through the engine
-        windows = []
-        for i, si in enumerate(scales):
-            h, w = (img_size if si == 1 else (math.ceil(d * si / gs) * gs for d in img_size))
-            rows = det.na * sum((h // s) * (w // s) for s in strides)
-            lo, hi = 0, rows
-            if i == 0:
-                hi = rows - (rows // g) * 1                    # without the tail: the coarsest level of the full-size pass
-            if i == len(scales) - 1:
-                lo = (rows // g) * 4 ** (nl - 1)               # without the head: the finest level of the smallest pass
-            windows.append((rows, lo, hi - lo))
-        out, off = None, 0
-        for (rows, lo, n), si, fi in zip(windows, scales, flips):
+        no = self.model[-1].no
+        # the row windows first (engine.tta_windows: host arithmetic on (h, w)): the result is allocated once and every pass is de-scaled into its window as
+        # soon as it is through the engine
+        passes = tta_windows(self, int(img_size[0]), int(img_size[1]))
+        total = sum(p[5] for p in passes)
+        out, off = (None, 0) if _out is None else check_window(self, x, _out, augment=True)[:2]
+        for si, fi, _, rows, lo, n in passes:
             yi = self._forward_once(ops.scale_img(x, si, gs=gs, flip_lr=fi == 3))[0]
             if yi.shape[1] != rows or yi.shape[2] != no:
                 raise RuntimeError(f"augmented pass at scale {si}: {tuple(yi.shape)} rows, expected {rows} x {no}")
             if out is None:
-                out = torch.empty(yi.shape[0], sum(w[2] for w in windows), no, dtype=yi.dtype, device=yi.device)
+                out = torch.empty(yi.shape[0], total, no, dtype=yi.dtype, device=yi.device)
             ops.descale_pred_into(yi.contiguous(), lo, n, si, fi, img_size, out, off)
             off += n
-        return out, None
+        return (out, None) if _out is None else total
 
     def _initialize_biases(self, cf=None):
         """Detect bias prior (reference :282-292): obj += log(8/(640/s)^2), cls += log(0.6/(nc-0.99999))."""
