@@ -75,8 +75,8 @@ void y3_tune_reset(void);                        /* defaults + Y3_TUNE again */
 
 /* number of elements (of `dtype`) of a packed filter bank for (cout, cin, ksize).  ALWAYS size banks with this call: a 3x3 bank with cout % 256 == 0 and
  * cin % 32 == 0 is TWO copies -- the row-major one every kernel reads, followed by a fragment-ordered one (per 64-row wave and K-step a contiguous 4 KiB block
- * of four MFMA A fragments) that the persistent 3x3 kernel loads straight into registers (csrc/conv_v10.h, csrc/y3_common.h::y3_frag_index).  Every packer
- * below (y3_pack_filter, _dgrad, _pair, _jobs) writes both (ABI version 2). */
+ * of four MFMA A fragments) that the persistent 3x3 kernel loads straight into registers (csrc/conv_v10.h, csrc/filter_bank.h::y3_frag_index).  Every packer
+ * below (y3_pack_filter, _dgrad, _pair, _jobs) writes both (ABI version 2).  Every layout is defined in csrc/filter_bank.h, every packer lives in csrc/filter_bank.hip. */
 size_t y3_packed_filter_elems(int32_t cout, int32_t cin, int32_t ksize);
 /* OIHW fp32 (cout_src x cin_src x k x k) -> packed [cout_pad][k*k*cin_pad (+K pad)] in `dtype`;
  * `cout`/`cin` are the padded logical sizes used by y3_conv2d_fwd (>= the source sizes; pad = 0).

@@ -1,4 +1,4 @@
-"""CPU tests of the EMA-model / checkpoint surface: the two exports behind it (y3_ema_update in csrc/optim.hip, y3_fold_pack_jobs in csrc/train.hip) are declared, bound,
+"""CPU tests of the EMA-model / checkpoint surface: the two exports behind it (y3_ema_update in csrc/optim.hip, y3_fold_pack_jobs in csrc/filter_bank.hip) are declared, bound,
 exported and validate their arguments without a GPU; ModelEMA is backed by a real module; save_checkpoint / smart_resume / strip_optimizer / attempt_load round-trip
 the reference's checkpoint dict on CPU objects (no launch is needed for any of it)."""
 import re

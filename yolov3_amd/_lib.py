@@ -38,6 +38,17 @@ class Y3ConvDesc(C.Structure):
     ]
 
 
+class Y3PackJob(C.Structure):   # y3_pack_job: one record of the device table of y3_pack_filter_jobs (48 bytes)
+    _fields_ = [("w", C.c_void_p), ("packed_fwd", C.c_void_p), ("packed_dgrad", C.c_void_p), ("cout_src", C.c_int32), ("cin_src", C.c_int32), ("ksize", C.c_int32),
+                ("cout", C.c_int32), ("cin", C.c_int32), ("first_block", C.c_int32)]
+
+
+class Y3FoldPackJob(C.Structure):   # y3_fold_pack_job: one record of the device table of y3_fold_pack_jobs (96 bytes)
+    _fields_ = [("w", C.c_void_p), ("conv_bias", C.c_void_p), ("bn_gamma", C.c_void_p), ("bn_beta", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
+                ("packed", C.c_void_p), ("bias", C.c_void_p), ("bn_eps", C.c_float), ("cout_src", C.c_int32), ("cin_src", C.c_int32), ("ksize", C.c_int32),
+                ("cout", C.c_int32), ("cin", C.c_int32), ("stem", C.c_int32), ("first_block", C.c_int32)]
+
+
 class Y3NmsParams(C.Structure):
     _fields_ = [
         ("iou_thres", C.c_double),

@@ -32,6 +32,7 @@ SOURCES = [
     ("autoanchor.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
+    ("filter_bank.hip", []),
     ("optim.hip", ["-ffp-contract=off"]),
     ("api.cpp", []),
 ]

@@ -971,25 +971,6 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvArgs p) {
     }
 }
 
-// OIHW fp32 -> packed [rows][Kpad] T, K = (kh, kw, cin_pad)
-template <typename T>
-__global__ void pack_filter_kernel(const float* __restrict__ src, int cout_src, int cin_src, int ks, int cin, int rows,
-                                   int kpad, T* __restrict__ dst, int frag) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)rows * kpad;
-    if (idx >= total) return;
-    const int k = (int)(idx % kpad);
-    const int co = (int)(idx / kpad);
-    float v = 0.0f;
-    if (co < cout_src && k < ks * ks * cin) {
-        const int tap = k / cin, ci = k - tap * cin;
-        const int kh = tap / ks, kw = tap - kh * ks;
-        if (ci < cin_src) v = src[(((long long)co * cin_src + ci) * ks + kh) * ks + kw];
-    }
-    dst[idx] = from_f32<T>(v);
-    if (frag && k < 9 * cin) dst[total + y3_frag_index(co, k, cin)] = from_f32<T>(v);   // the copy conv_v10.h reads
-}
-
 template <typename T, int BK, int WAVES_C, int WAVES_P, int MC, int MP, bool SMALLC>
 int launch_igemm(ConvArgs& a, hipStream_t st) {
     tile_fill(a, BK);
@@ -1131,29 +1112,6 @@ template <typename T> int conv_launch(ConvArgs& a, const ConvPlan& p, hipStream_
 }
 
 }  // namespace
-
-extern "C" size_t y3_packed_filter_elems(int32_t cout, int32_t cin, int32_t ksize) {
-    return (size_t)y3_filter_rows(cout) * (size_t)y3_filter_kpad(cin, ksize) * (y3_filter_has_frag(cout, cin, ksize) ? 2 : 1);
-}
-
-extern "C" int y3_pack_filter(const float* w, int32_t cout_src, int32_t cin_src, int32_t ks, int32_t cout, int32_t cin,
-                              int32_t dtype, void* packed, void* stream) {
-    if (!w || !packed) Y3_FAIL("y3_pack_filter: null pointer");
-    if (cout < cout_src || cin < cin_src || (cin % 8) != 0) Y3_FAIL("y3_pack_filter: bad padded sizes cout=%d cin=%d", cout, cin);
-    const int rows = y3_filter_rows(cout), kpad = y3_filter_kpad(cin, ks);
-    const long long total = (long long)rows * kpad;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    const int frag = y3_filter_has_frag(cout, cin, ks) ? 1 : 0;   // 3x3 banks of >= 256-filter layers: a second, fragment-ordered copy behind the row-major one
-    switch (dtype) {
-        case Y3_F16: hipLaunchKernelGGL((pack_filter_kernel<f16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, ks, cin, rows, kpad, (f16_t*)packed, frag); break;
-        case Y3_BF16: hipLaunchKernelGGL((pack_filter_kernel<bf16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, ks, cin, rows, kpad, (bf16_t*)packed, frag); break;
-        case Y3_F32: hipLaunchKernelGGL((pack_filter_kernel<float>), grid, dim3(256), 0, st, w, cout_src, cin_src, ks, cin, rows, kpad, (float*)packed, frag); break;
-        default: Y3_FAIL("y3_pack_filter: bad dtype %d", dtype);
-    }
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
 
 // ---- step 1: validate the call and fill the arguments of the whole batch and the image ranges it is launched as ----
 struct ConvProblem {
@@ -1479,20 +1437,8 @@ extern "C" int y3_conv2d_fwd_bnin_stats(const y3_conv_desc* d, const y3_tensor* 
 // pixels split into four parity classes (hi%2, wi%2); class (ph, pw) only ever meets the taps kh = 1 (ph = 0) or
 // kh in {0, 2} (ph = 1), likewise for kw -> 1 + 2 + 2 + 4 = 9 taps in total, i.e. exactly the forward MACs.  Each class is
 // a stride-1 conv of du with its own small tap table and filter bank, written to every second pixel of the gradient.
+// (S2Class, s2_class and the banks' geometry: filter_bank.h)
 namespace {
-struct S2Class {
-    int nh, nw;
-    int kh[2], dh[2], kw[2], dw[2];
-};
-S2Class s2_class(int ph, int pw) {
-    S2Class c;
-    memset(&c, 0, sizeof(c));
-    if (ph == 0) { c.nh = 1; c.kh[0] = 1; c.dh[0] = 0; } else { c.nh = 2; c.kh[0] = 0; c.dh[0] = 1; c.kh[1] = 2; c.dh[1] = 0; }
-    if (pw == 0) { c.nw = 1; c.kw[0] = 1; c.dw[0] = 0; } else { c.nw = 2; c.kw[0] = 0; c.dw[0] = 1; c.kw[1] = 2; c.dw[1] = 0; }
-    return c;
-}
-size_t s2_bank_elems(int cout, int cin, int ntaps) { return (size_t)y3_filter_rows(cin) * y3_round_up((size_t)ntaps * cout, 64); }
-
 // the four classes as one launch of the v3 tile that the plan of class `big`, the one with the most taps, chose
 template <typename T> int launch_v3_quad(const ConvArgs* cls, int big, const ConvPlan& p, hipStream_t st) {
     ConvArgs lead = cls[big];
@@ -1501,53 +1447,11 @@ template <typename T> int launch_v3_quad(const ConvArgs* cls, int big, const Con
     return conv_launch<T>(lead, p, st, cls);
 }
 
-template <typename T>
-__global__ void pack_dgrad_s2_kernel(const float* __restrict__ src, int cout_src, int cin_src, int cout, int rows, int kpad, int nh, int nw, int kh0, int kh1, int kw0,
-                                     int kw1, T* __restrict__ dst) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)rows * kpad) return;
-    const int k = (int)(idx % kpad), ci = (int)(idx / kpad);
-    float v = 0.0f;
-    if (ci < cin_src && k < nh * nw * cout) {
-        const int tap = k / cout, co = k - tap * cout;
-        const int kh = (tap / nw) ? kh1 : kh0, kw = (tap % nw) ? kw1 : kw0;
-        if (co < cout_src) v = src[(((long long)co * cin_src + ci) * 3 + kh) * 3 + kw];
-    }
-    dst[idx] = from_f32<T>(v);
-}
 }  // namespace
 
 #ifdef Y3_TIMELINE
 extern "C" void y3_debug_timeline(void* buf) { g_timeline = (unsigned long long*)buf; }
 #endif
-
-extern "C" size_t y3_packed_filter_dgrad_s2_elems(int32_t cout, int32_t cin) {
-    return s2_bank_elems(cout, cin, 1) + 2 * s2_bank_elems(cout, cin, 2) + s2_bank_elems(cout, cin, 4);
-}
-
-extern "C" int y3_pack_filter_dgrad_s2(const float* w, int32_t cout_src, int32_t cin_src, int32_t cout, int32_t cin, int32_t dtype, void* packed, void* stream) {
-    if (!w || !packed) Y3_FAIL("y3_pack_filter_dgrad_s2: null pointer");
-    if (cout < cout_src || cin < cin_src || (cout % 8) || (cin % 8)) Y3_FAIL("y3_pack_filter_dgrad_s2: bad padded sizes");
-    hipStream_t st = (hipStream_t)stream;
-    size_t off = 0;
-    const int esz = dtype == Y3_F32 ? 4 : 2;
-    for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-            const S2Class c = s2_class(ph, pw);
-            const int rows = y3_filter_rows(cin), kpad = (int)y3_round_up((size_t)c.nh * c.nw * cout, 64);
-            const long long total = (long long)rows * kpad;
-            const dim3 grid((unsigned)((total + 255) / 256));
-            void* dst = (char*)packed + off * esz;
-            switch (dtype) {
-                case Y3_F16: hipLaunchKernelGGL((pack_dgrad_s2_kernel<f16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, cout, rows, kpad, c.nh, c.nw, c.kh[0], c.kh[1], c.kw[0], c.kw[1], (f16_t*)dst); break;
-                case Y3_BF16: hipLaunchKernelGGL((pack_dgrad_s2_kernel<bf16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, cout, rows, kpad, c.nh, c.nw, c.kh[0], c.kh[1], c.kw[0], c.kw[1], (bf16_t*)dst); break;
-                default: Y3_FAIL("y3_pack_filter_dgrad_s2: f16/bf16 only");
-            }
-            Y3_CHECK_LAUNCH();
-            off += (size_t)total;
-        }
-    return 0;
-}
 
 extern "C" int y3_conv2d_dgrad_s2(int32_t dtype, const y3_tensor* du, const void* packed4, const y3_tensor* residual, const y3_tensor* gx, void* stream) {
     if (!du || !packed4 || !gx) Y3_FAIL("y3_conv2d_dgrad_s2: null argument");
@@ -1560,16 +1464,16 @@ extern "C" int y3_conv2d_dgrad_s2(int32_t dtype, const y3_tensor* du, const void
     if ((long long)gx->n * H * W > 0x7fffffffLL) Y3_FAIL("y3_conv2d_dgrad_s2: too many gradient pixels");
     hipStream_t st = (hipStream_t)stream;
     const int cout = du->c, cin = gx->c;
-    size_t off = 0;
+    const S2Banks banks = s2_banks(cout, cin);   // filter_bank.h: what y3_pack_filter_dgrad_s2 wrote
     ConvArgs cls[4];
     bool live[4];
     for (int ph = 0; ph < 2; ++ph)
         for (int pw = 0; pw < 2; ++pw) {
             const S2Class c = s2_class(ph, pw);
             const int ntaps = c.nh * c.nw;
-            const int kpad = (int)y3_round_up((size_t)ntaps * cout, 64);
+            const int kpad = banks.kpad[ph * 2 + pw];
             const int Hc = (H - ph + 1) / 2, Wc = (W - pw + 1) / 2;
-            const size_t bank = (size_t)y3_filter_rows(cin) * kpad;
+            const size_t bank = (size_t)banks.rows * kpad, off = banks.off[ph * 2 + pw];
             ConvArgs& a = cls[ph * 2 + pw];
             live[ph * 2 + pw] = Hc > 0 && Wc > 0;
             memset(&a, 0, sizeof(a));
@@ -1592,7 +1496,6 @@ extern "C" int y3_conv2d_dgrad_s2(int32_t dtype, const y3_tensor* du, const void
                 a.r_bytes = rb < 0x7fffffffLL ? (unsigned)rb : 0u;
                 if (!a.x_bytes || !a.w_bytes || !a.y_bytes || (residual && !a.r_bytes)) Y3_FAIL("y3_conv2d_dgrad_s2: tensor too large");
             }
-            off += bank;
         }
     // all four classes in ONE launch when they share the geometry (even H and W) and the dispatcher picks a v3 tile for the class with
     // the longest K loop (the 4-tap class: its variant suits the shorter ones); knob "dgrad_quad" = 0 keeps the four launches (A/B)

@@ -9,7 +9,7 @@
 // r(m) + dh (W + 2) + dw, so dw * 80 and the k-substep are instruction immediates and there are no edge masks) -- and changes the three
 // things its ablation (profiles/r03_v9_ablation.txt) priced:
 //   * FILTER FRAGMENTS BY REGISTER LOADS.  The packed bank of an eligible layer carries a second, fragment-ordered copy
-//     (y3_frag_index, y3_common.h): the 4 KiB a wave needs for one K-step are contiguous and lane-ordered, so a K-step's filter operand is
+//     (y3_frag_index, filter_bank.h; written by the packers of filter_bank.hip): the 4 KiB a wave needs for one K-step are contiguous and lane-ordered, so a K-step's filter operand is
 //     four 1 KiB `buffer_load_dwordx4` into a ring of three register sets, two K-steps ahead.  No LDS-DMA requests, no LDS stages and no
 //     `ds_read` for that operand: 14 instead of 18 fragment reads per K-step (measured -7 % as ablation arm 9).
 //   * PERSISTENT BLOCKS OVER 32-PIXEL COLUMN BLOCKS.  The pixel axis is cut into column blocks of 32 pixels; the blocks of a filter tile

@@ -785,17 +785,6 @@ __global__ __launch_bounds__(C * 4, C == 64 ? 2 : 1) void bneck_pair_kernel(cons
     }
 }
 
-template <typename T>
-__global__ void pack_stem_kernel(const float* __restrict__ src, int cout_src, int cin_src, int rows, T* __restrict__ dst) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * 48) return;
-    const int k = idx % 16, kh = (idx / 16) % 3, co = idx / 48;
-    const int kw = k >> 2, c = k & 3;
-    float v = 0.0f;
-    if (co < cout_src && kw < 3 && c < cin_src) v = src[(((long long)co * cin_src + c) * 3 + kh) * 3 + kw];
-    dst[idx] = from_f32<T>(v);
-}
-
 template <typename T, typename S> int launch_stem(const StemArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)((long long)a.tiles_w * a.tiles_h * a.N));
     if (a.Cout <= 32)
@@ -817,23 +806,6 @@ template <typename T> int dispatch_src(const StemArgs& a, int sdt, hipStream_t s
 }
 
 }  // namespace
-
-extern "C" size_t y3_packed_filter_stem_elems(int32_t cout) { return (size_t)((cout + 31) / 32) * 32 * 48; }
-
-extern "C" int y3_pack_filter_stem(const float* w, int32_t cout_src, int32_t cin_src, int32_t cout, int32_t dtype, void* packed, void* stream) {
-    if (!w || !packed) Y3_FAIL("y3_pack_filter_stem: null pointer");
-    if (cin_src < 1 || cin_src > 4 || cout < cout_src) Y3_FAIL("y3_pack_filter_stem: needs 1..4 input channels and cout >= cout_src");
-    const int rows = (cout + 31) / 32 * 32;
-    const dim3 grid((unsigned)((rows * 48 + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case Y3_F16: hipLaunchKernelGGL((pack_stem_kernel<f16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, rows, (f16_t*)packed); break;
-        case Y3_BF16: hipLaunchKernelGGL((pack_stem_kernel<bf16_t>), grid, dim3(256), 0, st, w, cout_src, cin_src, rows, (bf16_t*)packed); break;
-        default: Y3_FAIL("y3_pack_filter_stem: f16/bf16 only");
-    }
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
 
 static int stem_conv_impl(const void* x_nchw, int32_t src_dtype, int32_t n, int32_t cin, int32_t h, int32_t w, float divisor, const void* packed, const float* bias,
                           int32_t dtype, int32_t act, const y3_tensor* y, float* stat_rows, int64_t capacity_rows, int64_t* n_rows, void* stream, const char* who) {

@@ -962,207 +962,6 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ 
     if (threadIdx.x == 0) out[c] = red[0];
 }
 
-// OIHW fp32 -> data-gradient filter bank: rows = cin, K = (kh', kw', cout) with the taps flipped
-template <typename T>
-__global__ void pack_filter_dgrad_kernel(const float* __restrict__ src, int cout_src, int cin_src, int ks, int cout, int rows, int kpad, T* __restrict__ dst, int frag) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)rows * kpad;
-    if (idx >= total) return;
-    const int k = (int)(idx % kpad);
-    const int ci = (int)(idx / kpad);
-    float v = 0.0f;
-    if (ci < cin_src && k < ks * ks * cout) {
-        const int tap = k / cout, co = k - tap * cout;
-        const int kh = ks - 1 - tap / ks, kw = ks - 1 - tap % ks;
-        if (co < cout_src) v = src[(((long long)co * cin_src + ci) * ks + kh) * ks + kw];
-    }
-    dst[idx] = from_f32<T>(v);
-    if (frag && k < 9 * cout) dst[total + y3_frag_index(ci, k, cout)] = from_f32<T>(v);   // the copy conv_v10.h reads (y3_common.h)
-}
-
-// both filter banks of a training step from the fp32 master weights in one launch: the forward bank [cout][kh][kw][cin] and the
-// data-gradient bank [cin][kh'][kw'][cout] (flipped taps) -- 145 ~7 us pack launches per step become 75
-template <typename T>
-__global__ void pack_filter_pair_kernel(const float* __restrict__ src, int cout_src, int cin_src, int ks, int cout, int cin, int rows_f, int kpad_f, int rows_d, int kpad_d,
-                                        T* __restrict__ dst_f, T* __restrict__ dst_d) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx < (long long)rows_f * kpad_f) {
-        const int k = (int)(idx % kpad_f), co = (int)(idx / kpad_f);
-        float v = 0.0f;
-        if (co < cout_src && k < ks * ks * cin) {
-            const int tap = k / cin, ci = k - tap * cin;
-            const int kh = tap / ks, kw = tap - kh * ks;
-            if (ci < cin_src) v = src[(((long long)co * cin_src + ci) * ks + kh) * ks + kw];
-        }
-        dst_f[idx] = from_f32<T>(v);
-        if (y3_filter_has_frag(cout, cin, ks) && k < 9 * cin) dst_f[(long long)rows_f * kpad_f + y3_frag_index(co, k, cin)] = from_f32<T>(v);   // the copies conv_v10.h reads
-    }
-    if (idx < (long long)rows_d * kpad_d) {
-        const int k = (int)(idx % kpad_d), ci = (int)(idx / kpad_d);
-        float v = 0.0f;
-        if (ci < cin_src && k < ks * ks * cout) {
-            const int tap = k / cout, co = k - tap * cout;
-            const int kh = ks - 1 - tap / ks, kw = ks - 1 - tap % ks;
-            if (co < cout_src) v = src[(((long long)co * cin_src + ci) * ks + kh) * ks + kw];
-        }
-        dst_d[idx] = from_f32<T>(v);
-        if (y3_filter_has_frag(cin, cout, ks) && k < 9 * cout) dst_d[(long long)rows_d * kpad_d + y3_frag_index(ci, k, cout)] = from_f32<T>(v);
-    }
-}
-
-// Every layer's banks in ONE launch: the training step re-packs all filters each step (the fp32 master weights moved); 75 pack launches of 4-40 us (0.8 ms per
-// batch-64 step, most of it launch-to-launch latency) became one in round 3.  Round 5: SOURCE-indexed tiles.  The destination-indexed form (a thread per bank element,
-// like the single-layer packers above) gathered the weights with a stride of 9 floats for the forward bank and of 9 Cin floats for the data-gradient bank -- 1.6 GB of
-// reads for 248 MB of weights, 0.54 ms.  Now a block owns a 32-filter x 32-channel tile: it reads the tile's 32 x (32 k k) floats as 32 contiguous runs, keeps them as T
-// in LDS ([tap][filter][channel]) and writes the four destinations -- forward bank (32 consecutive channels of a (filter, tap) = 64 bytes), data-gradient bank (32
-// consecutive filters of a (channel, flipped tap)), and the fragment-ordered copies of either -- from there.  ONLY the elements that come from a weight are written: row
-// padding (filters / channels beyond the source's) and K padding stay what they are, so the caller zero-fills a bank ONCE when it allocates it (ops.PackJobs does).
-// A block finds its job by a binary search over the jobs' first block (wave-uniform scalar loads).
-template <typename T>
-__global__ __launch_bounds__(256) void pack_filter_jobs_kernel(const y3_pack_job* __restrict__ jobs, int n_jobs) {
-    __shared__ T tile[9][32][34];   // (34: the transposed read of the data-gradient pass walks the filter index: 17 dwords apart)
-    int lo = 0, hi = n_jobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const y3_pack_job j = jobs[lo];
-    const float* __restrict__ src = j.w;
-    const int ks = j.ksize, KK = ks * ks, cin = j.cin, cout = j.cout;
-    const int n_tci = (cin + 31) / 32;
-    const int t = (int)blockIdx.x - j.first_block;
-    const int co0 = (t / n_tci) * 32, ci0 = (t % n_tci) * 32;
-    if (co0 >= j.cout_src || ci0 >= j.cin_src) return;   // a tile of padding only (uniform)
-    const int tid = threadIdx.x;
-    for (int e = tid; e < 32 * 32 * KK; e += 256) {
-        const int co_l = e / (32 * KK), r = e - co_l * (32 * KK);
-        const int ci_l = r / KK, tap = r - ci_l * KK;
-        const int co = co0 + co_l, ci = ci0 + ci_l;
-        float v = 0.0f;
-        if (co < j.cout_src && ci < j.cin_src) v = src[((long long)co * j.cin_src + ci) * KK + tap];
-        tile[tap][co_l][ci_l] = from_f32<T>(v);
-    }
-    __syncthreads();
-    const int rows_f = (cout + 127) / 128 * 128, kpad_f = (KK * cin + 63) / 64 * 64;
-    const int rows_d = (cin + 127) / 128 * 128, kpad_d = (KK * cout + 63) / 64 * 64;
-    if (j.packed_fwd) {
-        T* __restrict__ dst = (T*)j.packed_fwd;
-        const bool frag = y3_filter_has_frag(cout, cin, ks);
-        for (int e = tid; e < 32 * 32 * KK; e += 256) {
-            const int ci_l = e & 31, co_l = (e >> 5) & 31, tap = e >> 10;
-            const int co = co0 + co_l, ci = ci0 + ci_l;
-            if (co < j.cout_src && ci < j.cin_src) {
-                const T v = tile[tap][co_l][ci_l];
-                const int k = tap * cin + ci;
-                dst[(long long)co * kpad_f + k] = v;
-                if (frag) dst[(long long)rows_f * kpad_f + y3_frag_index(co, k, cin)] = v;   // the copy conv_v10.h reads (y3_common.h)
-            }
-        }
-    }
-    if (j.packed_dgrad) {
-        T* __restrict__ dst = (T*)j.packed_dgrad;
-        const bool frag = y3_filter_has_frag(cin, cout, ks);
-        for (int e = tid; e < 32 * 32 * KK; e += 256) {
-            const int co_l = e & 31, ci_l = (e >> 5) & 31, tap = e >> 10;
-            const int co = co0 + co_l, ci = ci0 + ci_l;
-            if (co < j.cout_src && ci < j.cin_src) {
-                const T v = tile[tap][co_l][ci_l];
-                const int k = (KK - 1 - tap) * cout + co;   // flipped tap (kh, kw) -> (ks - 1 - kh, ks - 1 - kw)
-                dst[(long long)ci * kpad_d + k] = v;
-                if (frag) dst[(long long)rows_d * kpad_d + y3_frag_index(ci, k, cout)] = v;
-            }
-        }
-    }
-}
-
-// ---- inference plans: Conv + BatchNorm fold and pack of EVERY layer in one launch (y3_fold_pack_jobs) ------------------------------------------------------------
-// The algebra of upstream fuse_conv_and_bn as yolov3_amd/engine.py::_fold evaluates it with torch, operation for operation: IEEE sqrt and division, every product and
-// sum rounded on its own (no FMA contraction in these two functions, whatever the file is built with) -- the banks equal the ones _fold + y3_pack_filter write, bit for bit.
-__device__ __forceinline__ float fold_scale(float gamma, float var, float eps) {
-#pragma clang fp contract(off)
-    return gamma / sqrtf(eps + var);
-}
-__device__ __forceinline__ float fold_bias(float scale, float b, float gamma, float beta, float mean, float var, float eps) {
-#pragma clang fp contract(off)
-    const float gm = gamma * mean;
-    const float b_bn = beta - gm / sqrtf(var + eps);
-    const float sb = scale * b;
-    return sb + b_bn;
-}
-
-// The tiling of pack_filter_jobs_kernel (a block owns 32 filters x 32 channels of one job, found by a binary search over first_block); the weights are scaled by their
-// filter's BatchNorm factor on the way into LDS and leave in the layout of y3_pack_filter (+ the fragment-ordered copy) or, for a `stem` job, of y3_pack_filter_stem
-// ([filter][kh][kw * 4 + channel]).  The block of channel tile 0 also writes its 32 entries of the fp32 bias vector.  Only elements that come from a weight are written:
-// banks and bias vectors are zero-filled once by the caller.
-template <typename T>
-__global__ __launch_bounds__(256) void fold_pack_jobs_kernel(const y3_fold_pack_job* __restrict__ jobs, int n_jobs) {
-    __shared__ T tile[9][32][34];
-    __shared__ float sc[32];
-    int lo = 0, hi = n_jobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const y3_fold_pack_job j = jobs[lo];
-    const float* __restrict__ src = j.w;
-    const int ks = j.ksize, KK = ks * ks, cin = j.cin, cout = j.cout;
-    const int n_tci = (cin + 31) / 32;
-    const int t = (int)blockIdx.x - j.first_block;
-    const int co0 = (t / n_tci) * 32, ci0 = (t % n_tci) * 32;
-    if (co0 >= j.cout_src || ci0 >= j.cin_src) return;   // a tile of padding only (uniform)
-    const int tid = threadIdx.x;
-    const bool bn = j.bn_gamma != nullptr;
-    if (tid < 32) {
-        const int co = co0 + tid;
-        float s = 1.0f;
-        if (co < j.cout_src) {
-            if (bn) s = fold_scale(j.bn_gamma[co], j.bn_var[co], j.bn_eps);
-            if (ci0 == 0) {
-                const float b = j.conv_bias ? j.conv_bias[co] : 0.0f;
-                j.bias[co] = bn ? fold_bias(s, b, j.bn_gamma[co], j.bn_beta[co], j.bn_mean[co], j.bn_var[co], j.bn_eps) : b;
-            }
-        }
-        sc[tid] = s;
-    }
-    __syncthreads();
-    for (int e = tid; e < 32 * 32 * KK; e += 256) {
-        const int co_l = e / (32 * KK), r = e - co_l * (32 * KK);
-        const int ci_l = r / KK, tap = r - ci_l * KK;
-        const int co = co0 + co_l, ci = ci0 + ci_l;
-        float v = 0.0f;
-        if (co < j.cout_src && ci < j.cin_src) {
-            v = src[((long long)co * j.cin_src + ci) * KK + tap];
-            if (bn) v = sc[co_l] * v;
-        }
-        tile[tap][co_l][ci_l] = from_f32<T>(v);
-    }
-    __syncthreads();
-    T* __restrict__ dst = (T*)j.packed;
-    if (j.stem) {   // ksize 3, <= 4 channels (checked by the host mirror): one channel tile
-        for (int e = tid; e < 32 * 4 * 9; e += 256) {
-            const int c = e & 3, co_l = (e >> 2) & 31, tap = e >> 7;
-            const int co = co0 + co_l;
-            if (co < j.cout_src && c < j.cin_src) {
-                const int kh = tap / 3, kw = tap - kh * 3;
-                dst[(long long)co * 48 + kh * 16 + kw * 4 + c] = tile[tap][co_l][c];
-            }
-        }
-        return;
-    }
-    const int rows_f = (cout + 127) / 128 * 128, kpad_f = (KK * cin + 63) / 64 * 64;
-    const bool frag = y3_filter_has_frag(cout, cin, ks);
-    for (int e = tid; e < 32 * 32 * KK; e += 256) {
-        const int ci_l = e & 31, co_l = (e >> 5) & 31, tap = e >> 10;
-        const int co = co0 + co_l, ci = ci0 + ci_l;
-        if (co < j.cout_src && ci < j.cin_src) {
-            const T v = tile[tap][co_l][ci_l];
-            const int k = tap * cin + ci;
-            dst[(long long)co * kpad_f + k] = v;
-            if (frag) dst[(long long)rows_f * kpad_f + y3_frag_index(co, k, cin)] = v;   // the copy conv_v10.h reads (y3_common.h)
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // backward of nearest x2 upsampling: dx[h,w] (+)= sum of the 2x2 block of dy
 template <typename T>
@@ -1888,67 +1687,6 @@ extern "C" int y3_stem_bn_bwd_wgrad(const void* x_nchw, int32_t src_dtype, int32
 #undef Y3_SB
     Y3_CHECK_LAUNCH();
     hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((32 * cin * 9 + 255) / 256), dim3(256), 0, st, (const float*)workspace, blocks, cin, 32, dw_oihw);
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int y3_pack_filter_dgrad(const float* w, int32_t cout_src, int32_t cin_src, int32_t ks, int32_t cout, int32_t cin, int32_t dtype, void* packed,
-                                    void* stream) {
-    if (!w || !packed) Y3_FAIL("y3_pack_filter_dgrad: null pointer");
-    if (cout < cout_src || cin < cin_src || (cout % 8) != 0 || (cin % 8) != 0) Y3_FAIL("y3_pack_filter_dgrad: bad padded sizes");
-    // the data-gradient convolution has `cin` filters of ks*ks*cout taps: same packed geometry with the roles swapped
-    const int rows = y3_filter_rows(cin), kpad = y3_filter_kpad(cout, ks);
-    const long long total = (long long)rows * kpad;
-    hipStream_t st = (hipStream_t)stream;
-    Y3_DISPATCH_T(dtype, hipLaunchKernelGGL((pack_filter_dgrad_kernel<T>), dim3(nblk(total)), dim3(256), 0, st, w, cout_src, cin_src, ks, cout, rows, kpad, (T*)packed,
-                                    y3_filter_has_frag(cin, cout, ks) ? 1 : 0));
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int y3_pack_filter_pair(const float* w, int32_t cout_src, int32_t cin_src, int32_t ks, int32_t cout, int32_t cin, int32_t dtype, void* packed_fwd, void* packed_dgrad,
-                                   void* stream) {
-    if (!w || !packed_fwd || !packed_dgrad) Y3_FAIL("y3_pack_filter_pair: null pointer");
-    if (cout < cout_src || cin < cin_src || (cout % 8) != 0 || (cin % 8) != 0) Y3_FAIL("y3_pack_filter_pair: bad padded sizes");
-    if (dtype != Y3_F16 && dtype != Y3_BF16) Y3_FAIL("y3_pack_filter_pair: f16/bf16 only");
-    const int rows_f = y3_filter_rows(cout), kpad_f = y3_filter_kpad(cin, ks), rows_d = y3_filter_rows(cin), kpad_d = y3_filter_kpad(cout, ks);
-    const long long tf = (long long)rows_f * kpad_f, td = (long long)rows_d * kpad_d;
-    const long long total = tf > td ? tf : td;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == Y3_F16) hipLaunchKernelGGL((pack_filter_pair_kernel<f16_t>), dim3(nblk(total)), dim3(256), 0, st, w, cout_src, cin_src, ks, cout, cin, rows_f, kpad_f, rows_d, kpad_d, (f16_t*)packed_fwd, (f16_t*)packed_dgrad);
-    else hipLaunchKernelGGL((pack_filter_pair_kernel<bf16_t>), dim3(nblk(total)), dim3(256), 0, st, w, cout_src, cin_src, ks, cout, cin, rows_f, kpad_f, rows_d, kpad_d, (bf16_t*)packed_fwd, (bf16_t*)packed_dgrad);
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-// blocks a job of y3_pack_filter_jobs occupies (the caller lays the jobs out back to back: first_block = running sum)
-extern "C" int64_t y3_pack_job_blocks(int32_t ksize, int32_t cout, int32_t cin, int32_t want_fwd, int32_t want_dgrad) {
-    (void)ksize; (void)want_fwd; (void)want_dgrad;
-    return (int64_t)((cout + 31) / 32) * ((cin + 31) / 32);   // one block per 32-filter x 32-channel tile of the weights
-}
-
-extern "C" int y3_pack_filter_jobs(const y3_pack_job* jobs_device, int32_t n_jobs, int64_t total_blocks, int32_t dtype, void* stream) {
-    if (!jobs_device || n_jobs <= 0 || total_blocks <= 0 || total_blocks > 0x7fffffffLL) Y3_FAIL("y3_pack_filter_jobs: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == Y3_F16) hipLaunchKernelGGL((pack_filter_jobs_kernel<f16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs);
-    else if (dtype == Y3_BF16) hipLaunchKernelGGL((pack_filter_jobs_kernel<bf16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs);
-    else Y3_FAIL("y3_pack_filter_jobs: f16/bf16 only");
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-// One launch for a whole model's inference banks: see fold_pack_jobs_kernel.  The table is DEVICE memory and cannot be inspected here: its geometry is the host mirror's
-// (yolov3_amd/engine.py::FoldPackJobs) to get right.
-extern "C" int y3_fold_pack_jobs(const y3_fold_pack_job* jobs_device, int32_t n_jobs, int64_t total_blocks, int32_t dtype, void* stream) {
-    if (!jobs_device) Y3_FAIL("y3_fold_pack_jobs: null job table");
-    if (n_jobs <= 0 || total_blocks <= 0 || total_blocks > 0x7fffffffLL) Y3_FAIL("y3_fold_pack_jobs: n_jobs %d and total_blocks %lld must be positive (and fit a grid)", (int)n_jobs, (long long)total_blocks);
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-        case Y3_F16: hipLaunchKernelGGL((fold_pack_jobs_kernel<f16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
-        case Y3_BF16: hipLaunchKernelGGL((fold_pack_jobs_kernel<bf16_t>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
-        case Y3_F32: hipLaunchKernelGGL((fold_pack_jobs_kernel<float>), dim3((unsigned)total_blocks), dim3(256), 0, st, jobs_device, n_jobs); break;
-        default: Y3_FAIL("y3_fold_pack_jobs: bad dtype %d (f16 / bf16 / f32)", (int)dtype);
-    }
     Y3_CHECK_LAUNCH();
     return 0;
 }

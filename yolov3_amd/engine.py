@@ -260,27 +260,23 @@ class FoldPackJobs:
         if not self.jobs:
             self.dirty = False
             return
-        import struct
-
         srcs = []
         for conv, bn, _cw, _shape, _stem in self.jobs:
             ts = (conv.weight, conv.bias) + ((bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4)
             srcs.append([self._f32(t) for t in ts])
         ptrs = [t.data_ptr() if t is not None else 0 for row in srcs for t in row]
         if self._table is None or self._table[1] != ptrs:
-            L = _lib.lib()
             rows, first = [], 0
             for (conv, bn, cw, (co, ci, k), stem), row in zip(self.jobs, srcs):
                 if tuple(row[0].shape) != (co, ci, k, k) or any(t is not None and t.numel() != co for t in row[1:]):
                     raise ValueError("a layer changed shape under its compiled plans: call model._drop_plans()")
                 grid_cin = 8 if stem else cw.cin
-                rows.append(struct.pack("<8Qf7i", *(t.data_ptr() if t is not None else 0 for t in row), cw.filt.data_ptr(), cw.bias.data_ptr(),
-                                        float(bn.eps) if bn is not None else 0.0, co, ci, k, cw.cout, grid_cin, int(stem), first))
-                first += int(L.y3_pack_job_blocks(k, cw.cout, grid_cin, 1, 0))
-            host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
-            self._table = (host.to(self.device), ptrs, first)
+                rows.append(_lib.Y3FoldPackJob(*(t.data_ptr() if t is not None else 0 for t in row), cw.filt.data_ptr(), cw.bias.data_ptr(),
+                                               float(bn.eps) if bn is not None else 0.0, co, ci, k, cw.cout, grid_cin, int(stem), first))
+                first += ops.pack_job_blocks(k, cw.cout, grid_cin)
+            self._table = (ops.job_table(rows, self.device), ptrs, first)
         self._keep = srcs
-        _lib.check(_lib.lib().y3_fold_pack_jobs(self._table[0].data_ptr(), len(self.jobs), self._table[2], ops.dtype_code(self.dtype), ops.stream_ptr()), "y3_fold_pack_jobs")
+        ops.fold_pack_jobs(self._table[0], len(self.jobs), self._table[2], self.dtype)
         self.dirty = False
 
 

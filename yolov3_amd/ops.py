@@ -696,6 +696,22 @@ def conv2d_stats(x: View, filt: torch.Tensor, bias: torch.Tensor, y: View, k: in
     return int(n.value)
 
 
+def pack_job_blocks(k: int, cout: int, cin: int, want_fwd: bool = True, want_dgrad: bool = False) -> int:
+    """blocks one job occupies in the grid of y3_pack_filter_jobs / y3_fold_pack_jobs: the jobs lie back to back, first_block = running sum"""
+    return int(_lib.lib().y3_pack_job_blocks(k, cout, cin, int(want_fwd), int(want_dgrad)))
+
+
+def job_table(records, device) -> torch.Tensor:
+    """a list of ctypes records (_lib.Y3PackJob / _lib.Y3FoldPackJob) -> the device array the jobs launches read"""
+    host = torch.frombuffer(bytearray(b"".join(bytes(r) for r in records)), dtype=torch.uint8)
+    return host.to(device)
+
+
+def fold_pack_jobs(table: torch.Tensor, n_jobs: int, blocks: int, dtype: torch.dtype):
+    """Conv + BatchNorm fold and pack of every job of a device table of _lib.Y3FoldPackJob records in one launch (engine.FoldPackJobs)"""
+    check(_lib.lib().y3_fold_pack_jobs(table.data_ptr(), int(n_jobs), int(blocks), dtype_code(dtype), stream_ptr()), "y3_fold_pack_jobs")
+
+
 class PackJobs:
     """Every layer's filter banks in one launch (y3_pack_filter_jobs): `add` registers a layer and returns its persistent (forward bank,
     data-gradient bank) tensors, `run` re-packs them from the current fp32 weights.  The job table lives on the device and is
@@ -738,22 +754,19 @@ class PackJobs:
         ptrs = [self.jobs[i][0].data_ptr() for i in todo]
         ent = self._tables.get(todo)
         if ent is None or ent[1] != ptrs:
-            import struct
-
-            L = _lib.lib()
             rows, first = [], 0
             for i, ptr in zip(todo, ptrs):
                 w, fwd, dg, cout, cin = self.jobs[i]
                 if w.dtype != torch.float32 or not w.is_contiguous():
                     raise TypeError("PackJobs expects contiguous fp32 master weights")
                 co, ci, k, _ = w.shape
-                rows.append(struct.pack("<QQQ6i", ptr, fwd.data_ptr() if fwd is not None else 0, dg.data_ptr() if dg is not None else 0, co, ci, k, cout, cin, first))
-                first += int(L.y3_pack_job_blocks(k, cout, cin, int(fwd is not None), int(dg is not None)))
-            host = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8)
+                rows.append(_lib.Y3PackJob(ptr, fwd.data_ptr() if fwd is not None else 0, dg.data_ptr() if dg is not None else 0, co, ci, k, cout, cin, first))
+                first += pack_job_blocks(k, cout, cin, fwd is not None, dg is not None)
+            table = job_table(rows, self.device)
             self._tables.pop(todo, None)
             while len(self._tables) >= self.MAX_TABLES:
                 self._tables.pop(next(iter(self._tables)))
-            ent = self._tables[todo] = (host.to(self.device), ptrs, first)
+            ent = self._tables[todo] = (table, ptrs, first)
         check(_lib.lib().y3_pack_filter_jobs(ent[0].data_ptr(), len(todo), ent[2], dtype_code(self.dtype), stream_ptr()), "y3_pack_filter_jobs")
         # a weight that is being trained may be written by a kernel torch's version counter does not see (FusedSGD): nothing is remembered about ANY of its jobs, so a plan
         # that freezes it later packs it afresh
