@@ -15,6 +15,7 @@ Public surface mirrors the reference's own Python signatures:
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
     save_checkpoint / smart_resume / strip_optimizer   (reference train.py:470-488, utils/torch_utils.py smart_resume, utils/general.py strip_optimizer)
+    save_reference_checkpoint / export_reference / to_reference   (the way out: files the unmodified reference's attempt_load, strip_optimizer and smart_resume read)
     DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py)
     Ensemble                             (reference models/experimental.py:74-86, `--weights a.pt b.pt`: every member decodes into its window of one prediction)
 Everything executes through libyolov3_hip.so (include/yolov3_hip.h); there is no CPU/PyTorch fallback.
@@ -28,6 +29,7 @@ from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401
+from .compat import export_reference, reference_pickle_module, save_reference_checkpoint, to_reference  # noqa: F401
 from .experimental import Ensemble  # noqa: F401
 from .loss import ComputeLoss  # noqa: F401
 from .optim import FusedAdam, FusedAdamW, FusedRMSProp, FusedSGD, GradScaler, ModelEMA, freeze_layers, smart_optimizer, smart_param_groups  # noqa: F401

@@ -15,6 +15,10 @@ the same) and swaps torch's parameter-free layers for the stand-ins the engine p
 ``save_checkpoint`` / ``smart_resume`` / ``strip_optimizer`` are the way OUT and back: the reference's checkpoint dict (train.py:470-488), its resume
 (utils/torch_utils.py smart_resume) and its final strip (utils/general.py strip_optimizer), over this package's model, ModelEMA and fused optimizers.
 
+``save_reference_checkpoint`` / ``export_reference`` write files that an UNMODIFIED reference process loads (its ``attempt_load``, ``strip_optimizer``,
+``smart_resume``): ``to_reference`` gives a copy of the model the attributes the reference's classes expect, and a scoped pickler
+(``torch.save(pickle_module=reference_pickle_module())``, the mirror of the scoped unpickler) writes this package's classes under the reference's names.
+
 ``install_aliases()`` remains for callers that use a plain ``torch.load`` in a process WITHOUT a reference checkout: it
 registers ``models`` / ``models.yolo`` / ``models.common`` / ``models.experimental`` alias modules, and only then: a real
 ``models`` package that is imported or importable is never shadowed or overwritten.
@@ -214,6 +218,166 @@ def attempt_load(weights, device=None, inplace=True, fuse=True):
     model.stride = model[int(torch.argmax(torch.tensor([float(m.stride.max()) for m in model])))].stride  # max stride
     assert all(model[0].nc == m.nc for m in model), f"Models have different class counts: {[m.nc for m in model]}"
     return model
+
+
+def _name_map() -> dict:
+    """the inverse of ``_class_map``: class (or function) of this package -> the reference's (module, name) for it.  ``Model`` is ``DetectionModel`` under a
+    second name on both sides: an object is written under its own ``__name__``."""
+    return {obj: key for key, obj in _class_map().items() if getattr(obj, "__name__", None) == key[1]}
+
+
+class _ReferencePickler(pickle._Pickler):
+    """``save_global`` with this package's classes written under the reference's qualified names (``models.yolo.DetectionModel``, ``models.common.Conv`` ...): the
+    mirror of ``_Unpickler.find_class``.  The names are WRITTEN, never resolved: nothing is imported, ``sys.modules`` is not read or touched and no class is
+    patched, so the stream is the same in a bare process, next to ``install_aliases()`` and inside a live reference process.  A global of this package that has no
+    reference name is refused by name: the file would not load in the reference."""
+
+    def save_global(self, obj, name=None):
+        hit = _name_map().get(obj) if isinstance(obj, (type, types.FunctionType)) else None
+        if hit is None:
+            module = getattr(obj, "__module__", None) or ""
+            if module == __package__ or module.startswith(__package__ + "."):
+                qual = name or getattr(obj, "__qualname__", None) or getattr(obj, "__name__", repr(obj))
+                raise pickle.PicklingError(f"{module}.{qual} has no counterpart in the reference (models.yolo / models.common): a file that holds it cannot be "
+                                           "loaded there.  Pass plain data (tensors, numbers, str, dict, list) next to the model instead")
+            return super().save_global(obj, name)
+        module, name = hit
+        if self.proto >= 4:
+            self.save(module)
+            self.save(name)
+            self.write(pickle.STACK_GLOBAL)
+        else:
+            self.write(pickle.GLOBAL + module.encode("ascii") + b"\n" + name.encode("ascii") + b"\n")
+        self.memoize(obj)
+
+    # classes come through dispatch[type] (save_type -> self.save_global); functions are dispatched to the function object itself: point that at the override
+    dispatch = dict(pickle._Pickler.dispatch)
+    dispatch[types.FunctionType] = save_global
+
+
+def reference_pickle_module() -> types.ModuleType:
+    """a stand-in for the ``pickle`` module whose Pickler writes the reference's class names (what ``torch.save(pickle_module=...)`` expects); the mirror of
+    ``_pickle_module``.  The pickler is the pure-Python one: tensors leave through torch's persistent ids, so the stream it walks is small."""
+    mod = types.ModuleType("yolov3_amd._reference_pickle")
+    mod.__dict__.update({k: v for k, v in pickle.__dict__.items() if not k.startswith("__")})
+    mod.Pickler = _ReferencePickler
+
+    def dump(obj, file, protocol=None, **kw):
+        _ReferencePickler(file, protocol, **kw).dump(obj)
+
+    def dumps(obj, protocol=None, **kw):
+        import io
+
+        f = io.BytesIO()
+        _ReferencePickler(f, protocol, **kw).dump(obj)
+        return f.getvalue()
+
+    mod.dump, mod.dumps = dump, dumps
+    return mod
+
+
+_ENGINE_ONLY = ("_plans", "weights_epoch", "infer_dtype")   # instance attributes the engine reads and the reference does not know
+
+
+def to_reference(model: nn.Module) -> nn.Module:
+    """The inverse of ``adopt``: a deep copy of `model` (wrappers removed) whose objects are still this package's classes and whose attributes are exactly what the
+    reference's classes of the same names expect, so that the copy, written with ``reference_pickle_module()``, runs in an unmodified reference process: torch's
+    own parameter-free layers in place of the engine's stand-ins, ``SPP.m`` (models/common.py:279), ``Detect.grid`` / ``anchor_grid`` (models/yolo.py:83-84), and
+    nothing that exists for the engine alone.  `model` itself -- modules, parameters, compiled plans, filter banks, ``weights_epoch`` -- is not touched."""
+    from copy import deepcopy
+
+    from .loss import de_parallel
+
+    model = de_parallel(model)
+    if isinstance(model, experimental.Ensemble):
+        raise TypeError("an Ensemble is not exported: the reference never pickles one, it builds it in attempt_load from a list of files -- export every member to "
+                        "a file of its own and pass the files as `--weights a.pt b.pt`")
+    if not isinstance(model, yolo.BaseModel):
+        raise TypeError(f"to_reference takes a yolov3_amd detection model, not {type(model).__module__}.{type(model).__name__}")
+    if any(isinstance(m, common.Conv) and m.fused for m in model.modules()):
+        raise ValueError("a fused model is not exported: the reference's Conv.forward needs `bn` and its loaders fuse for themselves -- export the unfused model "
+                         "(the training model, ema.ema, or attempt_load(..., fuse=False))")
+    ref = deepcopy(model)
+    mapped = set(_name_map())
+    for parent in ref.modules():
+        for name, m in parent._modules.items():
+            new = None
+            if type(m) is common.Upsample:
+                new = nn.Upsample(None, m.scale_factor, m.mode)
+            elif type(m) is common.MaxPool2d:
+                new = nn.MaxPool2d(m.kernel_size, m.stride, m.padding)
+            elif type(m) is common.ZeroPad2d:
+                new = nn.ZeroPad2d(list(m.padding))
+            if new is None:
+                continue
+            for a in ("i", "f", "np"):
+                if hasattr(m, a):
+                    setattr(new, a, getattr(m, a))
+            if hasattr(m, "type"):   # what the reference's parse_model derives from the class: str(nn.Upsample)[8:-2]
+                new.type = f"{type(new).__module__}.{type(new).__name__}"
+            parent._modules[name] = new
+    for m in ref.modules():
+        if isinstance(m, common.SPP):
+            if not hasattr(m, "m"):
+                m.m = nn.ModuleList(nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in m.k)
+            m.__dict__.pop("k", None)   # (adopt derives it back from `m`)
+        if isinstance(m, yolo.Detect):
+            for a in ("grid", "anchor_grid"):
+                if not isinstance(getattr(m, a, None), list):
+                    setattr(m, a, [torch.empty(0) for _ in range(m.nl)])
+        for a in _ENGINE_ONLY:
+            m.__dict__.pop(a, None)
+        for a, v in list(m.__dict__.items()):
+            t = type(v)
+            if a not in ("_modules", "_parameters", "_buffers") and t.__module__.split(".")[0] == __package__ and t not in mapped:
+                del m.__dict__[a]
+    return ref
+
+
+def _save_reference(obj, path):
+    """``torch.save`` with the reference's class names, through a temporary file next to `path`: a refused object leaves nothing behind and nothing half-written"""
+    import os
+
+    path = str(path)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    try:
+        torch.save(obj, tmp, pickle_module=reference_pickle_module())
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def save_reference_checkpoint(path, model, ema, optimizer, epoch, best_fitness=None, **extra):
+    """``save_checkpoint`` for a file that the UNMODIFIED reference loads: the same dict (train.py:470-488), ``model`` and ``ema`` passed through ``to_reference`` and
+    written under the reference's class names -- for its ``attempt_load`` (detect.py, val.py, export.py, hubconf.custom), ``train.py --weights`` and
+    ``smart_resume``.  This package reads the file like any reference checkpoint.  The ``optimizer`` entry is ``optimizer.state_dict()``: torch's format, in the
+    group and parameter order of the reference's ``smart_optimizer`` (``smart_param_groups`` is that order); an optimizer built over a model with frozen parameters
+    lists the trained ones only, which the reference's ``--resume`` (it lists all) refuses to load.  Returns the dict."""
+    ckpt = {
+        "epoch": epoch,
+        "best_fitness": best_fitness,
+        "model": to_reference(model).half(),
+        "ema": to_reference(ema.ema).half() if ema is not None else None,
+        "updates": ema.updates if ema is not None else None,
+        "optimizer": optimizer.state_dict() if optimizer is not None else None,
+        **extra,
+    }
+    _save_reference(ckpt, path)
+    return ckpt
+
+
+def export_reference(src, dst=None):
+    """Convert a file written by ``save_checkpoint`` or ``strip_optimizer`` (a full checkpoint or a stripped ``best.pt``) into one the unmodified reference loads;
+    everything but ``model`` / ``ema`` goes through as it is.  Written to `dst` (or over `src`); returns the dict."""
+    x = load_checkpoint(src)
+    if not isinstance(x, dict):
+        raise TypeError(f"{src}: expected a checkpoint dict (save_checkpoint / strip_optimizer), got {type(x).__name__}")
+    for k in ("model", "ema"):
+        if isinstance(x.get(k), nn.Module):
+            x[k] = to_reference(x[k])
+    _save_reference(x, dst or src)
+    return x
 
 
 def save_checkpoint(path, model, ema, optimizer, epoch, best_fitness=None, **extra):
