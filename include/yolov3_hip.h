@@ -285,6 +285,23 @@ int y3_labels_to_native(const float* targets, int32_t nl, int32_t bs, float widt
  * Rows outside the window are not touched.  Any `no` >= 6, any alignment. */
 int y3_label_rows(const float* targets, int32_t nl, const int32_t* label_offsets, int32_t bs, float width, float height, void* pred, int32_t dtype,
                   int32_t total_rows, int32_t no, int32_t row0, int32_t n_rows, void* stream);
+/* What a run writes (val.py --save-txt / --save-json, detect.py --save-txt, utils/plots.py:69-78 output_to_target), csrc/val_edge.hip: the per-box loops of val.py:98-103,
+ * val.py:134-144 and detect.py:223-236 as ONE compact table for the batch.  rows / img_stride / row_stride / counts / bs / max_rows: the padded NMS result as y3_scale_boxes takes
+ * it (row_stride >= 6; counts DEVICE, NULL = max_rows rows per image; views into a larger buffer work, elements past a row's sixth are not read).  Image i exports its first
+ * n_i = min(counts[i], max_rows, limit) rows (limit 0: no cap; `o[:max_det]` of output_to_target): out (DEVICE, capacity rows of 7 fp32) rows [offsets[i], offsets[i + 1]), in
+ * NMS order, or last to first with `reverse` (detect.py:231 `reversed(det)`); offsets (DEVICE, bs + 1 int32) is the exclusive prefix of n_i.  A row is
+ *   Y3_EXPORT_TARGET  [image0 + i, cls, cx, cy, w, h, conf]                     cx = (x1 + x2) / 2, w = x2 - x1, pixels
+ *   Y3_EXPORT_TXT     [image0 + i, cls, cx / w0, cy / h0, w / w0, h / h0, conf] sizes: DEVICE (bs, 2) fp32 native {w0, h0}, IEEE divisions
+ *   Y3_EXPORT_JSON    [image0 + i, cls, cx - w / 2, cy - h / 2, w, h, conf]     the corner the reference computes, which is not bitwise x1
+ * in fp32, operation for operation the reference's; `round_boxes` first rounds the four corners half to even (detect.py:223 `.round()`).  class_counts (DEVICE (bs, nc) int32, may be
+ * NULL): class_counts[i][cls] += 1 for each of image i's n_i rows with cls in [0, nc) -- the export only adds: the CALLER zeroes it.  With counts given, rows that would land
+ * at or past `capacity` are not stored (offsets[bs] and class_counts still hold the full count); with counts == NULL a capacity below bs * min(max_rows, limit) is an error.
+ * One launch; nothing is read back.  -1 with y3_last_error set, before any launch, for null rows / offsets / out, bs <= 0, row_stride < 6, an unknown form, the txt form without
+ * sizes, a histogram without classes and a capacity that is too small. */
+enum { Y3_EXPORT_TARGET = 0, Y3_EXPORT_TXT = 1, Y3_EXPORT_JSON = 2 };
+int y3_export_rows(const float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows, int32_t form, int32_t limit,
+                   int32_t round_boxes, int32_t reverse, int32_t image0, const float* sizes, float* out, int64_t capacity, int32_t* offsets, int32_t* class_counts,
+                   int32_t nc, void* stream);
 
 /* Autoanchor, device-resident (csrc/autoanchor.hip): reference utils/autoanchor.py -- check_anchors.metric, anchor_fitness, print_results, the genetic loop
  * of kmean_anchors and the scipy.cluster.vq.kmeans call ahead of it.  Nothing here allocates or synchronises.  wh / pts are DEVICE (N, 2) fp32; k, f, v, codes,

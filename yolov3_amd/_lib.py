@@ -17,6 +17,7 @@ ABI_VERSION = 6   # include/yolov3_hip.h::Y3_ABI_VERSION (2: round-3 export set 
                   # 5: layer 0 by recomputation (three exports), y3_shard_mean, knob wgrad_patch;
                   # 6: the deferred-epilogue form of conv_v10 and layer-0 recomputation removed)
 Y3_ALGO_AUTO, Y3_ALGO_MFMA, Y3_ALGO_DIRECT = 0, 1, 2
+Y3_EXPORT_TARGET, Y3_EXPORT_TXT, Y3_EXPORT_JSON = 0, 1, 2   # y3_export_rows `form`
 
 
 class Y3Tensor(C.Structure):
@@ -149,6 +150,8 @@ _SIGNATURES = {
     ),
     "y3_labels_to_native": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y3_label_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "y3_export_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "y3_anchor_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "y3_anchor_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "y3_anchor_evolve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

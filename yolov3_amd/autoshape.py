@@ -4,7 +4,8 @@ numpy / PIL images of any size go in; each is uploaded once as raw HWC uint8 and
 (csrc/val_edge.hip: cv2.resize INTER_LINEAR + 114-border + HWC->CHW in one pass, reference utils/augmentations.py:104-134),
 the uint8 batch feeds the model's first kernel directly (the /255 of models/common.py:868 happens inside the stem
 convolution), then batched NMS and batched scale_boxes (one launch each instead of the per-image loop of :871-872).
-Rendering helpers of the reference's ``Detections`` (show/save/crop/pandas) are outside the hot path and not provided.
+``Detections`` has the reference's data attributes and its text half (``str()`` / ``print()`` / ``pandas()``); the rendering helpers (show/save/crop/render) are
+outside the hot path and not provided.
 """
 from __future__ import annotations
 
@@ -71,6 +72,48 @@ class Detections:
 
     def tolist(self):
         return [Detections([self.ims[i]], [self.pred[i]], [self.files[i]], self.times, self.names, self.s) for i in range(self.n)]
+
+    def _name(self, c):
+        return self.names[c] if self.names is not None else str(c)
+
+    def __str__(self):
+        """reference models/common.py:906-913, 950-952 (`_run(pprint=True)`): per image its size and "2 persons, 1 tie", then the speed line.  The class counts of device
+        predictions come from the histogram of one export launch and one copy (outputs.class_histograms), not from a `unique()` and a sum per class and image."""
+        from .outputs import class_histograms
+
+        nc = len(self.names) if self.names is not None else 1000   # (DetectMultiBackend's default names cover 1000 classes)
+        s = ""
+        for i, (im, hist) in enumerate(zip(self.ims, class_histograms(self.pred, nc))):
+            s += f"\nimage {i + 1}/{len(self.pred)}: {im.shape[0]}x{im.shape[1]} "
+            if self.pred[i].shape[0]:
+                for c, n in hist.items():
+                    s += f"{n} {self._name(c)}{'s' * (n > 1)}, "
+                s = s.rstrip(", ")
+            else:
+                s += "(no detections)"
+        s = s.lstrip("\n")
+        return f"{s}\nSpeed: %.1fms pre-process, %.1fms inference, %.1fms NMS per image at shape {self.s}" % self.t
+
+    def __repr__(self):
+        return f"YOLOv3 {self.__class__} instance\n" + self.__str__()
+
+    def print(self):
+        import logging
+
+        logging.getLogger("yolov3_amd").info(self.__str__())
+
+    def pandas(self):
+        """reference models/common.py:990-998: a copy whose xyxy / xyxyn / xywh / xywhn are pandas DataFrames (pandas is imported here, not with the package)"""
+        import pandas as pd
+        from copy import copy
+
+        new = copy(self)
+        ca = "xmin", "ymin", "xmax", "ymax", "confidence", "class", "name"
+        cb = "xcenter", "ycenter", "width", "height", "confidence", "class", "name"
+        for k, c in zip(["xyxy", "xyxyn", "xywh", "xywhn"], [ca, ca, cb, cb]):
+            a = [[[*x[:5], int(x[5]), self._name(int(x[5]))] for x in t.tolist()] for t in getattr(self, k)]
+            setattr(new, k, [pd.DataFrame(x, columns=c) for x in a])
+        return new
 
 
 def _xyxy2xywh(x):

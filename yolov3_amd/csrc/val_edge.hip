@@ -219,7 +219,97 @@ template <typename T> __global__ __launch_bounds__(256) void label_rows_kernel(c
     pred[((long long)img * total_rows + row0 + r) * no + col] = from_f32<T>(v);
 }
 
+// ---- what a run writes: labels/*.txt, predictions.json, output_to_target ---------------------------------------------------------
+// The per-box loops of reference val.py:98-103 (save_one_txt), val.py:134-144 (save_one_json), detect.py:223-236 and utils/plots.py:69-78 (output_to_target) as one
+// compact table: image i's first n_i = min(counts[i], max_rows, limit) rows become rows [offsets[i], offsets[i + 1]) of `out`, seven floats each.  One block per
+// (image, 256 rows): it sums n_j over the images before its own (every block its own prefix: bs reads, no second launch and no order between blocks), reads its rows
+// element by element into LDS (consecutive lanes, consecutive addresses; the tail of a wider row is never read), computes one row per thread in the reference's
+// fp32 operation order and stores the 7-float rows from LDS the same way.
+constexpr int EXPORT_ROWS = 256;
+Y3_DEV int export_count(const int* counts, int img, int max_rows, int limit) {
+    int n = counts ? counts[img] : max_rows;
+    if (n > max_rows) n = max_rows;
+    if (limit > 0 && n > limit) n = limit;
+    return n < 0 ? 0 : n;
+}
+__global__ __launch_bounds__(EXPORT_ROWS) void export_rows_kernel(const float* __restrict__ rows, long long img_stride, int row_stride, const int* __restrict__ counts, int bs,
+                                                                    int max_rows, int chunks, int form, int limit, int round_boxes, int reverse, int image0,
+                                                                    const float* __restrict__ sizes, float* __restrict__ out, long long capacity, int* __restrict__ offsets,
+                                                                    int* __restrict__ class_counts, int nc) {
+    __shared__ float tile[EXPORT_ROWS * 6];
+    __shared__ float res[EXPORT_ROWS * 7];
+    __shared__ int part[EXPORT_ROWS];
+    const int img = blockIdx.x / chunks, chunk = blockIdx.x - img * chunks, t = threadIdx.x;
+    const int n = export_count(counts, img, max_rows, limit);
+    const int r0 = chunk * EXPORT_ROWS;
+    if (chunk > 0 && r0 >= n) return;   // (the whole block: n and chunk are the block's)
+    int s = 0;
+    for (int j = t; j < img; j += EXPORT_ROWS) s += export_count(counts, j, max_rows, limit);
+    part[t] = s;
+    __syncthreads();
+    for (int d = EXPORT_ROWS / 2; d > 0; d >>= 1) {
+        if (t < d) part[t] += part[t + d];
+        __syncthreads();
+    }
+    const int off = part[0];
+    if (chunk == 0 && t == 0) {
+        offsets[img] = off;
+        if (img == bs - 1) offsets[bs] = off + n;
+    }
+    const int m = n - r0 < EXPORT_ROWS ? n - r0 : EXPORT_ROWS;   // rows of this block
+    if (m <= 0) return;
+    const float* src = rows + img * img_stride + (long long)r0 * row_stride;
+    for (int e = t; e < m * row_stride; e += EXPORT_ROWS) {
+        const int r = e / row_stride, c = e - r * row_stride;
+        if (c < 6) tile[r * 6 + c] = src[e];
+    }
+    __syncthreads();
+    if (t < m) {
+        float x1 = tile[t * 6], y1 = tile[t * 6 + 1], x2 = tile[t * 6 + 2], y2 = tile[t * 6 + 3];
+        const float conf = tile[t * 6 + 4], cls = tile[t * 6 + 5];
+        if (round_boxes) { x1 = rintf(x1); y1 = rintf(y1); x2 = rintf(x2); y2 = rintf(y2); }   // torch's round: half to even (detect.py:223)
+        float bx = (x1 + x2) / 2.0f, by = (y1 + y2) / 2.0f;   // xyxy2xywh
+        float bw = x2 - x1, bh = y2 - y1;
+        if (form == Y3_EXPORT_TXT) {   // / gn (val.py:98-100): IEEE divisions
+            const float w0 = sizes[img * 2], h0 = sizes[img * 2 + 1];
+            bx = bx / w0; by = by / h0; bw = bw / w0; bh = bh / h0;
+        } else if (form == Y3_EXPORT_JSON) {   // box[:, :2] -= box[:, 2:] / 2 (val.py:135): not x1 again, the last bit differs
+            bx = bx - bw / 2.0f;
+            by = by - bh / 2.0f;
+        }
+        float* o = res + (reverse ? m - 1 - t : t) * 7;
+        o[0] = (float)(image0 + img);
+        o[1] = cls;
+        o[2] = bx; o[3] = by; o[4] = bw; o[5] = bh;
+        o[6] = conf;
+        if (class_counts && cls > -1.0f && cls < (float)nc) atomicAdd(class_counts + (long long)img * nc + (int)cls, 1);
+    }
+    __syncthreads();
+    const long long d0 = (long long)off + (reverse ? n - r0 - m : r0);   // first row of this block in the table
+    float* dst = out + d0 * 7;
+    for (int e = t; e < m * 7; e += EXPORT_ROWS)
+        if (d0 + e / 7 < capacity) dst[e] = res[e];   // (a table smaller than the counts say drops rows; offsets[bs] still tells)
+}
+
 }  // namespace
+
+extern "C" int y3_export_rows(const float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows, int32_t form, int32_t limit,
+                              int32_t round_boxes, int32_t reverse, int32_t image0, const float* sizes, float* out, int64_t capacity, int32_t* offsets, int32_t* class_counts,
+                              int32_t nc, void* stream) {
+    if (!rows || !offsets || (capacity > 0 && !out)) Y3_FAIL("y3_export_rows: null argument");
+    if (bs <= 0 || max_rows < 0 || row_stride < 6 || limit < 0) Y3_FAIL("y3_export_rows: bad geometry (bs %d, rows %d, row stride %d, limit %d)", bs, max_rows, row_stride, limit);
+    if (form != Y3_EXPORT_TARGET && form != Y3_EXPORT_TXT && form != Y3_EXPORT_JSON) Y3_FAIL("y3_export_rows: unknown form %d (0 target, 1 txt, 2 json)", form);
+    if (form == Y3_EXPORT_TXT && !sizes) Y3_FAIL("y3_export_rows: the txt form needs the native sizes (bs, 2) of the images");
+    if (class_counts && nc < 1) Y3_FAIL("y3_export_rows: a class histogram of %d classes", nc);
+    const int per = (limit > 0 && limit < max_rows) ? limit : max_rows;   // most rows one image can export
+    if (capacity < 0 || (!counts && capacity < (long long)bs * per)) Y3_FAIL("y3_export_rows: capacity %lld too small for %d x %d rows", (long long)capacity, bs, per);
+    const int chunks = per > 0 ? (per + EXPORT_ROWS - 1) / EXPORT_ROWS : 1;
+    if ((long long)bs * chunks > 0x7fffffffLL) Y3_FAIL("y3_export_rows: batch too large");
+    hipLaunchKernelGGL(export_rows_kernel, dim3((unsigned)(bs * chunks)), dim3(EXPORT_ROWS), 0, (hipStream_t)stream, rows, (long long)img_stride, row_stride, counts, bs, max_rows, chunks, form,
+                       limit, round_boxes ? 1 : 0, reverse ? 1 : 0, image0, sizes, out, (long long)capacity, offsets, class_counts, nc);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int y3_scale_boxes(float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows, const float* params, void* stream) {
     if (!rows || !params) Y3_FAIL("y3_scale_boxes: null argument");

@@ -571,6 +571,34 @@ def label_rows(pred: torch.Tensor, row0: int, n_rows: int, targets: torch.Tensor
                                    int(row0), int(n_rows), stream_ptr()), "y3_label_rows")
 
 
+EXPORT_FORMS = {"target": _lib.Y3_EXPORT_TARGET, "txt": _lib.Y3_EXPORT_TXT, "json": _lib.Y3_EXPORT_JSON}
+
+
+def export_rows(rows: torch.Tensor, img_stride: int, row_stride: int, counts: torch.Tensor | None, bs: int, max_rows: int, form: str, total: int, limit: int = 0,
+                round_boxes: bool = False, reverse: bool = False, image0: int = 0, sizes: torch.Tensor | None = None, nc: int = 0):
+    """The padded NMS result (as scale_boxes_raw takes it) -> (table (total, 7) fp32, offsets (bs + 1) int32, class_counts (bs, nc) int32 or None), all on the device, in one
+    launch (y3_export_rows).  `form`: "target" [image, cls, cx, cy, w, h, conf], "txt" (xywh / native size; `sizes` (bs, 2) fp32 {w0, h0} on the device) or "json" (top-left corner).
+    `total`: the rows the caller expects, i.e. sum(min(count, max_rows, limit)) from the counts NMS already brought to the host; rows beyond it are dropped.  `nc` > 0 also
+    returns the per-image histogram of the class column."""
+    require_gpu(rows, "export_rows")
+    if rows.dtype != torch.float32:
+        raise TypeError("export_rows expects fp32 rows [x1, y1, x2, y2, conf, cls]")
+    if form not in EXPORT_FORMS:
+        raise ValueError(f"export_rows: form {form!r} is not one of {sorted(EXPORT_FORMS)}")
+    dev = rows.device
+    if counts is not None and (counts.dtype != torch.int32 or counts.device != dev or counts.numel() != bs or not counts.is_contiguous()):
+        raise TypeError("export_rows expects bs int32 counts on the rows' device")
+    if sizes is not None and (sizes.dtype != torch.float32 or sizes.device != dev or sizes.numel() != 2 * bs or not sizes.is_contiguous()):
+        raise TypeError("export_rows expects (bs, 2) fp32 native sizes {w0, h0} on the rows' device")
+    table = torch.empty(int(total), 7, dtype=torch.float32, device=dev)
+    offsets = torch.empty(bs + 1, dtype=torch.int32, device=dev)
+    hist = torch.zeros(bs, nc, dtype=torch.int32, device=dev) if nc > 0 else None   # (the export adds into it)
+    check(_lib.lib().y3_export_rows(rows.data_ptr(), int(img_stride), int(row_stride), _ptr(counts), int(bs), int(max_rows), EXPORT_FORMS[form], int(limit), int(bool(round_boxes)),
+                                    int(bool(reverse)), int(image0), _ptr(sizes), table.data_ptr() if total else None, int(total), offsets.data_ptr(), _ptr(hist), int(nc), stream_ptr()),
+          "y3_export_rows")
+    return table, offsets, hist
+
+
 def scale_img(img: torch.Tensor, ratio: float = 1.0, same_shape: bool = False, gs: int = 32, flip_lr: bool = False) -> torch.Tensor:
     """upstream scale_img (the resize + pad of reference models/yolo.py:246), fused with the left-right mirror of the same line: (n, c, h, w) ->
     (n, c, ceil(h ratio / gs) gs, ceil(w ratio / gs) gs).  ratio 1.0 without a mirror returns `img` itself, like upstream."""

@@ -136,7 +136,7 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
 
 
 def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False, half=False, dtype=None, augment=False, save_hybrid=False,
-                compute_loss=None):
+                compute_loss=None, save_txt=False, save_conf=False, save_json=False, save_dir=None, class_map=None, jdict=None):
     """The validation loop of reference val.py:351-428 over ``(im, targets, shapes)`` triples in the reference dataloader's format: im (bs, 3, h, w)
     (uint8 is scaled by 1 / 255 like val.py:358-359), targets (nl, 6) [image, class, x, y, w, h] normalised and grouped by image, shapes[i] =
     ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))).  The post-processing of batch i (NMS, scale_boxes, labels to native space, process_batch, the
@@ -150,12 +150,35 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     `compute_loss` (val.py:364-368; train.py:445-456 passes it every epoch): a ``ComputeLoss``; ``compute_loss(train_out, targets)[1]`` of every batch is summed on the
     device and read back once, and the first element of the result becomes the reference's 7-tuple (mp, mr, map50, map, box, obj, cls): the sums divided by
     the number of batches (val.py:449).  An Ensemble has no train output (None in the reference): TypeError.
+    `save_txt` / `save_conf` (val.py:410-411): ``save_dir / "labels" / (stem + ".txt")`` per image with detections, `cls x y w h [conf]` normalised by the native size.
+    `save_json` (val.py:412-413, 454-462): the COCO-JSON entries of the run, appended to `jdict` (the caller's list, or a new one) and dumped to ``save_dir /
+    "predictions.json"`` (a str or Path: that file name inside `save_dir`) when there are any; `class_map[int(cls)]` is the category id (``list(range(1000))`` as val.py:344;
+    ``outputs.coco80_to_coco91_class()`` for COCO).  The file is written, not evaluated.  With either flag the batches are the dataloader's own 4-tuples ``(im, targets, paths,
+    shapes)`` and `save_dir` is required (ValueError before anything is launched); a 4-tuple is accepted without them too.  The boxes of a batch are converted by one launch
+    after scale_boxes (outputs.save_txt_batched / save_json_batched) and reach the host in one copy per flag; the metrics do not change.
     Returns ((mp, mr, map50, map[, box, obj, cls]), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
-    from . import ops
+    import itertools
+    import json
+    from pathlib import Path
+
+    from . import ops, outputs
     from .experimental import Ensemble
     from .general import _gain_pad, non_max_suppression_batched
     from .metrics import ConfusionMatrix, ValStats
 
+    saving = bool(save_txt or save_json)
+    if saving:   # (before any device work: a wrong call must not cost a forward)
+        if save_dir is None:
+            raise ValueError("save_txt / save_json need save_dir")
+        save_dir = Path(save_dir)
+        batches = iter(batches)
+        first = next(batches, None)
+        if first is not None and len(first) != 4:
+            raise ValueError("save_txt / save_json need the dataloader's 4-tuples (im, targets, paths, shapes): the file names come from the paths")
+        batches = itertools.chain(() if first is None else (first,), batches)
+        (save_dir / "labels" if save_txt else save_dir).mkdir(parents=True, exist_ok=True)   # val.py:279
+        class_map = list(range(1000)) if class_map is None else class_map
+        jdict = [] if jdict is None else jdict
     inner = _engine_model(model)
     if compute_loss is not None:
         if isinstance(inner, Ensemble):
@@ -175,7 +198,7 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     pending, seen = None, 0
 
     def finish(p):
-        pred, ev, targets, shapes, hw, tail = p
+        pred, ev, targets, shapes, hw, tail, paths = p
         bs = pred.shape[0]
         with torch.cuda.stream(side):
             side.wait_event(ev)
@@ -191,13 +214,20 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
             if single_cls:
                 rows[:, :, 5] = 0
             ops.scale_boxes_raw(rows, rows.stride(0), rows.stride(1), counts, bs, rows.shape[1], params)
+            if save_txt:   # val.py:410-413 on predn, the native-space rows (the class column already zeroed under single_cls)
+                outputs.save_txt_batched(rows, (counts, counts_list), [s[0] for s in shapes], paths, save_dir / "labels", save_conf)
+            if save_json:
+                outputs.save_json_batched(rows, (counts, counts_list), paths, jdict, class_map)
             correct = process_batch_batched(rows, counts, labels, offs, iouv)
             stats.update(rows, counts, counts_list, correct, labels, offs)
             if cm is not None:
                 cm.process_batch_batched(rows, counts, labels, offs)
         cur.wait_stream(side)
 
-    for im, targets, shapes in batches:
+    for batch in batches:
+        if saving and len(batch) != 4:
+            raise ValueError("save_txt / save_json need the dataloader's 4-tuples (im, targets, paths, shapes)")
+        im, targets, paths, shapes = batch if len(batch) == 4 else (batch[0], batch[1], None, batch[2])
         im = im.to(dev, non_blocking=True)
         if im.dtype == torch.uint8:
             im = im.to(dtype) / 255
@@ -231,10 +261,13 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
         ev.record(cur)
         if pending is not None:
             finish(pending)
-        pending = (pred, ev, targets, shapes, tuple(im.shape[2:]), tail)
+        pending = (pred, ev, targets, shapes, tuple(im.shape[2:]), tail, paths)
         seen += 1
     if pending is not None:
         finish(pending)
+    if save_json and len(jdict):   # val.py:454-462, without the pycocotools evaluation behind it
+        with open(save_dir / ("predictions.json" if save_json is True else Path(save_json).name), "w") as f:
+            json.dump(jdict, f)
     res = stats.results()
     if loss is not None:
         res = (*res, *(loss.cpu() / max(seen, 1)).tolist())
