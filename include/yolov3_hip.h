@@ -323,6 +323,24 @@ int y3_anchor_evolve(const float* wh, int64_t N, double* k, double* f, int32_t n
 int y3_kmeans_step(const float* pts, int64_t N, int32_t n, int32_t R, double* codes, int32_t* live, uint64_t frozen, double* dist, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* Class and image weights of --image-weights training, device-resident (csrc/label_weights.hip): reference utils/general.py:543-568 labels_to_class_weights /
+ * labels_to_image_weights and the random.choices call of train.py:363.  Nothing here allocates or synchronises.  cls is the DEVICE fp32 class column of every
+ * label; a class id is the value truncated toward zero (astype(int)).  Limits: 1 <= nc <= 4096, 0 <= labels < 2^31, 1 <= images < 2^31.
+ * label_histogram: counts is DEVICE int32 (nc + 1), overwritten: counts[c] = labels of class c at cls[i stride], counts[nc] = ids outside [0, nc) (NaN
+ *   included) -- the error word (y3_val_stats_count_labels skips such ids silently and adds to what nt holds).  Integer atomics only: independent of order.
+ * image_weights: offsets is DEVICE int64 (n_img + 1), image i owns the labels [offsets[i], offsets[i + 1]) (clamped to [0, n_labels]; empty allowed);
+ *   iw[i] = sum over its labels of class_weights[id] (DEVICE fp64 (nc) / (n_img)), ids outside [0, nc) skipped.  One wave per image: lane l adds the labels
+ *   first + l, first + l + 64, ... in ascending order, the 64 lane sums meet in an xor butterfly (32, 16, ..., 1) -- the order does not depend on the launch.
+ * weighted_choices: random.choices(range(n), weights, k=k) for k uniforms u in [0, 1) drawn by the caller.  cum = inclusive fp64 prefix sum of weights (in the
+ *   workspace; order: 8 consecutive weights per thread, Hillis-Steele over the 256 threads of a 2048-weight chunk, the same over the chunk totals -- fixed, so
+ *   bit-identical run to run), total = cum[n - 1] + 0.0, out[j] = bisect_right(cum, u[j] total, 0, n - 1) for j < k, and the status word
+ *   out[k] = 0, 1 (total <= 0: "Total of weights must be greater than zero") or 2 (total not finite).  out is DEVICE int64 (k + 1).
+ * weighted_choices_workspace_bytes: 8-byte aligned scratch of weighted_choices (n cumulative weights + one carry per chunk); 0 and a message for n out of range. */
+int y3_label_histogram(const float* cls, int32_t stride, int64_t n, int32_t* counts, int32_t nc, void* stream);
+int y3_image_weights(const float* cls, int64_t n_labels, const int64_t* offsets, int64_t n_img, const double* class_weights, int32_t nc, double* iw, void* stream);
+size_t y3_weighted_choices_workspace_bytes(int64_t n);
+int y3_weighted_choices(const double* weights, int64_t n, const double* u, int64_t k, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -13,6 +13,8 @@ Public surface mirrors the reference's own Python signatures:
     FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update; ema.ema is the averaged model)
     smart_optimizer / FusedAdam / FusedAdamW / FusedRMSProp   (reference utils/torch_utils.py:207-237, train.py --optimizer; torch-format state dicts)
     check_anchors / kmean_anchors / anchor_metrics / check_anchor_order   (reference utils/autoanchor.py, train.py:255: metric, k-means and genetic loop on the device)
+    labels_to_class_weights / labels_to_image_weights / image_weight_indices / LabelTable   (reference utils/general.py:543-568, train.py:333,360-363 --image-weights: the class
+                                         histogram, the image weights and the weighted draw of the epoch's indices on the device; the host keeps the random stream)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
@@ -28,6 +30,7 @@ from .val import detect_batches, process_batch, process_batch_batched, run_batch
 from .metrics import ConfusionMatrix, ValStats, ap_per_class, ap_per_class_device, compute_ap, fitness  # noqa: F401
 from .backend import DetectMultiBackend  # noqa: F401
 from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
+from .label_weights import LabelTable, image_weight_indices, labels_to_class_weights, labels_to_image_weights  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .outputs import coco80_to_coco91_class, output_to_target, save_json_batched, save_one_json, save_one_txt, save_txt_batched  # noqa: F401

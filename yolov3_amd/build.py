@@ -30,6 +30,7 @@ SOURCES = [
     ("batch_edge.hip", ["-ffp-contract=off"]),
     ("val_stats.hip", ["-ffp-contract=off"]),
     ("autoanchor.hip", ["-ffp-contract=off"]),
+    ("label_weights.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("filter_bank.hip", []),

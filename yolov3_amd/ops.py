@@ -896,3 +896,59 @@ def kmeans_step(pts: torch.Tensor, codes: torch.Tensor, live: torch.Tensor, froz
     N = int(pts.shape[0])
     ws = _anchor_workspace(pts.device, max(N, 1), n, R)
     check(_lib.lib().y3_kmeans_step(pts.data_ptr(), N, n, R, codes.data_ptr(), live.data_ptr(), int(frozen), dist.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_kmeans_step")
+
+
+_choices_ws: dict = {}
+
+
+def _label_classes(cls: torch.Tensor, what: str) -> torch.Tensor:
+    require_gpu(cls, what)
+    if cls.dtype != torch.float32 or cls.dim() != 1 or not cls.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous fp32 class column of the labels")
+    return cls
+
+
+def label_histogram(cls: torch.Tensor, nc: int) -> torch.Tensor:
+    """the class histogram of the fp32 class column `cls` (N,) on the device (y3_label_histogram) -> DEVICE int32 (nc + 1,): labels per class, then the number of
+    ids outside [0, nc)"""
+    cls = _label_classes(cls, "label_histogram")
+    N = int(cls.numel())
+    counts = torch.empty(int(nc) + 1, dtype=torch.int32, device=cls.device)
+    check(_lib.lib().y3_label_histogram(cls.data_ptr() if N else None, 1, N, counts.data_ptr(), int(nc), stream_ptr()), "y3_label_histogram")
+    return counts
+
+
+def image_weights(cls: torch.Tensor, offsets: torch.Tensor, class_weights: torch.Tensor) -> torch.Tensor:
+    """iw[i] = sum of class_weights[id] over the labels [offsets[i], offsets[i + 1]) of image i (y3_image_weights): cls (N,) fp32, offsets (n + 1,) int64,
+    class_weights (nc,) fp64, all on the device -> DEVICE fp64 (n,)"""
+    cls = _label_classes(cls, "image_weights")
+    require_gpu(offsets, "image_weights")
+    require_gpu(class_weights, "image_weights")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or class_weights.dtype != torch.float64 or class_weights.dim() != 1 \
+            or not class_weights.is_contiguous():
+        raise TypeError("image_weights expects contiguous int64 offsets (n + 1,) and fp64 class weights (nc,)")
+    N, n = int(cls.numel()), int(offsets.numel()) - 1
+    iw = torch.empty(max(n, 0), dtype=torch.float64, device=cls.device)
+    check(_lib.lib().y3_image_weights(cls.data_ptr() if N else None, N, offsets.data_ptr(), n, class_weights.data_ptr(), int(class_weights.numel()), iw.data_ptr(), stream_ptr()),
+          "y3_image_weights")
+    return iw
+
+
+def weighted_choices(weights: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """random.choices(range(n), weights, k=len(u)) for the uniforms `u` on the device (y3_weighted_choices): weights (n,) and u (k,) fp64 -> DEVICE int64 (k + 1,):
+    the k indices, then the status word (0, 1: total of weights not positive, 2: not finite)"""
+    require_gpu(weights, "weighted_choices")
+    require_gpu(u, "weighted_choices")
+    if weights.dtype != torch.float64 or u.dtype != torch.float64 or weights.dim() != 1 or u.dim() != 1 or not weights.is_contiguous() or not u.is_contiguous():
+        raise TypeError("weighted_choices expects contiguous fp64 weights (n,) and uniforms (k,)")
+    n, k = int(weights.numel()), int(u.numel())
+    need = int(_lib.lib().y3_weighted_choices_workspace_bytes(n))
+    if need == 0:
+        check(-1, "y3_weighted_choices_workspace_bytes")
+    dev = weights.device
+    ws = _choices_ws.get(dev.index)
+    if ws is None or ws.numel() < need:
+        ws = _choices_ws[dev.index] = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(k + 1, dtype=torch.int64, device=dev)
+    check(_lib.lib().y3_weighted_choices(weights.data_ptr(), n, u.data_ptr() if k else None, k, out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_weighted_choices")
+    return out
