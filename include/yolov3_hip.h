@@ -341,6 +341,31 @@ int y3_image_weights(const float* cls, int64_t n_labels, const int64_t* offsets,
 size_t y3_weighted_choices_workspace_bytes(int64_t n);
 int y3_weighted_choices(const double* weights, int64_t n, const double* u, int64_t k, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* COCO bbox evaluation of the run's COCO-JSON, device-resident (csrc/coco_eval.hip): pycocotools' COCOeval.computeIoU / evaluateImg / accumulate, which reference
+ * val.py:464-477 runs on the host.  fp64 in pycocotools' operation order, integer counts: precision / recall / scores are its arrays bit for bit.  Nothing here
+ * allocates or synchronises.  Limits: T <= 16, A <= 8, M <= 8, R <= 1024, detections and ground truths < 2^31, n_img * K < 2^31 - 1.
+ * coco_match: det_img / det_cat DEVICE int64 (n_det) ids, det_box DEVICE fp64 (n_det, 4) [x, y, w, h], det_score fp64 (n_det); img_ids (n_img) / cat_ids (K) DEVICE
+ *   int64, ascending and duplicate-free -- a detection whose image or category is in neither takes no part.  The ground truth is grouped by (image position,
+ *   category position) in file order: gt_box fp64 (n_gt, 4), gt_area fp64 (the annotation's area), gt_crowd uint8, gt_cat int32 (category position), and
+ *   gt_offsets DEVICE int32 (n_img * K + 1): pair p = image * K + category owns [gt_offsets[p], gt_offsets[p + 1]).  iou_thrs fp64 (T), area_rng fp64 (A, 2)
+ *   inclusive bounds, max_det = the largest maxDets (only the first max_det detections of a pair, by score, are matched).
+ *   Writes the rows in ACCUMULATE order (category position, score descending, image position, arrival): row_score fp64, row_rank int32 (rank inside the row's
+ *   (image, category) pair; rows that take no part lie behind every category and keep what the buffer held), row_match / row_ignore uint16 (n_det, A), bit t =
+ *   matched / ignored at threshold t; cat_begin / cat_end int32 (K): the rows of a category; npig int32 (K, A): ground truths not ignored (not crowd, area inside).
+ * coco_accumulate: over the rows with rank < max_dets[m] of category k: tp / fp running counts of (match & ~ignore) / (~match & ~ignore), rc = tp / npig,
+ *   pr = tp / (fp + tp + 2^-52) replaced by its reversed running maximum; recall[t, k, a, m] = last rc (0 without rows); for rec_thrs[r] the first j with
+ *   rc[j] >= r gives precision[t, r, k, a, m] = pr[j] and scores[...] = score[j], 0 past the end.  Cells with npig == 0 are -1.  precision / scores DEVICE fp64
+ *   (T, R, K, A, M), recall (T, K, A, M); max_dets DEVICE int32 (M), rec_thrs DEVICE fp64 (R).
+ * coco_eval_workspace_bytes: 256-byte aligned scratch of coco_match; 0 and a message for arguments out of range. */
+size_t y3_coco_eval_workspace_bytes(int64_t n_det, int64_t n_gt, int32_t T, int32_t A);
+int y3_coco_match(const int64_t* det_img, const int64_t* det_cat, const double* det_box, const double* det_score, int64_t n_det, const int64_t* img_ids, int32_t n_img,
+                  const int64_t* cat_ids, int32_t K, const double* gt_box, const double* gt_area, const uint8_t* gt_crowd, const int32_t* gt_cat, int64_t n_gt,
+                  const int32_t* gt_offsets, const double* iou_thrs, int32_t T, const double* area_rng, int32_t A, int32_t max_det, double* row_score, int32_t* row_rank,
+                  uint16_t* row_match, uint16_t* row_ignore, int32_t* cat_begin, int32_t* cat_end, int32_t* npig, void* workspace, size_t workspace_bytes, void* stream);
+int y3_coco_accumulate(const double* row_score, const int32_t* row_rank, const uint16_t* row_match, const uint16_t* row_ignore, int64_t n_det, const int32_t* cat_begin,
+                       const int32_t* cat_end, const int32_t* npig, int32_t K, int32_t T, const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M, int32_t A,
+                       double* precision, double* scores, double* recall, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -9,6 +9,8 @@ Public surface mirrors the reference's own Python signatures:
     ap_per_class_device / ValStats / ConfusionMatrix / run_batches   (the same statistics kept and computed on the device: val.py:386-428)
     save_one_txt / save_one_json / output_to_target / coco80_to_coco91_class   (reference val.py:60-144, utils/plots.py:69-78, utils/general.py; + save_txt_batched /
                                          save_json_batched: the boxes of a batch converted by one launch, one copy to the host; run_batches(save_txt=, save_json=))
+    CocoGroundTruth / CocoEval / CocoResult   (reference val.py:464-477: pycocotools' bbox AP / AR of the COCO-JSON, matched and accumulated on the device, bit for bit;
+                                         run_batches(save_json=True, anno_json=...) puts its map / map50 into the results)
     ComputeLoss                          (reference utils/loss.py)
     FusedSGD / GradScaler / ModelEMA     (reference train.py:345,411-422: scaler.scale / unscale_ / clip / step / update / ema.update; ema.ema is the averaged model)
     smart_optimizer / FusedAdam / FusedAdamW / FusedRMSProp   (reference utils/torch_utils.py:207-237, train.py --optimizer; torch-format state dicts)
@@ -33,6 +35,7 @@ from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean
 from .label_weights import LabelTable, image_weight_indices, labels_to_class_weights, labels_to_image_weights  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
+from .coco_eval import CocoEval, CocoGroundTruth, CocoResult  # noqa: F401
 from .outputs import coco80_to_coco91_class, output_to_target, save_json_batched, save_one_json, save_one_txt, save_txt_batched  # noqa: F401
 from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401
 from .compat import export_reference, reference_pickle_module, save_reference_checkpoint, to_reference  # noqa: F401

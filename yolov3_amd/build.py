@@ -31,6 +31,7 @@ SOURCES = [
     ("val_stats.hip", ["-ffp-contract=off"]),
     ("autoanchor.hip", ["-ffp-contract=off"]),
     ("label_weights.hip", ["-ffp-contract=off"]),
+    ("coco_eval.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("filter_bank.hip", []),

@@ -952,3 +952,61 @@ def weighted_choices(weights: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     out = torch.empty(k + 1, dtype=torch.int64, device=dev)
     check(_lib.lib().y3_weighted_choices(weights.data_ptr(), n, u.data_ptr() if k else None, k, out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "y3_weighted_choices")
     return out
+
+
+_coco_ws: dict = {}
+
+
+def _coco_check(what: str, **tensors):
+    """every tensor on the device, contiguous, of the dtype its name's suffix says (name__dtype)"""
+    for name, t in tensors.items():
+        label, dt = name.rsplit("__", 1)
+        require_gpu(t, what)
+        if t.dtype != getattr(torch, dt) or not t.is_contiguous():
+            raise TypeError(f"{what} expects contiguous {dt} {label}")
+
+
+def coco_match(det_img, det_cat, det_box, det_score, img_ids, cat_ids, gt_box, gt_area, gt_crowd, gt_cat, gt_offsets, iou_thrs, area_rng, max_det: int):
+    """COCOeval.computeIoU + evaluateImg for every (image, category) pair on the device (y3_coco_match; include/yolov3_hip.h has the layouts) -> dict of DEVICE tensors:
+    score fp64 (N,), rank int32 (N,), match / ignore uint16 (N, A) -- the rows in accumulate order -- cat_begin / cat_end int32 (K,), npig int32 (K, A)"""
+    what = "coco_match"
+    _coco_check(what, det_img__int64=det_img, det_cat__int64=det_cat, det_box__float64=det_box, det_score__float64=det_score, img_ids__int64=img_ids, cat_ids__int64=cat_ids,
+                gt_box__float64=gt_box, gt_area__float64=gt_area, gt_crowd__uint8=gt_crowd, gt_cat__int32=gt_cat, gt_offsets__int32=gt_offsets, iou_thrs__float64=iou_thrs,
+                area_rng__float64=area_rng)
+    N, G, n_img, K, T, A = int(det_score.numel()), int(gt_area.numel()), int(img_ids.numel()), int(cat_ids.numel()), int(iou_thrs.numel()), int(area_rng.numel()) // 2
+    if det_img.numel() != N or det_cat.numel() != N or det_box.numel() != 4 * N or gt_box.numel() != 4 * G or gt_crowd.numel() != G or gt_cat.numel() != G \
+            or gt_offsets.numel() != n_img * K + 1 or area_rng.numel() != 2 * A:
+        raise ValueError("coco_match: the detection / ground-truth columns and the offsets do not have the sizes of one table")
+    dev = det_score.device
+    need = int(_lib.lib().y3_coco_eval_workspace_bytes(N, G, T, A))
+    if need == 0:
+        check(-1, "y3_coco_eval_workspace_bytes")
+    ws = _coco_ws.get(dev.index)
+    if ws is None or ws.numel() < need:
+        ws = _coco_ws[dev.index] = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = dict(score=torch.empty(N, dtype=torch.float64, device=dev), rank=torch.empty(N, dtype=torch.int32, device=dev),
+               match=torch.empty(N, A, dtype=torch.uint16, device=dev), ignore=torch.empty(N, A, dtype=torch.uint16, device=dev),
+               cat_begin=torch.empty(K, dtype=torch.int32, device=dev), cat_end=torch.empty(K, dtype=torch.int32, device=dev), npig=torch.empty(K, A, dtype=torch.int32, device=dev))
+    p = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+    check(_lib.lib().y3_coco_match(p(det_img), p(det_cat), p(det_box), p(det_score), N, img_ids.data_ptr(), n_img, cat_ids.data_ptr(), K, p(gt_box), p(gt_area), p(gt_crowd), p(gt_cat),
+                                   G, gt_offsets.data_ptr(), iou_thrs.data_ptr(), T, area_rng.data_ptr(), A, int(max_det), p(out["score"]), p(out["rank"]), p(out["match"]),
+                                   p(out["ignore"]), out["cat_begin"].data_ptr(), out["cat_end"].data_ptr(), out["npig"].data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "y3_coco_match")
+    return out
+
+
+def coco_accumulate(rows: dict, T: int, rec_thrs: torch.Tensor, max_dets: torch.Tensor):
+    """COCOeval.accumulate over the rows `coco_match` returned (y3_coco_accumulate) -> DEVICE fp64 precision (T, R, K, A, M), recall (T, K, A, M), scores (T, R, K, A, M)"""
+    what = "coco_accumulate"
+    _coco_check(what, score__float64=rows["score"], rank__int32=rows["rank"], match__uint16=rows["match"], ignore__uint16=rows["ignore"], cat_begin__int32=rows["cat_begin"],
+                cat_end__int32=rows["cat_end"], npig__int32=rows["npig"], rec_thrs__float64=rec_thrs, max_dets__int32=max_dets)
+    N, (K, A), R, M = int(rows["score"].numel()), rows["npig"].shape, int(rec_thrs.numel()), int(max_dets.numel())
+    dev = rec_thrs.device
+    precision = torch.empty(T, R, K, A, M, dtype=torch.float64, device=dev)
+    scores = torch.empty(T, R, K, A, M, dtype=torch.float64, device=dev)
+    recall = torch.empty(T, K, A, M, dtype=torch.float64, device=dev)
+    p = lambda t: t.data_ptr() if t.numel() else None   # noqa: E731
+    check(_lib.lib().y3_coco_accumulate(p(rows["score"]), p(rows["rank"]), p(rows["match"]), p(rows["ignore"]), N, rows["cat_begin"].data_ptr(), rows["cat_end"].data_ptr(),
+                                        rows["npig"].data_ptr(), int(K), int(T), rec_thrs.data_ptr(), R, max_dets.data_ptr(), M, int(A), precision.data_ptr(), scores.data_ptr(),
+                                        recall.data_ptr(), stream_ptr()), "y3_coco_accumulate")
+    return precision, recall, scores

@@ -1,8 +1,8 @@
 """What a validation or detection run writes: ``labels/*.txt`` (reference val.py:98-103 save_one_txt, detect.py:231-236), the COCO-JSON entries (val.py:134-144
 save_one_json) and the plotting targets (utils/plots.py:69-78 output_to_target).  The reference builds a tensor, converts and opens a file per detection; here the boxes of
 a whole batch are converted by ONE launch (y3_export_rows, csrc/val_edge.hip) into a compact (N, 7) table -- bit for bit the reference's fp32 values -- that reaches the host in
-ONE copy; the rest is the reference's string formatting on NumPy rows (`txt_lines`, `json_entries`: pure functions, no device).  The JSON is written, not evaluated:
-pycocotools stays outside."""
+ONE copy; the rest is the reference's string formatting on NumPy rows (`txt_lines`, `json_entries`: pure functions, no device).  The JSON is evaluated by
+`coco_eval.CocoEval` (pycocotools' bbox AP / AR on the device), not here."""
 from __future__ import annotations
 
 from pathlib import Path

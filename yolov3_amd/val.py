@@ -136,7 +136,7 @@ def detect_batches(model, batches, conf_thres=0.25, iou_thres=0.45, classes=None
 
 
 def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, confusion=False, half=False, dtype=None, augment=False, save_hybrid=False,
-                compute_loss=None, save_txt=False, save_conf=False, save_json=False, save_dir=None, class_map=None, jdict=None):
+                compute_loss=None, save_txt=False, save_conf=False, save_json=False, save_dir=None, class_map=None, jdict=None, anno_json=None, coco_img_ids=None):
     """The validation loop of reference val.py:351-428 over ``(im, targets, shapes)`` triples in the reference dataloader's format: im (bs, 3, h, w)
     (uint8 is scaled by 1 / 255 like val.py:358-359), targets (nl, 6) [image, class, x, y, w, h] normalised and grouped by image, shapes[i] =
     ((h0, w0), ((h / h0, w / w0), (pad_w, pad_h))).  The post-processing of batch i (NMS, scale_boxes, labels to native space, process_batch, the
@@ -153,9 +153,14 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     `save_txt` / `save_conf` (val.py:410-411): ``save_dir / "labels" / (stem + ".txt")`` per image with detections, `cls x y w h [conf]` normalised by the native size.
     `save_json` (val.py:412-413, 454-462): the COCO-JSON entries of the run, appended to `jdict` (the caller's list, or a new one) and dumped to ``save_dir /
     "predictions.json"`` (a str or Path: that file name inside `save_dir`) when there are any; `class_map[int(cls)]` is the category id (``list(range(1000))`` as val.py:344;
-    ``outputs.coco80_to_coco91_class()`` for COCO).  The file is written, not evaluated.  With either flag the batches are the dataloader's own 4-tuples ``(im, targets, paths,
+    ``outputs.coco80_to_coco91_class()`` for COCO).  With either flag the batches are the dataloader's own 4-tuples ``(im, targets, paths,
     shapes)`` and `save_dir` is required (ValueError before anything is launched); a 4-tuple is accepted without them too.  The boxes of a batch are converted by one launch
     after scale_boxes (outputs.save_txt_batched / save_json_batched) and reach the host in one copy per flag; the metrics do not change.
+    `anno_json` (val.py:464-477; needs `save_json`, ValueError otherwise): the COCO annotation file (a path, its dict, or a `coco_eval.CocoGroundTruth` to parse and upload it
+    once for many runs).  After the dump the jdict is evaluated on the device (`coco_eval.CocoEval`: pycocotools' bbox AP / AR without pycocotools); `map` and `map50` of the
+    results tuple become its ``stats[0]`` and ``stats[1]``, the base value of `maps` the new `map` (val.py:486), and the `CocoResult` is kept as ``stats.coco`` (None when
+    there was nothing to evaluate).  `coco_img_ids`: the images to evaluate -- None: every image of the file; ``"seen"``: ``int(Path(p).stem)`` of the paths that went through
+    the run (val.py:473); or a list of ids.  With ``anno_json=None`` nothing changes.
     Returns ((mp, mr, map50, map[, box, obj, cls]), maps, stats[, confusion_matrix]) with `stats` the `ValStats` of the run."""
     import itertools
     import json
@@ -167,6 +172,11 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     from .metrics import ConfusionMatrix, ValStats
 
     saving = bool(save_txt or save_json)
+    if anno_json is not None:
+        if not save_json:
+            raise ValueError("anno_json needs save_json: the COCO evaluation reads the run's COCO-JSON entries")
+        if isinstance(anno_json, (str, Path)) and not Path(anno_json).is_file():
+            raise FileNotFoundError(f"anno_json: {anno_json} does not exist")
     if saving:   # (before any device work: a wrong call must not cost a forward)
         if save_dir is None:
             raise ValueError("save_txt / save_json need save_dir")
@@ -195,7 +205,7 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
     scope = _infer_dtype(model, half, dtype)
     dtype = _plan_dtype(model, scope)
     loss = torch.zeros(3, device=dev) if compute_loss is not None else None
-    pending, seen = None, 0
+    pending, seen, seen_paths = None, 0, []
 
     def finish(p):
         pred, ev, targets, shapes, hw, tail, paths = p
@@ -263,15 +273,34 @@ def run_batches(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300
             finish(pending)
         pending = (pred, ev, targets, shapes, tuple(im.shape[2:]), tail, paths)
         seen += 1
+        if anno_json is not None:
+            seen_paths.extend(paths)
     if pending is not None:
         finish(pending)
     if save_json and len(jdict):   # val.py:454-462, without the pycocotools evaluation behind it
         with open(save_dir / ("predictions.json" if save_json is True else Path(save_json).name), "w") as f:
             json.dump(jdict, f)
-    res = stats.results()
+    res, maps = stats.results(), stats.maps(nc)
+    if anno_json is not None:
+        stats.coco = None
+        if len(jdict):   # val.py:464-477 on the device: map, map50 = eval.stats[:2]
+            import numpy as np
+
+            from .coco_eval import CocoEval, CocoGroundTruth
+
+            gt = anno_json if isinstance(anno_json, CocoGroundTruth) else CocoGroundTruth(anno_json, dev)
+            img_ids = [int(Path(p).stem) for p in seen_paths] if isinstance(coco_img_ids, str) and coco_img_ids == "seen" else coco_img_ids
+            stats.coco = CocoEval(gt, img_ids).evaluate(jdict)
+            coco_map, coco_map50 = (float(v) for v in stats.coco.stats[:2])
+            res = (res[0], res[1], coco_map50, coco_map)
+            maps = np.zeros(nc) + coco_map   # val.py:486-488: the new mean, then the loop's own AP of every class with labels
+            if stats.n and stats._result[1]:
+                ap, classes = stats.compute()[5], stats.compute()[6]
+                for i, c in enumerate(classes):
+                    maps[c] = ap[i].mean()
     if loss is not None:
         res = (*res, *(loss.cpu() / max(seen, 1)).tolist())
-    return (res, stats.maps(nc), stats, cm) if confusion else (res, stats.maps(nc), stats)
+    return (res, maps, stats, cm) if confusion else (res, maps, stats)
 
 
 def _pred_rows(model, im, augment):
