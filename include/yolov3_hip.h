@@ -366,6 +366,32 @@ int y3_coco_accumulate(const double* row_score, const int32_t* row_rank, const u
                        const int32_t* cat_end, const int32_t* npig, int32_t K, int32_t T, const double* rec_thrs, int32_t R, const int32_t* max_dets, int32_t M, int32_t A,
                        double* precision, double* scores, double* recall, void* stream);
 
+/* A cached dataset kept in device memory and batched without a host loader (csrc/dataset.hip): the augment=False path of reference utils/dataloaders.py:659-735
+ * (LoadImagesAndLabels.__getitem__ over images cached already resized: the pad-only branch of letterbox, HWC -> CHW, BGR -> RGB, the two label conversions) and
+ * collate_fn (:825-830).  Nothing here allocates or synchronises.
+ * arena: DEVICE uint8, 16-byte aligned, arena_bytes a multiple of 4: every image (h, w, 3) BGR at images[i].offset.  images: DEVICE table of n_images records, 8-byte
+ *   aligned; top / left are letterbox's round(dh - 0.1) / round(dw - 0.1) for the image's batch shape (bh, bw), computed by the host.  A batch is `count` images:
+ *   indices[0 .. count) (DEVICE int64) or, with indices NULL, first .. first + count - 1.  An index outside [0, n_images), or a record that does not lie inside the
+ *   arena or the batch width, yields an all-border image: no read leaves the arena.  Limits: W % 16 == 0, W <= 4096, H <= 65535, count * H < 2^25.
+ * dataset_batch: dst is DEVICE (count, 3, H, W) of dst_dtype (Y3_U8 / Y3_F16 / Y3_BF16 / Y3_F32), contiguous, 16-byte aligned, written in one launch with 16-byte
+ *   stores: element (b, c, y, x) = src_b[y - top_b][x - left_b][2 - c] inside the image, 114 outside; a floating output holds value / 255 (the fp32 IEEE quotient,
+ *   rounded once to dst_dtype): what `im.to(dtype) / 255` gives.
+ * dataset_targets: labels DEVICE fp32 (total, 5) [cls, x, y, w, h] normalised, label_offsets DEVICE int64 (n_images + 1).  Writes targets, DEVICE fp32 (n_rows, 6)
+ *   [image in batch, cls, x, y, w, h] in image order, and offsets, DEVICE int64 (count + 1).  n_rows is the batch's label count, known to the caller from the
+ *   offsets (rows past the device's own count are zeroed, rows past n_rows never written).  Per row, in fp32 and in the operation order of upstream xywhn2xyxy
+ *   and xyxy2xywhn: x1 = w (xc - bw / 2) + padw, ... with padw = (W - w) / 2; clipped to [0, W - 1e-3] / [0, H - 1e-3] (the bounds formed in double and rounded to
+ *   fp32 once); x = ((x1 + x2) / 2) / W, bw = (x2 - x1) / W.  count <= 1024. */
+typedef struct {
+    int64_t offset;         /* first byte of the image in the arena, a multiple of 16 */
+    int32_t h, w;           /* the cached image */
+    int32_t top, left;      /* rows / columns of border before it */
+    int32_t bh, bw;         /* the batch shape top / left were computed for */
+} y3_dataset_image;         /* 32 bytes */
+int y3_dataset_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const int64_t* indices, int64_t first, int32_t count,
+                     void* dst, int32_t dst_dtype, int32_t H, int32_t W, void* stream);
+int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const int64_t* indices, int64_t first,
+                       int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -17,6 +17,8 @@ Public surface mirrors the reference's own Python signatures:
     check_anchors / kmean_anchors / anchor_metrics / check_anchor_order   (reference utils/autoanchor.py, train.py:255: metric, k-means and genetic loop on the device)
     labels_to_class_weights / labels_to_image_weights / image_weight_indices / LabelTable   (reference utils/general.py:543-568, train.py:333,360-363 --image-weights: the class
                                          histogram, the image weights and the weighted draw of the epoch's indices on the device; the host keeps the random stream)
+    DeviceDataset / rect_batch_shapes    (reference utils/dataloaders.py:548-570, 659-735, 825-830; train.py:299-312, val.py:351-360: a cached augment=False dataset kept in device
+                                         memory -- rect batch shapes on the host once, every letterboxed CHW RGB batch and its targets in one launch each, no host loader)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
@@ -33,6 +35,7 @@ from .metrics import ConfusionMatrix, ValStats, ap_per_class, ap_per_class_devic
 from .backend import DetectMultiBackend  # noqa: F401
 from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
 from .label_weights import LabelTable, image_weight_indices, labels_to_class_weights, labels_to_image_weights  # noqa: F401
+from .dataset import DeviceDataset, rect_batch_shapes  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .coco_eval import CocoEval, CocoGroundTruth, CocoResult  # noqa: F401

@@ -32,6 +32,7 @@ SOURCES = [
     ("autoanchor.hip", ["-ffp-contract=off"]),
     ("label_weights.hip", ["-ffp-contract=off"]),
     ("coco_eval.hip", ["-ffp-contract=off"]),
+    ("dataset.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("filter_bank.hip", []),

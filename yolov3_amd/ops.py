@@ -954,6 +954,61 @@ def weighted_choices(weights: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _dataset_args(what: str, images: torch.Tensor, n: int, indices: torch.Tensor | None, first: int, count: int):
+    require_gpu(images, what)
+    if images.dtype != torch.uint8 or images.dim() != 1 or not images.is_contiguous() or images.numel() != 32 * n:
+        raise TypeError(f"{what} expects the contiguous record table of the set: uint8 ({32 * n},)")
+    if indices is not None:
+        require_gpu(indices, what)
+        if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous() or indices.numel() != count:
+            raise TypeError(f"{what} expects {count} contiguous int64 indices")
+    elif first < 0 or first + count > n:
+        raise ValueError(f"{what}: images {first} .. {first + count - 1} lie outside the {n} of the set")
+
+
+def dataset_batch(arena: torch.Tensor, images: torch.Tensor, n: int, indices: torch.Tensor | None, first: int, count: int, height: int, width: int,
+                  dtype: torch.dtype = torch.uint8, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One batch of a device-resident dataset in one launch (y3_dataset_batch): `arena` the uint8 image arena, `images` its record table as bytes (32 n,), the batch
+    the images indices[0 .. count) (DEVICE int64) or first .. first + count - 1 -> (count, 3, height, width) in `dtype` (uint8, or float16 / bfloat16 / float32
+    divided by 255): letterboxed with 114, CHW, RGB.  `out`: a contiguous, 16-byte aligned tensor of that shape and dtype to write into."""
+    what = "dataset_batch"
+    require_gpu(arena, what)
+    _dataset_args(what, images, n, indices, first, count)
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise TypeError("dataset_batch expects the contiguous uint8 arena of the set")
+    if dtype not in DTYPE_CODE:
+        raise TypeError(f"dataset_batch writes uint8 / float16 / bfloat16 / float32, not {dtype}")
+    shape = (int(count), 3, int(height), int(width))
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=arena.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
+        raise TypeError(f"dataset_batch: `out` must be a contiguous {shape} {dtype} tensor on {arena.device}")
+    if count:
+        check(_lib.lib().y3_dataset_batch(arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), _ptr(indices), int(first), int(count), out.data_ptr(), DTYPE_CODE[dtype],
+                                          int(height), int(width), stream_ptr()), "y3_dataset_batch")
+    return out
+
+
+def dataset_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, indices: torch.Tensor | None, first: int, count: int, height: int,
+                    width: int, n_rows: int):
+    """The targets of one batch of a device-resident dataset (y3_dataset_targets): `labels` fp32 (total, 5) and `label_offsets` int64 (n + 1,) on the device, `n_rows`
+    the batch's label count (the caller's host copy of the offsets knows it) -> (DEVICE fp32 (n_rows, 6) [image in batch, cls, x, y, w, h], DEVICE int64 (count + 1,)
+    offsets): collate_fn's targets of the letterboxed images."""
+    what = "dataset_targets"
+    require_gpu(labels, what)
+    require_gpu(label_offsets, what)
+    _dataset_args(what, images, n, indices, first, count)
+    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
+        raise TypeError("dataset_targets expects the contiguous fp32 (total, 5) label table")
+    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
+        raise TypeError(f"dataset_targets expects {n + 1} contiguous int64 label offsets")
+    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
+    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
+    check(_lib.lib().y3_dataset_targets(labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), _ptr(indices), int(first), int(count),
+                                        int(height), int(width), targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr()), "y3_dataset_targets")
+    return targets, offsets
+
+
 _coco_ws: dict = {}
 
 
