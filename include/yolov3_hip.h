@@ -392,6 +392,45 @@ int y3_dataset_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset
 int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const int64_t* indices, int64_t first,
                        int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
 
+/* The train-mode loader over the same arena and record table (csrc/augment.hip): the augment=True, rect=False path of reference utils/dataloaders.py:659-735, 764-822
+ * and utils/augmentations.py:57-73, 137-216, 270-283 -- mosaic, random_perspective (affine only), mixup, augment_hsv, the flips, collate_fn.  The host draws the random
+ * numbers and sends one y3_augment_item per item of the batch (DEVICE, 8-byte aligned); nothing here allocates or synchronises.
+ * A mosaic is a square canvas of `canvas` pixels (2 S, or S for the letterbox branch) filled with 114 on which tile t shows image `img`: canvas pixel (X, Y) of the
+ *   rectangle [x1, x2) x [y1, y2) is image pixel (X - padw, Y - padh).  inv is the inverse of the affine matrix m (both row-major 2 x 3, float64).  An item blends
+ *   two mosaics when nmos == 2: trunc(a * ratio + b * ratio1) in float64.  lut: the hue, saturation and value tables of augment_hsv, applied when hsv != 0.
+ * augment_batch: dst is DEVICE (count, 3, S, S) of dst_dtype, contiguous, 16-byte aligned, written in one launch: per output pixel the flips undone, the source
+ *   coordinate in 1 / 32 pixel ((rint((inv01 y + inv02) 1024) + 16 + rint(inv00 x 1024)) >> 5, likewise Y), four bilinear taps with integer weights (+ 512 >> 10),
+ *   a tap outside the canvas or in no tile being 114; the blend; BGR -> HSV (integer, H in [0, 180)), the tables, HSV -> BGR (fp32); RGB planes; a floating output
+ *   holds value / 255.  No read leaves the arena whatever the items and the records hold.  Limits: S % 16 == 0, 16 <= S <= 4096, count <= 1024.
+ * augment_targets: every label row of the item's tiles, in tile order (the second mosaic's after the first's), through xywhn2xyxy(w, h, lpadw, lpadh) in fp32, the
+ *   clip to [0, canvas] when clip != 0, the four corners through m in fp64, min / max, the clip to [0, S], box_candidates against the unwarped box times `scale`
+ *   (wh_thr 2, ar_thr 100, area_thr 0.1, eps 1e-16), xyxy2xywhn(clip=True, eps=1e-3) and the flips.  Survivors are compacted in that order into targets, DEVICE
+ *   fp32 (n_rows, 6) [item in batch, cls, x, y, w, h]; offsets, DEVICE int64 (count + 1), holds where every item's rows begin and, last, the survivor count.
+ *   n_rows is the caller's upper bound (the label count of all tiles); rows past the survivor count are not written. */
+typedef struct {
+    int32_t img;            /* index into the record table */
+    int32_t x1, y1, x2, y2; /* the rectangle on the canvas */
+    int32_t padw, padh;     /* canvas position of image pixel (0, 0) */
+    float lpadw, lpadh;     /* the same for the labels (letterbox's halves may end in .5) */
+    int32_t reserved;
+} y3_augment_tile;          /* 40 bytes */
+typedef struct {
+    double inv[6], m[6];
+    double scale;           /* random_perspective's s */
+    int32_t ntiles, canvas, clip, reserved;
+    y3_augment_tile tiles[4];
+} y3_augment_mosaic;        /* 280 bytes */
+typedef struct {
+    y3_augment_mosaic mosaics[2];
+    double ratio, ratio1;   /* mixup's r and 1 - r */
+    int32_t nmos, flipud, fliplr, hsv;
+    uint8_t lut[3][256];
+} y3_augment_item;          /* 1360 bytes */
+int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, void* dst,
+                     int32_t dst_dtype, int32_t S, void* stream);
+int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                       int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

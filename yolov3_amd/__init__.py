@@ -19,6 +19,9 @@ Public surface mirrors the reference's own Python signatures:
                                          histogram, the image weights and the weighted draw of the epoch's indices on the device; the host keeps the random stream)
     DeviceDataset / rect_batch_shapes    (reference utils/dataloaders.py:548-570, 659-735, 825-830; train.py:299-312, val.py:351-360: a cached augment=False dataset kept in device
                                          memory -- rect batch shapes on the host once, every letterboxed CHW RGB batch and its targets in one launch each, no host loader)
+    DeviceTrainDataset / draw_item       (reference utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283: the augment=True loader -- mosaic, affine
+                                         warp, HSV, flips and mixup sampled straight from the cached images in one launch per batch, the labels in another; the host keeps
+                                         the reference's random stream)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
@@ -36,6 +39,7 @@ from .backend import DetectMultiBackend  # noqa: F401
 from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
 from .label_weights import LabelTable, image_weight_indices, labels_to_class_weights, labels_to_image_weights  # noqa: F401
 from .dataset import DeviceDataset, rect_batch_shapes  # noqa: F401
+from .augment import DeviceTrainDataset, draw_item  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .coco_eval import CocoEval, CocoGroundTruth, CocoResult  # noqa: F401

@@ -1,0 +1,250 @@
+"""The train-mode loader on the device: mosaic, random affine, HSV, flips and mixup of a cached dataset (reference utils/dataloaders.py:659-735, 764-822;
+utils/augmentations.py:57-73, 137-216, 270-283).
+
+    ds = DeviceTrainDataset(images, labels, hyp, img_size=640, batch_size=64)       # or DeviceTrainDataset.from_dataset(train_loader.dataset, batch_size=64)
+    ds.set_indices(perm)                                                            # the epoch's order; also the pool load_mosaic's random.choices draws from
+    for im, targets, paths, shapes in ds: ...                                       # im (bs, 3, s, s) RGB CHW and targets (nl, 6) are DEVICE tensors
+
+The host keeps the random stream and nothing per pixel: draw_item makes the reference's calls to `random` and `np.random` in the reference's order (a seeded process
+stands, after every item, where the reference's __getitem__ would leave both generators) and forms, in float64 and in the reference's operation order, the matrix
+M = T @ S @ R @ P @ C, the paste rectangles of load_mosaic, the three HSV look-up tables, the flip flags and the mixup ratio.  They go into one fixed-size record per
+item (y3_augment_item); a batch is one pinned host -> device copy of bs records.  csrc/augment.hip does the rest in two launches per batch: y3_augment_batch samples
+every output pixel straight from the image arena (the 2s x 2s canvas is never materialised) and y3_augment_targets transforms, filters and compacts the labels.  The
+survivor count is known only on the device: the host reads the bs + 1 offsets once per batch.
+
+What rests on what: the draws, the geometry, M, the tables, the whole label path, the blend, the flips and the layout are pinned by the unmodified reference
+(tests/golden/make_augment_golden.py).  The pixel sampler of cv2.warpAffine and the two cv2.cvtColor conversions follow the integer / fp32 statements of
+tests/augment_cases.py, which restate the published 8-bit algorithms and have not been compared with a cv2 build.
+
+Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0, polygon labels (a non-empty segments[i]), rect=True, an image whose
+long side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; KeyError for a missing hyp key.  Albumentations is a
+no-op, as in the reference when the package is absent.  Out of scope: warpPerspective, copy-paste, polygon labels, load_mosaic9, cutout, prefetching.
+"""
+from __future__ import annotations
+
+import math
+import random
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import ops
+from .dataset import DeviceDataset
+
+HYP_KEYS = ("mosaic", "mixup", "degrees", "translate", "scale", "shear", "perspective", "hsv_h", "hsv_s", "hsv_v", "flipud", "fliplr", "copy_paste")
+
+# y3_augment_tile / y3_augment_mosaic / y3_augment_item of include/yolov3_hip.h
+TILE = np.dtype([("img", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("padw", "<i4"), ("padh", "<i4"), ("lpadw", "<f4"), ("lpadh", "<f4"), ("reserved", "<i4")])
+MOSAIC = np.dtype([("inv", "<f8", (6,)), ("m", "<f8", (6,)), ("scale", "<f8"), ("ntiles", "<i4"), ("canvas", "<i4"), ("clip", "<i4"), ("reserved", "<i4"), ("tiles", TILE, (4,))])
+ITEM = np.dtype([("mosaics", MOSAIC, (2,)), ("ratio", "<f8"), ("ratio1", "<f8"), ("nmos", "<i4"), ("flipud", "<i4"), ("fliplr", "<i4"), ("hsv", "<i4"), ("lut", "u1", (3, 256))])
+assert (TILE.itemsize, MOSAIC.itemsize, ITEM.itemsize) == (40, 280, 1360)
+
+
+@dataclass
+class Mosaic:
+    """One canvas and its warp: `indices` the images of the tiles in paste order, `rects` per tile (x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b), `M` the 3 x 3 float64
+    matrix of random_perspective, `scale` its s, `canvas` the side of the canvas (2 s, or s for the letterbox branch), `pad` per tile the (padw, padh) of its labels."""
+
+    indices: list
+    rects: list
+    M: np.ndarray
+    scale: float
+    canvas: int
+    pad: list
+    center: tuple | None = None   # (yc, xc)
+
+
+@dataclass
+class Item:
+    index: int
+    mosaics: list
+    ratio: float | None       # the mixup ratio r, or None
+    luts: np.ndarray | None   # (3, 256) uint8: hue, sat, val; None when every gain is 0
+    flipud: bool
+    fliplr: bool
+    mosaic: bool              # False: the letterbox branch (one tile on an s x s canvas)
+
+
+def rotation_matrix_2d(angle, scale):
+    """cv2.getRotationMatrix2D(center=(0, 0)) from its documented formula -> the two rows"""
+    a = angle * math.pi / 180
+    alpha, beta = math.cos(a) * scale, math.sin(a) * scale
+    return [[alpha, beta, (1 - alpha) * 0 - beta * 0], [-beta, alpha, beta * 0 + (1 - alpha) * 0]]
+
+
+def draw_perspective(hyp, side, border):
+    """random_perspective's eight draws and its matrix for a (side, side) image: -> (M (3, 3) float64, s)"""
+    height = width = side + border * 2
+    C, P, R, S, T = (np.eye(3) for _ in range(5))
+    C[0, 2] = -side / 2
+    C[1, 2] = -side / 2
+    perspective = hyp["perspective"]
+    P[2, 0] = random.uniform(-perspective, perspective)
+    P[2, 1] = random.uniform(-perspective, perspective)
+    a = random.uniform(-hyp["degrees"], hyp["degrees"])
+    s = random.uniform(1 - hyp["scale"], 1 + hyp["scale"])
+    R[:2] = rotation_matrix_2d(a, s)
+    S[0, 1] = math.tan(random.uniform(-hyp["shear"], hyp["shear"]) * math.pi / 180)
+    S[1, 0] = math.tan(random.uniform(-hyp["shear"], hyp["shear"]) * math.pi / 180)
+    T[0, 2] = random.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]) * width
+    T[1, 2] = random.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]) * height
+    return T @ S @ R @ P @ C, s   # (NumPy's matrix product, as the reference forms it)
+
+
+def draw_mosaic(index, hw, hyp, s, pool) -> Mosaic:
+    """load_mosaic's draws and geometry (dataloaders.py:764-822)"""
+    border = -s // 2
+    yc, xc = (int(random.uniform(-x, 2 * s + x)) for x in (border, border))
+    indices = [index, *random.choices(pool, k=3)]
+    random.shuffle(indices)
+    rects, pad = [], []
+    for i, j in enumerate(indices):
+        h, w = hw[j]
+        if i == 0:
+            x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+            x1b, y1b, x2b, y2b = w - (x2a - x1a), h - (y2a - y1a), w, h
+        elif i == 1:
+            x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, s * 2), yc
+            x1b, y1b, x2b, y2b = 0, h - (y2a - y1a), min(w, x2a - x1a), h
+        elif i == 2:
+            x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(s * 2, yc + h)
+            x1b, y1b, x2b, y2b = w - (x2a - x1a), 0, w, min(y2a - y1a, h)
+        else:
+            x1a, y1a, x2a, y2a = xc, yc, min(xc + w, s * 2), min(s * 2, yc + h)
+            x1b, y1b, x2b, y2b = 0, 0, min(w, x2a - x1a), min(y2a - y1a, h)
+        rects.append((x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b))
+        pad.append((x1a - x1b, y1a - y1b))
+    M, scale = draw_perspective(hyp, 2 * s, border)
+    return Mosaic([int(j) for j in indices], rects, M, scale, 2 * s, pad, (yc, xc))
+
+
+def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
+    """The draws of one __getitem__ (dataloaders.py:659-735) for image `index` (already looked up in the epoch's order), from the global `random` and `np.random`, in
+    the reference's order: random.random() for mosaic; load_mosaic (two uniforms, yc then xc, choices(pool, k=3), shuffle) and random_perspective's eight uniforms;
+    random.random() for mixup and, on mixup, randint(0, n - 1), a second load_mosaic and np.random.beta(32, 32) -- or the letterbox branch with its one
+    random_perspective; np.random.uniform(-1, 1, 3) if an HSV gain is non-zero; random.random() for flipud, then for fliplr.
+    hw: the cached (h, w) of every image; pool: the epoch's order (default range(n)); n: the number of images (default len(hw))."""
+    s = int(img_size)
+    n = len(hw) if n is None else int(n)
+    pool = range(n) if pool is None else pool
+    ratio = None
+    if mosaic and random.random() < hyp["mosaic"]:
+        is_mosaic = True
+        mosaics = [draw_mosaic(index, hw, hyp, s, pool)]
+        if random.random() < hyp["mixup"]:
+            mosaics.append(draw_mosaic(random.randint(0, n - 1), hw, hyp, s, pool))
+            ratio = float(np.random.beta(32.0, 32.0))
+    else:
+        is_mosaic = False
+        h, w = hw[index]
+        dw, dh = (s - w) / 2, (s - h) / 2
+        top, left = round(dh - 0.1), round(dw - 0.1)
+        M, scale = draw_perspective(hyp, s, 0)
+        mosaics = [Mosaic([int(index)], [(left, top, left + w, top + h, 0, 0, w, h)], M, scale, s, [(dw, dh)])]
+    luts = None
+    if hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"]:
+        r = np.random.uniform(-1, 1, 3) * [hyp["hsv_h"], hyp["hsv_s"], hyp["hsv_v"]] + 1
+        x = np.arange(0, 256, dtype=r.dtype)
+        luts = np.stack([((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8), np.clip(x * r[2], 0, 255).astype(np.uint8)])
+    flipud = random.random() < hyp["flipud"]
+    fliplr = random.random() < hyp["fliplr"]
+    return Item(int(index), mosaics, ratio, luts, bool(flipud), bool(fliplr), is_mosaic)
+
+
+def invert_affine(M):
+    """cv2.invertAffineTransform of the first two rows, float64 -> (A00, A01, A02, A10, A11, A12)"""
+    m00, m01, m02, m10, m11, m12 = (float(v) for v in np.asarray(M, dtype=np.float64)[:2].reshape(-1))
+    D = m00 * m11 - m01 * m10
+    D = 1.0 / D if D != 0 else 0.0
+    a00, a11 = m11 * D, m00 * D
+    a01, a10 = m01 * -D, m10 * -D
+    return a00, a01, -a00 * m02 - a01 * m12, a10, a11, -a10 * m02 - a11 * m12
+
+
+def pack_items(items, out=None) -> np.ndarray:
+    """the records of a batch: a structured array of ITEM (1360 bytes each), written into `out` when given"""
+    rec = np.zeros(len(items), dtype=ITEM) if out is None else out
+    rec[...] = np.zeros((), dtype=ITEM)
+    for b, it in enumerate(items):
+        r = rec[b]
+        r["nmos"], r["flipud"], r["fliplr"], r["hsv"] = len(it.mosaics), int(it.flipud), int(it.fliplr), int(it.luts is not None)
+        if it.ratio is not None:
+            r["ratio"], r["ratio1"] = it.ratio, 1 - it.ratio
+        if it.luts is not None:
+            r["lut"] = it.luts
+        for k, mo in enumerate(it.mosaics):
+            m = r["mosaics"][k]
+            m["inv"], m["m"], m["scale"] = invert_affine(mo.M), mo.M[:2].reshape(-1), mo.scale
+            m["ntiles"], m["canvas"], m["clip"] = len(mo.indices), mo.canvas, int(it.mosaic)
+            for t, (j, rect, (padw, padh)) in enumerate(zip(mo.indices, mo.rects, mo.pad)):
+                x1a, y1a, x2a, y2a, x1b, y1b = rect[:6]
+                m["tiles"][t] = (j, x1a, y1a, x2a, y2a, x1a - x1b, y1a - y1b, padw, padh, 0)
+    return rec
+
+
+class DeviceTrainDataset(DeviceDataset):
+    """The cached images and labels of an augment=True, rect=False dataset in device memory (the arena, the record table, the label table and the chunked upload of
+    DeviceDataset); iterating yields the reference loader's 4-tuples with mosaic, random_perspective (affine), augment_hsv, the flips and mixup applied on the
+    device.  shapes[i] is None for a mosaic item, the letterbox tuple otherwise.  hyp: the reference's hyperparameter dict (HYP_KEYS are read)."""
+
+    def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, mosaic=True, device="cuda", dtype=torch.uint8,
+                 rect=False, segments=None):
+        # every refusal comes before anything is uploaded
+        hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
+        if hyp["perspective"] != 0:
+            raise ValueError(f"DeviceTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
+        if hyp["copy_paste"] != 0:
+            raise ValueError(f"DeviceTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        if segments is not None and any(len(sg) for sg in segments):
+            raise ValueError("DeviceTrainDataset: the dataset holds polygon labels (a non-empty segments[i]); they warp differently and are not built")
+        if rect:
+            raise ValueError("DeviceTrainDataset: rect=True; the reference sets mosaic = augment and not rect, use DeviceDataset for rectangular batches")
+        if int(img_size) != img_size or int(img_size) < 16 or int(img_size) % 16:
+            raise ValueError(f"DeviceTrainDataset: img_size = {img_size} must be a multiple of 16 (hence even: the mosaic border is img_size / 2)")
+        for i, im in enumerate(images):
+            if isinstance(im, np.ndarray) and im.ndim == 3 and max(im.shape[:2]) != int(img_size):
+                raise ValueError(f"DeviceTrainDataset: image {paths[i] if paths is not None else i} is {im.shape[0]}x{im.shape[1]}: its long side is not img_size = "
+                                 f"{img_size} (load_image's cv2.resize is out of scope)")
+        super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=False, shapes0=shapes0, paths=paths, single_cls=single_cls,
+                         device=device, dtype=dtype)
+        self.hyp, self.mosaic = hyp, bool(mosaic)
+        self.hw = [tuple(int(v) for v in im.shape[:2]) for im in images]
+        self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
+        self._stage_rec = self._stage.numpy().view(ITEM)
+        self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
+
+    @classmethod
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False):
+        """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=False: reads .ims, .im_hw0, .im_hw, .labels, .segments, .im_files, .hyp,
+        .img_size, .stride, .rect, .mosaic and .indices (the epoch's order)."""
+        ims = list(dataset.ims)
+        if any(im is None for im in ims):
+            raise ValueError('DeviceTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
+        if not getattr(dataset, "augment", False):
+            raise ValueError("DeviceTrainDataset.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
+        ds = cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
+                 paths=dataset.im_files, single_cls=single_cls, mosaic=getattr(dataset, "mosaic", True), device=device, dtype=dtype, rect=bool(dataset.rect),
+                 segments=getattr(dataset, "segments", None))
+        indices = getattr(dataset, "indices", None)
+        if indices is not None and list(indices) != list(range(ds.n)):
+            ds.set_indices(indices)
+        return ds
+
+    def draw_batch(self, k: int):
+        """the items of batch k, drawn now from the global generators: a list of Item"""
+        pool = range(self.n) if self._perm is None else self._perm.tolist()
+        return [draw_item(i, self.hw, self.hyp, self.img_size, pool, self.n, self.mosaic) for i in self.batch_images(k)]
+
+    def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
+        """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
+        items = self.draw_batch(k) if items is None else items
+        count = len(items)
+        pack_items(items, self._stage_rec[:count])
+        nbytes = count * ITEM.itemsize
+        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
+        upper = int(sum(self._counts[j] for it in items for mo in it.mosaics for j in mo.indices))
+        im = ops.augment_batch(self._arena, self._records, self.n, self._items_dev, count, self.img_size, self.dtype, out)
+        targets, offsets = ops.augment_targets(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
+        nl = int(offsets.cpu()[count])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
+        return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)

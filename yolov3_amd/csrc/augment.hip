@@ -1,0 +1,427 @@
+// The train-mode loader on the device (gfx950): what the reference's LoadImagesAndLabels.__getitem__ does per item on the host for an augment=True, rect=False set whose
+// images are cached already resized (utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283) --
+//   * load_mosaic's paste of four images into a 2s x 2s canvas of 114 (or letterbox's border around one), random_perspective's cv2.warpAffine, mixup's blend, augment_hsv,
+//     np.flipud / np.fliplr, transpose((2, 0, 1))[::-1] and torch.stack                      -> augment_batch_kernel, ONE launch per batch; the canvas is never materialised;
+//   * xywhn2xyxy per tile, the clip to the canvas, the four-corner transform, box_candidates, xyxy2xywhn(clip=True, eps=1e-3), the flips of the labels, mixup's
+//     concatenation and collate_fn                                                            -> augment_targets_kernel, ONE launch per batch.
+// The host draws the random numbers and sends one y3_augment_item per item (yolov3_amd/augment.py); the images lie in the arena of csrc/dataset.hip with its record table.
+// Every arena read is bounded by the arena whatever the records hold: a tile is cut down, when the block starts, to the part of its rectangle whose source pixels lie
+// inside its image, and an image that does not lie inside the arena gives no tile at all (its pixels read as 114).
+//
+// The sampler is the 8-bit INTER_LINEAR of cv2.warpAffine as tests/augment_cases.py::warp_affine_u8 states it: the inverse matrix in float64 from the host, the source
+// coordinate in 1 / 32 pixel as (rint((A01 y + A02) 1024) + 16 + rint(A00 x 1024)) >> 5, four taps weighted by (32 - fy | fy)(32 - fx | fx), + 512 >> 10; a tap outside the
+// canvas or in no tile is 114.  The colour conversions are bgr2hsv_u8 (integer) and hsv2bgr_u8 (fp32, one rounding per operation) of the same file.  Built with
+// -ffp-contract=off: every product and sum below rounds on its own, as NumPy's do.
+#include "y3_common.h"
+
+namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int BT = 256;
+constexpr int CHUNK = 1024;        // consecutive output pixels of one item per block (4 per lane)
+constexpr int BORDER = 114;
+constexpr int MAX_S = 4096;
+constexpr int MAX_BS = 1024;
+constexpr int SLOTS = 8;           // tiles of an item: 2 mosaics x 4
+
+struct BatchArgs {
+    const unsigned char* arena;
+    long long arena_bytes;
+    const y3_dataset_image* images;
+    long long n_images;
+    const y3_augment_item* items;
+    void* dst;
+    int count, S, pixels;          // pixels = S * S
+    y3_divisor s_div;
+};
+
+template <typename D> Y3_DEV void store_px(D* d, const float* v);   // 16 bytes: 16 / sizeof(D) values
+template <> Y3_DEV void store_px<float>(float* d, const float* v) {
+    const f32x4 q = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(d) = q;
+}
+template <> Y3_DEV void store_px<f16_t>(f16_t* d, const float* v) {
+    const u32x4 q = {pack2<f16_t>(v[0], v[1]), pack2<f16_t>(v[2], v[3]), pack2<f16_t>(v[4], v[5]), pack2<f16_t>(v[6], v[7])};
+    *reinterpret_cast<u32x4*>(d) = q;
+}
+template <> Y3_DEV void store_px<bf16_t>(bf16_t* d, const float* v) {
+    const u32x4 q = {pack2<bf16_t>(v[0], v[1]), pack2<bf16_t>(v[2], v[3]), pack2<bf16_t>(v[4], v[5]), pack2<bf16_t>(v[6], v[7])};
+    *reinterpret_cast<u32x4*>(d) = q;
+}
+
+Y3_DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// The tiles of one item as the block uses them: the rectangle on the canvas (empty when the tile is absent or invalid) and the arena address of canvas pixel (0, 0)
+// of that tile's image: pixel (X, Y) of the rectangle is at base + Y * pitch + 3 X.
+struct Tiles {
+    int x1[SLOTS], y1[SLOTS], x2[SLOTS], y2[SLOTS], pitch[SLOTS];
+    long long base[SLOTS];
+};
+
+Y3_DEV void setup_tile(Tiles& T, int slot, const BatchArgs& a, const y3_augment_item* it) {
+    const int m = slot >> 2, t = slot & 3;
+    int x1 = 0, y1 = 0, x2 = 0, y2 = 0, pitch = 0;
+    long long base = 0;
+    const y3_augment_mosaic* mo = &it->mosaics[m];
+    if (m < clampi(it->nmos, 0, 2) && t < clampi(mo->ntiles, 0, 4)) {
+        const y3_augment_tile tl = mo->tiles[t];
+        const int canvas = clampi(mo->canvas, 0, 2 * MAX_S);
+        if (tl.img >= 0 && tl.img < a.n_images) {
+            const y3_dataset_image r = a.images[tl.img];
+            if (r.w >= 1 && r.h >= 1 && r.w <= 0xffff && r.h <= 0xffff && r.offset >= 0 && r.offset <= a.arena_bytes && 3LL * r.w * r.h <= a.arena_bytes - r.offset) {
+                // the part of the rectangle that lies on the canvas AND whose source pixel (X - padw, Y - padh) lies in the image
+                const long long lx = tl.padw > 0 ? tl.padw : 0, ly = tl.padh > 0 ? tl.padh : 0;
+                long long hx = (long long)tl.padw + r.w, hy = (long long)tl.padh + r.h;
+                hx = hx < canvas ? hx : canvas;
+                hy = hy < canvas ? hy : canvas;
+                const long long ax1 = tl.x1 > lx ? tl.x1 : lx, ay1 = tl.y1 > ly ? tl.y1 : ly, ax2 = tl.x2 < hx ? tl.x2 : hx, ay2 = tl.y2 < hy ? tl.y2 : hy;
+                if (ax1 < ax2 && ay1 < ay2) {
+                    x1 = (int)ax1; y1 = (int)ay1; x2 = (int)ax2; y2 = (int)ay2;   // all in [0, canvas]
+                    pitch = 3 * r.w;
+                    base = r.offset - ((long long)tl.padh * r.w + tl.padw) * 3;
+                }
+            }
+        }
+    }
+    T.x1[slot] = x1; T.y1[slot] = y1; T.x2[slot] = x2; T.y2[slot] = y2; T.pitch[slot] = pitch; T.base[slot] = base;
+}
+
+// one tap of mosaic m: the canvas pixel (tx, ty) as B | G << 8 | R << 16
+Y3_DEV unsigned tap(const Tiles& T, const unsigned char* arena, int m, long long tx, long long ty) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int s = m * 4 + t;
+        if (tx >= T.x1[s] && tx < T.x2[s] && ty >= T.y1[s] && ty < T.y2[s]) {
+            const unsigned char* p = arena + (T.base[s] + ty * T.pitch[s] + tx * 3);
+            return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+        }
+    }
+    return (unsigned)BORDER * 0x010101u;
+}
+
+// the warped mosaic m at output pixel (x, y): warp_affine_u8
+Y3_DEV void sample(const Tiles& T, const unsigned char* arena, const y3_augment_mosaic* mo, int m, int x, int y, int* bgr) {
+    const double a00 = mo->inv[0], a01 = mo->inv[1], a02 = mo->inv[2], a10 = mo->inv[3], a11 = mo->inv[4], a12 = mo->inv[5];
+    const double xd = (double)x, yd = (double)y;
+    const long long X = ((long long)rint((a01 * yd + a02) * 1024.0) + 16 + (long long)rint(a00 * xd * 1024.0)) >> 5;
+    const long long Y = ((long long)rint((a11 * yd + a12) * 1024.0) + 16 + (long long)rint(a10 * xd * 1024.0)) >> 5;
+    const long long sx = X >> 5, sy = Y >> 5;
+    const int fx = (int)(X & 31), fy = (int)(Y & 31);
+    const unsigned p00 = tap(T, arena, m, sx, sy), p01 = tap(T, arena, m, sx + 1, sy), p10 = tap(T, arena, m, sx, sy + 1), p11 = tap(T, arena, m, sx + 1, sy + 1);
+    const int w00 = (32 - fy) * (32 - fx), w01 = (32 - fy) * fx, w10 = fy * (32 - fx), w11 = fy * fx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int sh = 8 * c;
+        const int acc = w00 * (int)((p00 >> sh) & 255u) + w01 * (int)((p01 >> sh) & 255u) + w10 * (int)((p10 >> sh) & 255u) + w11 * (int)((p11 >> sh) & 255u);
+        bgr[c] = (acc + 512) >> 10;
+    }
+}
+
+// One block: CHUNK consecutive pixels (row-major) of one item.  Lane `tid` takes pixels tid, tid + 256, ...: consecutive lanes, consecutive pixels of a row, so with
+// little rotation the taps of a wave lie next to each other in the arena.  The three bytes of a pixel go to LDS planes; then every lane stores 16 bytes per pass.
+template <typename D> __global__ __launch_bounds__(BT) void augment_batch_kernel(const BatchArgs a) {
+    constexpr bool U8 = sizeof(D) == 1;
+    constexpr int PX = 16 / (int)sizeof(D);
+    __shared__ Tiles T;
+    __shared__ unsigned char s_lut[3 * 256];
+    __shared__ int s_sdiv[256], s_hdiv[256];
+    __shared__ float s_q[U8 ? 1 : 256];
+    __shared__ __attribute__((aligned(16))) unsigned char s_out[3][CHUNK];
+    const int tid = threadIdx.x, b = blockIdx.y, first = blockIdx.x * CHUNK;
+    const y3_augment_item* it = a.items + b;
+    const int nmos = clampi(it->nmos, 0, 2);
+    const bool hsv = it->hsv != 0, ud = it->flipud != 0, lr = it->fliplr != 0;
+    if (tid < SLOTS) setup_tile(T, tid, a, it);
+    if constexpr (!U8) s_q[tid] = (float)tid / 255.0f;
+    if (hsv) {
+        const unsigned char* l = &it->lut[0][0];
+        for (int i = tid; i < 3 * 256; i += BT) s_lut[i] = l[i];
+        s_sdiv[tid] = tid ? (int)rint((double)(255 << 12) / (1.0 * tid)) : 0;
+        s_hdiv[tid] = tid ? (int)rint((double)(180 << 12) / (6.0 * tid)) : 0;
+    }
+    __syncthreads();
+    const int valid = a.pixels - first < CHUNK ? a.pixels - first : CHUNK;   // a multiple of 256: S is one of 16
+    const double r0 = it->ratio, r1 = it->ratio1;
+    for (int k = tid; k < valid; k += BT) {
+        const int p = first + k;
+        const int y = y3_fdiv(p, a.s_div), x = p - y * a.S;
+        const int ox = lr ? a.S - 1 - x : x, oy = ud ? a.S - 1 - y : y;
+        int c0[3] = {BORDER, BORDER, BORDER};
+        if (nmos >= 1) sample(T, a.arena, &it->mosaics[0], 0, ox, oy, c0);
+        if (nmos == 2) {   // mixup: (im * r + im2 * (1 - r)).astype(uint8) in float64
+            int c1[3];
+            sample(T, a.arena, &it->mosaics[1], 1, ox, oy, c1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                double v = (double)c0[c] * r0 + (double)c1[c] * r1;
+                v = v > 0.0 ? v : 0.0;   // (also a NaN of a record that is no record)
+                v = v < 255.0 ? v : 255.0;
+                c0[c] = (int)v;
+            }
+        }
+        if (hsv) {
+            // bgr2hsv_u8
+            const int B = c0[0], G = c0[1], R = c0[2];
+            const int v = max(max(B, G), R), diff = v - min(min(B, G), R);
+            int s = (diff * s_sdiv[v] + (1 << 11)) >> 12;
+            int h = v == R ? G - B : (v == G ? B - R + 2 * diff : R - G + 4 * diff);
+            h = (h * s_hdiv[diff] + (1 << 11)) >> 12;
+            h += h < 0 ? 180 : 0;
+            h = clampi(h, 0, 255);
+            s = clampi(s, 0, 255);
+            // the look-up tables
+            const int H2 = s_lut[h], S2 = s_lut[256 + s], V2 = s_lut[512 + v];
+            // hsv2bgr_u8
+            const float hf = (float)H2 * (6.0f / 180.0f), sf = (float)S2 * (1.0f / 255.0f), vf = (float)V2 * (1.0f / 255.0f);
+            float sec = floorf(hf), f = hf - sec;
+            int sector = (int)sec;
+            if ((unsigned)sector >= 6u) { sector = 0; f = 0.0f; }
+            const float t0 = vf, t1 = vf * (1.0f - sf), t2 = vf * (1.0f - sf * f), t3 = vf * (1.0f - sf * (1.0f - f));
+            float fb, fg, fr;   // sector table {1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0}
+            switch (sector) {
+                case 0: fb = t1; fg = t3; fr = t0; break;
+                case 1: fb = t1; fg = t0; fr = t2; break;
+                case 2: fb = t3; fg = t0; fr = t1; break;
+                case 3: fb = t0; fg = t2; fr = t1; break;
+                case 4: fb = t0; fg = t1; fr = t3; break;
+                default: fb = t2; fg = t1; fr = t0; break;
+            }
+            if (S2 == 0) fb = fg = fr = vf;
+            c0[0] = clampi((int)rintf(fb * 255.0f), 0, 255);
+            c0[1] = clampi((int)rintf(fg * 255.0f), 0, 255);
+            c0[2] = clampi((int)rintf(fr * 255.0f), 0, 255);
+        }
+        s_out[0][k] = (unsigned char)c0[2];   // RGB planes of a BGR pixel
+        s_out[1][k] = (unsigned char)c0[1];
+        s_out[2][k] = (unsigned char)c0[0];
+    }
+    __syncthreads();
+    D* dst = (D*)a.dst + (long long)b * 3 * a.pixels + first;
+    const int per = valid / PX, segs = 3 * per;   // 16-byte stores of the block
+    for (int i = tid; i < segs; i += BT) {
+        const int c = i / per, j = (i - c * per) * PX;
+        if constexpr (U8) {
+            *reinterpret_cast<u32x4*>(dst + (long long)c * a.pixels + j) = *reinterpret_cast<const u32x4*>(&s_out[c][j]);
+        } else {
+            float v[PX];
+#pragma unroll
+            for (int e = 0; e < PX; ++e) v[e] = s_q[s_out[c][j + e]];
+            store_px<D>(dst + (long long)c * a.pixels + j, v);
+        }
+    }
+}
+
+struct TargetArgs {
+    const float* labels;
+    const long long* label_offsets;
+    const y3_dataset_image* images;
+    long long n_images;
+    const y3_augment_item* items;
+    float* out;
+    long long n_rows;
+    long long* out_offsets;
+    int count, S;
+    float clip_s;   // S - eps: computed in double, rounded to fp32 once
+};
+
+// the label rows of tile `slot` of the batch: [beg, end) of the table, or nothing
+Y3_DEV void tile_rows(const TargetArgs& a, long long total, int slot, long long& beg, long long& end) {
+    beg = end = 0;
+    const y3_augment_item* it = a.items + (slot >> 3);
+    const int m = (slot >> 2) & 1, t = slot & 3;
+    const y3_augment_mosaic* mo = &it->mosaics[m];
+    if (m >= clampi(it->nmos, 0, 2) || t >= clampi(mo->ntiles, 0, 4)) return;
+    const long long img = mo->tiles[t].img;
+    if (img < 0 || img >= a.n_images) return;
+    beg = a.label_offsets[img];
+    end = a.label_offsets[img + 1];
+    beg = beg < 0 ? 0 : (beg > total ? total : beg);   // a table that does not describe `labels` reads nothing outside it
+    end = end < beg ? beg : (end > total ? total : end);
+    if (end - beg > (1 << 20)) end = beg + (1 << 20);
+}
+
+// ONE block per batch.  The prefix of the label counts of the batch's tiles (item, mosaic, tile: the reference's order) lives in LDS; the block walks the rows 256 at
+// a time: a lane transforms one label and decides whether box_candidates keeps it, a ballot and the waves' counts give every survivor its place behind the
+// survivors before it, and the per-item counts become the bs + 1 offsets.  Survivors past n_rows are dropped (and not counted).
+__global__ __launch_bounds__(BT) void augment_targets_kernel(const TargetArgs a) {
+    __shared__ int s_pref[MAX_BS * SLOTS + 1];
+    __shared__ int s_cnt[MAX_BS];
+    __shared__ int s_wave[BT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nslots = a.count * SLOTS;
+    const long long total = a.label_offsets[a.n_images];
+    for (int s = tid; s < nslots; s += BT) {
+        long long beg, end;
+        tile_rows(a, total, s, beg, end);
+        s_pref[s + 1] = (int)(end - beg);
+    }
+    for (int b = tid; b < a.count; b += BT) s_cnt[b] = 0;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        s_pref[0] = 0;
+        for (int s = 0; s < nslots; ++s) {
+            const int n = s_pref[s + 1];
+            run = run > 0x3fffffff - n ? 0x3fffffff : run + n;
+            s_pref[s + 1] = run;
+        }
+    }
+    __syncthreads();
+    const int have = s_pref[nslots];
+    const float Sf = (float)a.S;
+    const double Sd = (double)a.S;
+    long long running = 0;
+    for (int base = 0; base < have; base += BT) {
+        const int j = base + tid;
+        bool keep = false;
+        int b = 0;
+        float cls = 0.0f, ox = 0.0f, oy = 0.0f, ow = 0.0f, oh = 0.0f;
+        if (j < have) {
+            int lo = 0, hi = nslots - 1;   // the last slot with s_pref[slot] <= j
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (s_pref[mid] <= j) lo = mid;
+                else hi = mid - 1;
+            }
+            long long beg, end;
+            tile_rows(a, total, lo, beg, end);
+            const long long row = beg + (j - s_pref[lo]);
+            if (row < end) {
+                b = lo >> 3;
+                const y3_augment_item* it = a.items + b;
+                const y3_augment_mosaic* mo = &it->mosaics[(lo >> 2) & 1];
+                const y3_augment_tile tl = mo->tiles[lo & 3];
+                const y3_dataset_image im = a.images[tl.img];
+                const float* l = a.labels + row * 5;
+                cls = l[0];
+                const float xc = l[1], yc = l[2], bw = l[3], bh = l[4];
+                const float wf = (float)im.w, hf = (float)im.h;
+                // xywhn2xyxy with the tile's w, h, padw, padh (fp32)
+                const float hw2 = bw / 2.0f, hh2 = bh / 2.0f;
+                float x1 = wf * (xc - hw2) + tl.lpadw;
+                float y1 = hf * (yc - hh2) + tl.lpadh;
+                float x2 = wf * (xc + hw2) + tl.lpadw;
+                float y2 = hf * (yc + hh2) + tl.lpadh;
+                if (mo->clip) {   // np.clip(x, 0, 2 s) of load_mosaic
+                    const float c = (float)mo->canvas;
+                    x1 = x1 < 0.0f ? 0.0f : x1; x1 = x1 > c ? c : x1;
+                    y1 = y1 < 0.0f ? 0.0f : y1; y1 = y1 > c ? c : y1;
+                    x2 = x2 < 0.0f ? 0.0f : x2; x2 = x2 > c ? c : x2;
+                    y2 = y2 < 0.0f ? 0.0f : y2; y2 = y2 > c ? c : y2;
+                }
+                // the four corners through M in fp64, each coordinate a plain left-to-right sum of three terms
+                const double m00 = mo->m[0], m01 = mo->m[1], m02 = mo->m[2], m10 = mo->m[3], m11 = mo->m[4], m12 = mo->m[5];
+                const double px[4] = {(double)x1, (double)x2, (double)x1, (double)x2}, py[4] = {(double)y1, (double)y2, (double)y2, (double)y1};
+                double nx1 = 0, ny1 = 0, nx2 = 0, ny2 = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double X = px[q] * m00 + py[q] * m01 + m02, Y = px[q] * m10 + py[q] * m11 + m12;
+                    nx1 = q == 0 || X < nx1 ? X : nx1; nx2 = q == 0 || X > nx2 ? X : nx2;
+                    ny1 = q == 0 || Y < ny1 ? Y : ny1; ny2 = q == 0 || Y > ny2 ? Y : ny2;
+                }
+                nx1 = nx1 < 0.0 ? 0.0 : nx1; nx1 = nx1 > Sd ? Sd : nx1;
+                nx2 = nx2 < 0.0 ? 0.0 : nx2; nx2 = nx2 > Sd ? Sd : nx2;
+                ny1 = ny1 < 0.0 ? 0.0 : ny1; ny1 = ny1 > Sd ? Sd : ny1;
+                ny2 = ny2 < 0.0 ? 0.0 : ny2; ny2 = ny2 > Sd ? Sd : ny2;
+                // box_candidates(box1 = targets * s (fp32), box2 = new (fp64), wh_thr 2, ar_thr 100, area_thr 0.1, eps 1e-16)
+                const float sc = (float)mo->scale;
+                const float w1 = x2 * sc - x1 * sc, h1 = y2 * sc - y1 * sc;
+                const double w2 = nx2 - nx1, h2 = ny2 - ny1, eps = 1e-16;
+                const double r1 = w2 / (h2 + eps), r2 = h2 / (w2 + eps), ar = r1 > r2 ? r1 : r2;
+                const float den = w1 * h1 + (float)eps;
+                keep = w2 > 2.0 && h2 > 2.0 && w2 * h2 / (double)den > 0.1 && ar < 100.0;
+                // the survivor as fp32, xyxy2xywhn(clip=True, eps=1e-3), the flips
+                float fx1 = (float)nx1, fy1 = (float)ny1, fx2 = (float)nx2, fy2 = (float)ny2;
+                fx1 = fx1 < 0.0f ? 0.0f : fx1; fx1 = fx1 > a.clip_s ? a.clip_s : fx1;
+                fx2 = fx2 < 0.0f ? 0.0f : fx2; fx2 = fx2 > a.clip_s ? a.clip_s : fx2;
+                fy1 = fy1 < 0.0f ? 0.0f : fy1; fy1 = fy1 > a.clip_s ? a.clip_s : fy1;
+                fy2 = fy2 < 0.0f ? 0.0f : fy2; fy2 = fy2 > a.clip_s ? a.clip_s : fy2;
+                ox = ((fx1 + fx2) / 2.0f) / Sf;
+                oy = ((fy1 + fy2) / 2.0f) / Sf;
+                ow = (fx2 - fx1) / Sf;
+                oh = (fy2 - fy1) / Sf;
+                if (it->flipud) oy = 1.0f - oy;
+                if (it->fliplr) ox = 1.0f - ox;
+            }
+        }
+        const unsigned long long vote = __ballot(keep);
+        if (lane == 0) s_wave[wave] = __popcll(vote);
+        __syncthreads();
+        int before = __popcll(vote & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+        for (int w = 0; w < BT / 64; ++w) {
+            before += w < wave ? s_wave[w] : 0;
+            all += s_wave[w];
+        }
+        const long long pos = running + before;
+        if (keep && pos < a.n_rows) {
+            float* o = a.out + pos * 6;
+            o[0] = (float)b; o[1] = cls; o[2] = ox; o[3] = oy; o[4] = ow; o[5] = oh;
+            atomicAdd(&s_cnt[b], 1);
+        }
+        running += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        long long run = 0;
+        a.out_offsets[0] = 0;
+        for (int b = 0; b < a.count; ++b) {
+            run += s_cnt[b];
+            a.out_offsets[b + 1] = run;
+        }
+    }
+}
+
+bool aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+
+int check_set(const char* fn, const void* images, int64_t n_images, const void* items, int32_t count, int32_t S) {
+    if (!images || !items) Y3_FAIL("%s: null argument", fn);
+    if (n_images < 1 || n_images > 0x7fffffffLL || count < 0 || count > MAX_BS || S < 16 || S > MAX_S)
+        Y3_FAIL("%s: bad geometry (%lld images in 1 .. 2^31 - 1, a batch of %d in 0 .. %d items of %d x %d in 16 .. %d)", fn, (long long)n_images, count, MAX_BS, S, S, MAX_S);
+    if (S % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, S);
+    if (!aligned(images, 8) || !aligned(items, 8)) Y3_FAIL("%s: the record table and the items must be 8-byte aligned", fn);
+    return 0;
+}
+
+}  // namespace
+
+static_assert(sizeof(y3_augment_tile) == 40 && sizeof(y3_augment_mosaic) == 280 && sizeof(y3_augment_item) == 1360, "the records yolov3_amd/augment.py packs");
+
+extern "C" int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                                void* dst, int32_t dst_dtype, int32_t S, void* stream) {
+    if (!arena || !dst) Y3_FAIL("y3_augment_batch: null argument");
+    if (check_set("y3_augment_batch", images, n_images, items, count, S)) return -1;
+    if (arena_bytes < 4 || (arena_bytes & 3)) Y3_FAIL("y3_augment_batch: the arena's %lld bytes are not a positive multiple of 4", (long long)arena_bytes);
+    if (!aligned(arena, 16) || !aligned(dst, 16)) Y3_FAIL("y3_augment_batch: the arena and the output must be 16-byte aligned");
+    if (dst_dtype != Y3_U8 && dst_dtype != Y3_F16 && dst_dtype != Y3_BF16 && dst_dtype != Y3_F32) Y3_FAIL("y3_augment_batch: unsupported output dtype %d (uint8 / float16 / bfloat16 / float32)", dst_dtype);
+    if (count == 0) return 0;
+    BatchArgs a;
+    a.arena = arena; a.arena_bytes = arena_bytes; a.images = images; a.n_images = n_images; a.items = items; a.dst = dst;
+    a.count = count; a.S = S; a.pixels = S * S;
+    a.s_div = y3_make_divisor(S);
+    const dim3 grid((unsigned)((a.pixels + CHUNK - 1) / CHUNK), (unsigned)count);
+    hipStream_t st = (hipStream_t)stream;
+    switch (dst_dtype) {
+        case Y3_U8: hipLaunchKernelGGL(augment_batch_kernel<unsigned char>, grid, dim3(BT), 0, st, a); break;
+        case Y3_F16: hipLaunchKernelGGL(augment_batch_kernel<f16_t>, grid, dim3(BT), 0, st, a); break;
+        case Y3_BF16: hipLaunchKernelGGL(augment_batch_kernel<bf16_t>, grid, dim3(BT), 0, st, a); break;
+        default: hipLaunchKernelGGL(augment_batch_kernel<float>, grid, dim3(BT), 0, st, a); break;
+    }
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                  int32_t count, int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
+    if (!label_offsets || !offsets || (n_rows > 0 && (!labels || !targets))) Y3_FAIL("y3_augment_targets: null argument");
+    if (check_set("y3_augment_targets", images, n_images, items, count, S)) return -1;
+    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("y3_augment_targets: bad geometry (%lld rows)", (long long)n_rows);
+    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(labels, 4) || !aligned(targets, 4)) Y3_FAIL("y3_augment_targets: the offsets must be 8-byte, the fp32 tables 4-byte aligned");
+    TargetArgs a;
+    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
+    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.S = S;
+    a.clip_s = (float)((double)S - 1e-3);
+    hipLaunchKernelGGL(augment_targets_kernel, dim3(1), dim3(BT), 0, (hipStream_t)stream, a);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}

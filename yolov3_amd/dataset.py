@@ -214,7 +214,7 @@ class DeviceDataset:
         if any(im is None for im in ims):
             raise ValueError('DeviceDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
         if getattr(dataset, "augment", False):
-            raise ValueError("DeviceDataset.from_dataset: the dataset augments (augment=True); only the augment=False path is here")
+            raise ValueError("DeviceDataset.from_dataset: the dataset augments (augment=True); only the augment=False path is here, DeviceTrainDataset is the train-mode loader")
         for i, (im, hw) in enumerate(zip(ims, dataset.im_hw)):
             if isinstance(im, np.ndarray) and tuple(im.shape[:2]) != tuple(int(v) for v in hw):
                 raise ValueError(f"DeviceDataset.from_dataset: im_hw[{i}] = {tuple(hw)} is not the cached image's {im.shape[:2]}")
