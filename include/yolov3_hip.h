@@ -177,6 +177,16 @@ int y3_copy_slice(const y3_tensor* x, const y3_tensor* y, int32_t dtype, void* s
  * Arithmetic rounds after every op in `dtype`, as torch does for half tensors. */
 int y3_detect_decode(const y3_tensor* head, int32_t dtype, int32_t na, int32_t no, const float* anchors_px,
                      float stride, void* raw, void* z, int64_t row_offset, int64_t total_rows, void* stream);
+/* The same for n_levels (1..5) levels of one head in ONE launch of the tiled kernel of the 2-byte dtypes (16-byte loads and
+ * stores, sigmoid from a 64 Ki-entry table of the very expression): heads[l], anchors_px[l*na*2 ..], strides[l],
+ * raws[l] (raws or any entry may be NULL) and row_offsets[l] per level; z (may be NULL), total_rows, dtype, na, no common.
+ * Every level must be eligible: f16 / bf16, 16-byte aligned head (pitch % 8 == 0), raw and z, and row_offset*no,
+ * total_rows*no and ny*nx*no multiples of 8.  Otherwise (and with the knob decode_tile = 0) it returns non-zero, launches
+ * NOTHING and sets y3_last_error: call y3_detect_decode per level, which takes the same kernel for eligible arguments and
+ * the element kernels for the rest.  Results are bit for bit those of the per-level calls. */
+int y3_detect_decode_levels(const y3_tensor* heads, int32_t n_levels, int32_t dtype, int32_t na, int32_t no,
+                            const float* anchors_px, const float* strides, void* const* raws, void* z,
+                            const int64_t* row_offsets, int64_t total_rows, void* stream);
 
 /* Batched non_max_suppression: reference utils/general.py:630-750 incl. torchvision.ops.nms (:733).
  * pred: contiguous (bs, n_rows, 5+nc) of `dtype`.  Output: out_rows (bs, max_det, 6) fp32

@@ -112,6 +112,8 @@ _SIGNATURES = {
     "y3_upsample2x": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p]),
     "y3_copy_slice": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p]),
     "y3_detect_decode": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, _P(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "y3_detect_decode_levels": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float), _P(C.c_void_p), C.c_void_p, _P(C.c_int64),
+                                          C.c_int64, C.c_void_p]),
     "y3_nms_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, _P(Y3NmsParams), C.c_int64]),
     "y3_nms": (
         C.c_int,

@@ -19,6 +19,8 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include <atomic>
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------ decode
@@ -54,17 +56,21 @@ __global__ __launch_bounds__(256) void decode_kernel(const T* __restrict__ head,
 
 // One decoded element: the reference's op order with a round-to-T after every op (models/yolo.py:104-108 run in T).
 template <typename T>
+Y3_DEV float decode_finish(float s, int o, int x, int y, float stride, float aw, float ah);
+template <typename T> Y3_DEV T sigmoid_T(float v) { return from_f32<T>(1.0f / (1.0f + expf(-v))); }   // the sigmoid, rounded to T (ONE expression: decode_one and the table of decode_tile_kernel)
+template <typename T>
 Y3_DEV float decode_one(float v, int o, int x, int y, float stride, float aw, float ah) {
-    const float s = rt<T>(1.0f / (1.0f + expf(-v)));
-    if (o < 2) {
-        const float g = rt<T>((o == 0 ? (float)x : (float)y) - 0.5f);
-        return rt<T>(rt<T>(rt<T>(s * 2.0f) + g) * rt<T>(stride));
-    }
-    if (o < 4) {
-        const float d = rt<T>(s * 2.0f);
-        return rt<T>(rt<T>(d * d) * (o == 2 ? aw : ah));
-    }
-    return s;
+    return decode_finish<T>(to_f32<T>(sigmoid_T<T>(v)), o, x, y, stride, aw, ah);
+}
+// everything behind the sigmoid `s` (a value of T).  Straight-line: both box forms are evaluated and one result is selected -- the tiled kernel runs this on lanes whose `o`
+// differ, where branches cost more than the few operations they skip
+template <typename T>
+Y3_DEV float decode_finish(float s, int o, int x, int y, float stride, float aw, float ah) {
+    const float d = rt<T>(s * 2.0f);
+    const float g = rt<T>((o == 0 ? (float)x : (float)y) - 0.5f);
+    const float xy = rt<T>(rt<T>(d + g) * rt<T>(stride));
+    const float wh = rt<T>(rt<T>(d * d) * (o == 2 ? aw : ah));
+    return o < 2 ? xy : o < 4 ? wh : s;
 }
 
 // 2-byte dtypes, 16-byte aligned blocks: within one (image, anchor) block both outputs are ONE contiguous run of ny*nx*no
@@ -103,6 +109,177 @@ __global__ __launch_bounds__(256) void decode_vec_kernel(const T* __restrict__ h
     const long long f = (long long)ba * P * no + f0;
     if (raw) *(vec8*)(raw + f) = rv;
     if (z) *(vec8*)(z + ((long long)b * total_rows + row_offset + (long long)a * P) * no + f0) = zv;
+}
+
+// ---- tiled decode (knob decode_tile): every level of a Detect head in one launch, every global access 16 bytes per lane
+// decode_vec_kernel stores 16 bytes per lane but fetches its 8 head elements by 8 two-byte loads (lanes 16 bytes apart: 8 instructions over the same cache lines), pays
+// libm expf + an IEEE division per element, and a head takes one launch per level (119 / 30 / 9 us at 640 x 640, batch 32: 411 MB at 2.6 TB/s).  Here a work item is a
+// TILE: `tp` consecutive pixels of one image of one level, all channels -- tp * w8 16-byte vectors (w8 = ceil(na * no / 8) per pixel; at most 1024 = one per thread, 16 KiB),
+// loaded as they lie and put into LDS; every (anchor, 8 consecutive output elements) of the tile is then gathered from LDS by one thread, decoded and stored by one 16-byte
+// store per output, exactly as decode_vec_kernel does (tp * no is a multiple of 8, so a tile starts on a 16-byte group of every (image, anchor) block).
+// The sigmoid of a 2-byte T is a function of 16 bits: g_sigmoid_tab holds sigmoid_T<T> of every bit pattern, filled on the device by that very expression, and a block
+// copies the 128 KiB into LDS once (SIG 1: 128 KiB table + two 16 KiB tile buffers = the 160 KiB of a CU, one 1024-thread block per CU).  SIG 0 computes the sigmoid, SIG 2
+// reads the table from global memory (L2); which one a launch takes: decode_tile_sig().  Measured at 640 x 640, batch 32, fp16 (profiles/decode_tile_kernel_stats.md): the
+// three decode_vec launches 149 us per forward, this kernel 132 us with the computed sigmoid, 88 us with the table in LDS (4.6 TB/s), and slower than decode_vec with the
+// table read through L2 (64 different addresses per wave and load).
+// Schedule: blocks walk the items grid-stride.  In iteration i a thread issues the load of tile i + 2 into a register vector, gathers and decodes tile i from LDS, writes
+// the vector of tile i + 1 (issued one iteration earlier) into the other LDS buffer, THEN stores its results, and meets ONE barrier: two tile loads are in flight across
+// the compute phase, and the wait in front of the LDS write covers the stores of the iteration before, not the ones just issued.  What a thread does is the same in every
+// tile (its anchor, its 8 elements, their LDS addresses and channels), so it is worked out once: per tile remain the pixel coordinates, the level's anchors and the addresses --
+// at one 16-byte group per thread and tile, the per-tile instructions (scalar ones above all: 16 waves repeat them) were what bounded the first version of this kernel.
+__device__ unsigned short g_sigmoid_tab[2][65536];   // [0] f16, [1] bf16; built by sigmoid_table_kernel on the first decode of a dtype on a device
+
+template <typename T> struct tab_index;
+template <> struct tab_index<f16_t> { static constexpr int value = 0; };
+template <> struct tab_index<bf16_t> { static constexpr int value = 1; };
+
+template <typename T>
+__global__ __launch_bounds__(256) void sigmoid_table_kernel() {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;   // grid: 256 blocks
+    const T h = __builtin_bit_cast(T, (unsigned short)i);
+    g_sigmoid_tab[tab_index<T>::value][i] = __builtin_bit_cast(unsigned short, sigmoid_T<T>(to_f32<T>(h)));
+}
+
+constexpr int DT_THREADS = 1024, DT_MAX_LEVELS = 5;
+struct DecodeTileLevel {
+    const void* head;
+    void* raw;             // may be null
+    long long row_offset;  // first row of the level in z
+    int ny, nx, pitch;
+    int item0;             // first work item of the level; items [item0, item0 + bs * tiles) = (image, tile)
+    int tiles;             // tiles per image
+    y3_divisor div_tiles, div_nx;
+    float stride;
+    float anchors[10];
+};
+struct DecodeTileJob {
+    DecodeTileLevel lv[DT_MAX_LEVELS];
+    void* z;               // may be null
+    long long total_rows;
+    int n_levels, bs, na, no, tp, w8, items;
+    y3_divisor div_w8, div_no;
+};
+
+template <typename T, int SIG>
+__global__ __launch_bounds__(DT_THREADS) void decode_tile_kernel(const DecodeTileJob job) {
+    typedef T vec8 __attribute__((ext_vector_type(8)));
+    __shared__ __attribute__((aligned(16))) T stage[2][DT_THREADS * 8];
+    __shared__ __attribute__((aligned(16))) unsigned short tab[SIG == 1 ? 65536 : 8];
+    const int tid = threadIdx.x;
+    const int na = job.na, no = job.no, w8 = job.w8, tp = job.tp;
+    const bool want_z = job.z != nullptr;
+    const unsigned short* gtab = g_sigmoid_tab[tab_index<T>::value];
+    if (SIG == 1 && want_z) {
+#pragma unroll
+        for (int i = 0; i < 65536 / 8 / DT_THREADS; ++i) ((uint4*)tab)[i * DT_THREADS + tid] = ((const uint4*)gtab)[i * DT_THREADS + tid];
+    }
+    // ---- what a thread does in every tile (a partial tile at the end of an image keeps the mapping of a full one and switches the threads past its end off)
+    // load side: vector tid of the tile = (pixel row, 16-byte column)
+    const int lv = min(tid, tp * w8 - 1);
+    const int lrow = y3_fdiv(lv, job.div_w8), lcol8 = (lv - lrow * w8) * 8;
+    // compute side: anchor a, elements [f0, f0 + 8) of the tile's run of that anchor; element e is `inc` pixels on (0..2: no >= 4) at channel o0 + e - inc * no
+    const int chunks = tp * no >> 3;
+    int a = 0;
+#pragma unroll
+    for (int k = 1; k < DT_MAX_LEVELS; ++k) a += k < na && tid >= k * chunks;   // (na <= 5)
+    const bool mine = tid < na * chunks;
+    const int f0 = (tid - a * chunks) * 8;
+    const int pl = y3_fdiv(f0, job.div_no), o0 = f0 - pl * no;
+    const int lds0 = mine ? pl * w8 * 8 + a * no + o0 : 0, skip = mine ? w8 * 8 - no : 0;
+    const long long zimg = job.total_rows * no;   // elements of z per image
+
+    struct Item { int l, b, p0, npix; };   // (level, image, first pixel, pixels) of a work item: uniform over the block
+    auto locate = [&](int item) {
+        Item r;
+        item = min(item, job.items - 1);   // (loads past the last item re-read it: no branch around a load, so the waits in front of the LDS writes stay counted)
+        r.l = 0;
+#pragma unroll
+        for (int k = 1; k < DT_MAX_LEVELS; ++k)   // (item0 of the levels not given: INT_MAX)
+            if (item >= job.lv[k].item0) r.l = k;
+        const DecodeTileLevel& L = job.lv[r.l];
+        const int t = item - L.item0;
+        r.b = y3_fdiv(t, L.div_tiles);
+        r.p0 = (t - r.b * L.tiles) * tp;
+        r.npix = min(tp, L.ny * L.nx - r.p0);
+        return r;
+    };
+    auto load = [&](const Item& it) {   // this thread's vector of the tile (threads past a partial tile's end re-read its last row: never used)
+        const DecodeTileLevel& L = job.lv[it.l];
+        const T* hp = (const T*)L.head + ((long long)it.b * (L.ny * L.nx) + it.p0) * L.pitch;
+        return *(const uint4*)(hp + (unsigned)(min(lrow, it.npix - 1) * L.pitch + lcol8));
+    };
+    // gather + decode + store of the tile `it` held by the LDS buffer `cur`; the tile after it (register vector `vnext`) goes into `nxt`
+    auto compute = [&](const Item& it, const T* cur, T* nxt, const uint4& vnext) {
+        const DecodeTileLevel& L = job.lv[it.l];
+        const int Pno = L.ny * L.nx * no;
+        const bool live = mine && f0 < it.npix * no;
+        vec8 rv, zv;
+        int inc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            inc[e] = (o0 + e >= no) + (o0 + e >= 2 * no);
+            rv[e] = cur[lds0 + e + inc[e] * skip];
+        }
+        if (want_z) {
+            // (x, y) of the group's first pixel and of the next two
+            int px[3], py[3];
+            py[0] = y3_fdiv(it.p0 + pl, L.div_nx);
+            px[0] = it.p0 + pl - py[0] * L.nx;
+#pragma unroll
+            for (int k = 1; k < 3; ++k) {
+                const bool wrap = px[k - 1] + 1 == L.nx;
+                px[k] = wrap ? 0 : px[k - 1] + 1;
+                py[k] = py[k - 1] + wrap;
+            }
+            // (through readfirstlane: a select between kernel-argument loads becomes ONE per-lane load of a selected address, whose wait would cover the tile loads in flight)
+            float an[10];
+#pragma unroll
+            for (int k = 0; k < 10; ++k) an[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, L.anchors[k])));
+            const float aw = a == 0 ? an[0] : a == 1 ? an[2] : a == 2 ? an[4] : a == 3 ? an[6] : an[8];
+            const float ah = a == 0 ? an[1] : a == 1 ? an[3] : a == 2 ? an[5] : a == 3 ? an[7] : an[9];
+            T sg[8];   // three straight-line passes: the 8 LDS reads, then the 8 table reads, are in flight together
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned short hb = __builtin_bit_cast(unsigned short, (T)rv[e]);
+                sg[e] = SIG == 0 ? sigmoid_T<T>(to_f32<T>(rv[e])) : __builtin_bit_cast(T, SIG == 1 ? tab[hb] : gtab[hb]);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int k = inc[e], o = o0 + e - k * no;
+                const int x = k == 0 ? px[0] : k == 1 ? px[1] : px[2], y = k == 0 ? py[0] : k == 1 ? py[1] : py[2];
+                zv[e] = from_f32<T>(decode_finish<T>(to_f32<T>(sg[e]), o, x, y, L.stride, aw, ah));
+            }
+        }
+        // the next tile goes into LDS BEFORE the stores are issued: its wait then leaves the newest load in flight and covers, of the stores, only those of the tile before
+        ((uint4*)nxt)[tid] = vnext;
+        asm volatile("" ::: "memory");
+        if (live) {
+            const unsigned off = (unsigned)(a * Pno + f0);   // (na * ny * nx * no < 2^31: decode_tile_plan)
+            if (L.raw) *(vec8*)((T*)L.raw + ((long long)it.b * na * Pno + (long long)it.p0 * no) + off) = rv;
+            if (want_z) *(vec8*)((T*)job.z + (it.b * zimg + (L.row_offset + (long long)it.p0) * no) + off) = zv;
+        }
+    };
+    const int step = gridDim.x;
+    int item = blockIdx.x;
+    Item ic = locate(item), i0, i1 = locate(item + step);
+    uint4 v0 = load(ic), v1 = load(i1);
+    ((uint4*)stage[0])[tid] = v0;
+    __syncthreads();
+    // iteration: issue the load of tile item + 2 * step, work on tile item (in LDS), put tile item + step (loaded one iteration ago) into the other LDS buffer, one barrier
+    while (item < job.items) {
+        i0 = locate(item + 2 * step);
+        v0 = load(i0);
+        compute(ic, stage[0], stage[1], v1);
+        __syncthreads();
+        ic = i1;
+        if ((item += step) >= job.items) break;
+        i1 = locate(item + 2 * step);
+        v1 = load(i1);
+        compute(ic, stage[1], stage[0], v0);
+        __syncthreads();
+        ic = i0;
+        item += step;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ NMS
@@ -908,17 +1085,139 @@ extern "C" int y3_nms(const void* pred, int32_t dtype, int32_t bs, int32_t n_row
     Y3_FAIL("y3_nms: bad dtype %d", dtype);
 }
 
+// ---- host side of the tiled decode
+namespace {
+// which sigmoid a launch of decode_tile_kernel takes (knob decode_tile; `items` tiles, `cus` compute units): the 128 KiB table in LDS costs every block one
+// copy of it, which a block repays only over several tiles
+int decode_tile_sig(long long items, int cus, bool want_z) {
+    const long long k = y3_knob(Y3K_DECODE_TILE);
+    if (!want_z || k == 3) return 0;
+    if (k == 2) return 1;
+    if (k == 4) return 2;
+    return items >= 4ll * cus ? 1 : 0;
+}
+
+// Fills `job` for the levels given, or returns the reason why one of them cannot take decode_tile_kernel (nullptr = eligible).  The arguments were validated by the caller.
+const char* decode_tile_plan(DecodeTileJob& job, const y3_tensor* heads, int n_levels, int dtype, int na, int no, const float* anchors_px, const float* strides,
+                             void* const* raws, void* z, const int64_t* row_offsets, long long total_rows) {
+    if (dtype != Y3_F16 && dtype != Y3_BF16) return "not a 2-byte dtype";
+    if (n_levels < 1 || n_levels > DT_MAX_LEVELS) return "more than 5 levels";
+    if (no < 1) return "no < 1";
+    if (z && ((uintptr_t)z & 15)) return "z is not 16-byte aligned";
+    if (z && (total_rows * no) % 8) return "total_rows * no is no multiple of 8";
+    const int w8 = (na * no + 7) / 8;
+    int m = 8;   // pixels whose elements fill whole 16-byte groups: 8 / gcd(no, 8)
+    while (m > 1 && (no * (m / 2)) % 8 == 0) m /= 2;
+    const int tp = DT_THREADS / w8 / m * m;
+    if (tp < 1) return "na * no too wide for one tile";
+    memset(&job, 0, sizeof(job));
+    job.z = z;
+    job.total_rows = total_rows;
+    job.n_levels = n_levels;
+    job.bs = heads[0].n;
+    job.na = na;
+    job.no = no;
+    job.tp = tp;
+    job.w8 = w8;
+    job.div_w8 = y3_make_divisor(w8);
+    job.div_no = y3_make_divisor(no);
+    long long items = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const y3_tensor& h = heads[l];
+        void* raw = raws ? raws[l] : nullptr;
+        const long long P = (long long)h.h * h.w;
+        if (h.n != job.bs || h.n < 1 || P < 1) return "levels differ in batch size, or an empty level";
+        if (((uintptr_t)h.data & 15) || h.pitch % 8) return "head is not 16-byte aligned";
+        if ((uintptr_t)raw & 15) return "raw is not 16-byte aligned";
+        if ((P * no) % 8 || (z && (row_offsets[l] * no) % 8)) return "ny * nx * no or row_offset * no is no multiple of 8";
+        if (P * no * na >= 0x7fffffffLL || (long long)tp * h.pitch >= 0x7fffffffLL) return "level too large";
+        DecodeTileLevel& L = job.lv[l];
+        L.head = h.data;
+        L.raw = raw;
+        L.row_offset = z ? row_offsets[l] : 0;
+        L.ny = h.h;
+        L.nx = h.w;
+        L.pitch = h.pitch;
+        L.item0 = (int)items;
+        L.tiles = (int)((P + tp - 1) / tp);
+        L.div_tiles = y3_make_divisor(L.tiles);
+        L.div_nx = y3_make_divisor(h.w);
+        L.stride = strides[l];
+        for (int i = 0; i < na * 2; ++i) L.anchors[i] = anchors_px[l * na * 2 + i];
+        items += (long long)job.bs * L.tiles;
+        if (items >= 0x3fffffffLL) return "too many tiles";
+    }
+    for (int l = n_levels; l < DT_MAX_LEVELS; ++l) job.lv[l].item0 = 0x7fffffff;
+    job.items = (int)items;
+    return nullptr;
+}
+
+template <typename T>
+int decode_tile_launch(const DecodeTileJob& job, hipStream_t st) {
+    int dev = 0;
+    Y3_HIP(hipGetDevice(&dev));
+    const int cus = y3_cu_count();
+    const int sig = decode_tile_sig(job.items, cus, job.z != nullptr);
+    if (sig != 0) {
+        // the table of this dtype on this device: built once, on the caller's stream, in front of the first decode that reads it (host flag; a racing or repeated
+        // build writes the same bytes).  A build recorded into a stream capture runs only when that graph does, so it does not count.
+        constexpr int MAXD = 64;
+        static std::atomic<bool> built[MAXD][2];   // (zero-initialised)
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+        const int ti = tab_index<T>::value;
+        if (dev < 0 || dev >= MAXD || !built[dev][ti] || cap != hipStreamCaptureStatusNone) {
+            hipLaunchKernelGGL((sigmoid_table_kernel<T>), dim3(256), dim3(256), 0, st);
+            Y3_CHECK_LAUNCH();
+            if (dev >= 0 && dev < MAXD && cap == hipStreamCaptureStatusNone) built[dev][ti] = true;
+        }
+    }
+    // SIG 1 fills the CU's LDS: one block per CU; the others leave room for two
+    const long long cap_blocks = sig == 1 ? cus : 2ll * cus;
+    const dim3 grid((unsigned)(job.items < cap_blocks ? job.items : cap_blocks));
+    if (sig == 1) hipLaunchKernelGGL((decode_tile_kernel<T, 1>), grid, dim3(DT_THREADS), 0, st, job);
+    else if (sig == 2) hipLaunchKernelGGL((decode_tile_kernel<T, 2>), grid, dim3(DT_THREADS), 0, st, job);
+    else hipLaunchKernelGGL((decode_tile_kernel<T, 0>), grid, dim3(DT_THREADS), 0, st, job);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+int decode_check_level(const char* fn, const y3_tensor* head, int na, int no, const void* z, long long row_offset, long long total_rows) {
+    if (head->c < na * no) Y3_FAIL("%s: head has %d channels, needs %d", fn, head->c, na * no);
+    if (z && (row_offset < 0 || row_offset + (long long)na * head->h * head->w > total_rows))
+        Y3_FAIL("%s: rows [%lld, +%lld) do not fit the %lld rows of z", fn, (long long)row_offset, (long long)na * head->h * head->w, (long long)total_rows);
+    return 0;
+}
+}  // namespace
+
+extern "C" int y3_detect_decode_levels(const y3_tensor* heads, int32_t n_levels, int32_t dtype, int32_t na, int32_t no, const float* anchors_px, const float* strides,
+                                       void* const* raws, void* z, const int64_t* row_offsets, int64_t total_rows, void* stream) {
+    if (!heads || !anchors_px || !strides || (z && !row_offsets)) Y3_FAIL("y3_detect_decode_levels: null argument");
+    if (na < 1 || na > 5) Y3_FAIL("y3_detect_decode_levels: na=%d unsupported (1..5)", na);
+    if (n_levels < 1 || n_levels > DT_MAX_LEVELS) Y3_FAIL("y3_detect_decode_levels: %d levels unsupported (1..%d)", n_levels, DT_MAX_LEVELS);
+    if (y3_knob(Y3K_DECODE_TILE) == 0) Y3_FAIL("y3_detect_decode_levels: the tiled kernel is switched off (knob decode_tile = 0)");
+    for (int l = 0; l < n_levels; ++l)
+        if (decode_check_level("y3_detect_decode_levels", heads + l, na, no, z, z ? row_offsets[l] : 0, total_rows)) return -1;
+    DecodeTileJob job;
+    const char* why = decode_tile_plan(job, heads, n_levels, dtype, na, no, anchors_px, strides, raws, z, row_offsets, total_rows);
+    if (why) Y3_FAIL("y3_detect_decode_levels: a level cannot take the tiled kernel (%s): call y3_detect_decode per level", why);
+    return dtype == Y3_F16 ? decode_tile_launch<f16_t>(job, (hipStream_t)stream) : decode_tile_launch<bf16_t>(job, (hipStream_t)stream);
+}
+
 extern "C" int y3_detect_decode(const y3_tensor* head, int32_t dtype, int32_t na, int32_t no, const float* anchors_px, float stride, void* raw, void* z,
                                 int64_t row_offset, int64_t total_rows, void* stream) {
     if (!head || !anchors_px) Y3_FAIL("y3_detect_decode: null argument");
     if (na < 1 || na > 5) Y3_FAIL("y3_detect_decode: na=%d unsupported (1..5)", na);
-    if (head->c < na * no) Y3_FAIL("y3_detect_decode: head has %d channels, needs %d", head->c, na * no);
-    if (z && (row_offset < 0 || row_offset + (long long)na * head->h * head->w > total_rows))
-        Y3_FAIL("y3_detect_decode: rows [%lld, +%lld) do not fit the %lld rows of z", (long long)row_offset, (long long)na * head->h * head->w, (long long)total_rows);
+    if (decode_check_level("y3_detect_decode", head, na, no, z, row_offset, total_rows)) return -1;
     float a[10] = {0};
     for (int i = 0; i < na * 2; ++i) a[i] = anchors_px[i];
     const long long total = (long long)head->n * head->h * head->w * na * no;
     hipStream_t st = (hipStream_t)stream;
+    if (y3_knob(Y3K_DECODE_TILE) != 0 && total > 0) {
+        DecodeTileJob job;
+        if (!decode_tile_plan(job, head, 1, dtype, na, no, anchors_px, &stride, &raw, z, &row_offset, total_rows))
+            return dtype == Y3_F16 ? decode_tile_launch<f16_t>(job, st) : decode_tile_launch<bf16_t>(job, st);
+    }
     const long long P = (long long)head->h * head->w;
     const bool vec = dtype != Y3_F32 && no >= 8 && (P * no) % 8 == 0 && (total_rows * no) % 8 == 0 && (row_offset * no) % 8 == 0 &&
                      !((uintptr_t)raw & 15) && !((uintptr_t)z & 15) && P * no < 0x7fffffffLL;

@@ -747,13 +747,14 @@ def _decode_outputs(plan: Plan, det, heads, n, export=False, training=False, out
         export, total = True, z.shape[1]
     else:
         z, off = (None if training else torch.empty(n, total, no, dtype=dtype, device=dev)), 0
-    raws = []
-    for lvl, hv in enumerate(heads):
-        raw = None if export else torch.empty(n, na, hv.h, hv.w, no, dtype=dtype, device=dev)
-        apx, stride = consts[lvl]
-        ops.detect_decode(hv.real(), na, no, apx, stride, raw, z, off, total)
-        raws.append(raw)
-        off += rows[lvl]
+    raws = [None if export else torch.empty(n, na, hv.h, hv.w, no, dtype=dtype, device=dev) for hv in heads]
+    offs = [off + sum(rows[:lvl]) for lvl in range(len(heads))]
+    views = [hv.real() for hv in heads]
+    # all levels in one launch where the library's tiled kernel takes every one of them (2-byte dtypes, 16-byte aligned windows); else level by level
+    if dtype == torch.float32 or len(heads) > 5 or not ops.detect_decode_levels(views, na, no, [c[0] for c in consts], [c[1] for c in consts], raws, z, offs, total):
+        for lvl, hv in enumerate(views):
+            apx, stride = consts[lvl]
+            ops.detect_decode(hv, na, no, apx, stride, raws[lvl], z, offs[lvl], total)
     if out is not None:
         return sum(rows)
     if training:

@@ -429,6 +429,19 @@ def detect_decode(head: View, na: int, no: int, anchors_px, stride: float, raw: 
     )
 
 
+def detect_decode_levels(heads, na: int, no: int, anchors_px, strides, raws, z: torch.Tensor | None, row_offsets, total_rows: int) -> bool:
+    """every level of a Detect head in ONE launch (y3_detect_decode_levels: the tiled kernel of the 2-byte dtypes).  heads: Views; anchors_px: per level na * 2 floats;
+    raws: per level a tensor or None (or None for none at all).  False = the library refused (a level is not eligible for that kernel, or knob decode_tile = 0) and
+    launched nothing: call detect_decode per level -- the same values, bit for bit."""
+    nl = len(heads)
+    ts = (_lib.Y3Tensor * nl)(*[h.y3() for h in heads])
+    anc = (C.c_float * (nl * na * 2))(*[float(v) for a in anchors_px for v in a])
+    st = (C.c_float * nl)(*[float(s) for s in strides])
+    rp = (C.c_void_p * nl)(*[r.data_ptr() if r is not None else None for r in (raws if raws is not None else [None] * nl)])
+    ro = (C.c_int64 * nl)(*[int(r) for r in row_offsets])
+    return _lib.lib().y3_detect_decode_levels(ts, nl, dtype_code(heads[0].buf.dtype), na, no, anc, st, rp, z.data_ptr() if z is not None else None, ro, total_rows, stream_ptr()) == 0
+
+
 def detect_raw_bwd(graw: torch.Tensor, na: int, no: int, ghead: View):
     """ghead[b, y, x, a * no + o] = graw[b, a, y, x, o] (contiguous, ghead's dtype); the pad channels of ghead are zeroed"""
     check(_lib.lib().y3_detect_raw_bwd(graw.data_ptr(), dtype_code(graw.dtype), ghead.n, na, ghead.h, ghead.w, no, _ref(ghead), stream_ptr()), "y3_detect_raw_bwd")
