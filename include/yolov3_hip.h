@@ -24,6 +24,12 @@
 extern "C" {
 #endif
 
+/* The Python binding (yolov3_amd/_header.py) is READ from this file: constants, struct layouts, every signature, and -- by the missing trailing `void* stream` -- the
+ * exports that launch nothing.  Declare an export here, define it, write its ops wrapper; keep to the plain C the reader understands (it refuses the rest).
+ * ABI history -- 2: tune / SyncBN / TTA / wgrad_plan added, y3_bn_act_bwd_apply takes sums + 2C; 3: y3_loss_params.sort_obj_iou;
+ * 4: y3_conv_workspace_error / _reset removed (no-ops since the stream-K kernel went), the loss workspace grew by one int per slot;
+ * 5: layer 0 by recomputation (three exports), y3_shard_mean, knob wgrad_patch;
+ * 6: the deferred-epilogue form of conv_v10 and layer-0 recomputation removed. */
 #define Y3_ABI_VERSION 6
 
 typedef enum { Y3_F16 = 0, Y3_BF16 = 1, Y3_F32 = 2, Y3_U8 = 3 } y3_dtype;

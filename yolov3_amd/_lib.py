@@ -7,266 +7,41 @@ import os
 import threading
 from pathlib import Path
 
+from . import _header
+
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["Y3_LIB"]) if os.environ.get("Y3_LIB") else _PKG / "lib" / "libyolov3_hip.so"  # Y3_LIB: instrumented debug builds (tools/timeline.py)
-
-Y3_F16, Y3_BF16, Y3_F32, Y3_U8 = 0, 1, 2, 3
-Y3_ACT_NONE, Y3_ACT_SILU = 0, 1
-ABI_VERSION = 6   # include/yolov3_hip.h::Y3_ABI_VERSION (2: round-3 export set -- tune / SyncBN / TTA / wgrad_plan added, y3_bn_act_bwd_apply takes sums + 2C; 3: y3_loss_params.sort_obj_iou;
-                  # 4: y3_conv_workspace_error / _reset removed (no-ops since the stream-K kernel went), the loss workspace grew by one int per slot;
-                  # 5: layer 0 by recomputation (three exports), y3_shard_mean, knob wgrad_patch;
-                  # 6: the deferred-epilogue form of conv_v10 and layer-0 recomputation removed)
-Y3_ALGO_AUTO, Y3_ALGO_MFMA, Y3_ALGO_DIRECT = 0, 1, 2
-Y3_EXPORT_TARGET, Y3_EXPORT_TXT, Y3_EXPORT_JSON = 0, 1, 2   # y3_export_rows `form`
-
-
-class Y3Tensor(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("pitch", C.c_int32)]
-
-
-class Y3ConvDesc(C.Structure):
-    _fields_ = [
-        ("dtype", C.c_int32),
-        ("ksize", C.c_int32),
-        ("stride", C.c_int32),
-        ("act", C.c_int32),
-        ("upsample2x", C.c_int32),
-        ("algo", C.c_int32),
-        ("cin", C.c_int32),
-        ("cout", C.c_int32),
-        ("in_dilation", C.c_int32),
-        ("filter_elems", C.c_int64),   # elements the packed bank holds (0 = unchecked); ctypes pads to offset 40 like the C compiler
-    ]
-
-
-class Y3PackJob(C.Structure):   # y3_pack_job: one record of the device table of y3_pack_filter_jobs (48 bytes)
-    _fields_ = [("w", C.c_void_p), ("packed_fwd", C.c_void_p), ("packed_dgrad", C.c_void_p), ("cout_src", C.c_int32), ("cin_src", C.c_int32), ("ksize", C.c_int32),
-                ("cout", C.c_int32), ("cin", C.c_int32), ("first_block", C.c_int32)]
-
-
-class Y3FoldPackJob(C.Structure):   # y3_fold_pack_job: one record of the device table of y3_fold_pack_jobs (96 bytes)
-    _fields_ = [("w", C.c_void_p), ("conv_bias", C.c_void_p), ("bn_gamma", C.c_void_p), ("bn_beta", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
-                ("packed", C.c_void_p), ("bias", C.c_void_p), ("bn_eps", C.c_float), ("cout_src", C.c_int32), ("cin_src", C.c_int32), ("ksize", C.c_int32),
-                ("cout", C.c_int32), ("cin", C.c_int32), ("stem", C.c_int32), ("first_block", C.c_int32)]
-
-
-class Y3NmsParams(C.Structure):
-    _fields_ = [
-        ("iou_thres", C.c_double),
-        ("conf_thres", C.c_float),
-        ("multi_label", C.c_int32),
-        ("agnostic", C.c_int32),
-        ("max_det", C.c_int32),
-        ("max_nms", C.c_int32),
-        ("max_wh", C.c_float),
-        ("n_classes_filter", C.c_int32),
-    ]
-
-
-class Y3LossParams(C.Structure):
-    _fields_ = [
-        ("nl", C.c_int32),
-        ("na", C.c_int32),
-        ("nc", C.c_int32),
-        ("bs", C.c_int32),
-        ("ny", C.c_int32 * 5),
-        ("nx", C.c_int32 * 5),
-        ("anchors", C.c_float * 50),
-        ("balance", C.c_float * 5),
-        ("anchor_t", C.c_float),
-        ("box_gain", C.c_float),
-        ("obj_gain", C.c_float),
-        ("cls_gain", C.c_float),
-        ("cls_pw", C.c_float),
-        ("obj_pw", C.c_float),
-        ("cp", C.c_float),
-        ("cn", C.c_float),
-        ("fl_gamma", C.c_float),
-        ("sort_obj_iou", C.c_int32),
-    ]
-
-
-_P = C.POINTER
-# symbol -> (restype, argtypes).  Every symbol include/yolov3_hip.h declares is listed here and is REQUIRED.
-_SIGNATURES = {
-    "y3_abi_version": (C.c_int, []),
-    "y3_last_error": (C.c_char_p, []),
-    "y3_tune_set": (C.c_int, [C.c_char_p, C.c_int64]),
-    "y3_tune_get": (C.c_int64, [C.c_char_p]),
-    "y3_tune_reset": (None, []),
-    "y3_packed_filter_elems": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    "y3_pack_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_conv2d_fwd": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), _P(Y3Tensor), C.c_void_p]),
-    "y3_conv_workspace_bytes": (C.c_size_t, []),
-    "y3_conv2d_fwd_bnin_rows": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
-    "y3_conv2d_fwd_bnin_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                          C.c_void_p, C.c_void_p]),
-    "y3_conv2d_fwd_ws": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_conv_last_variant": (C.c_int, [C.c_char_p, C.c_size_t]),
-    "y3_conv2d_fwd_variant": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_size_t, C.c_char_p, C.c_size_t]),
-    "y3_conv_v10_tiles": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), _P(Y3Tensor), C.c_size_t, _P(C.c_int32), C.c_int64, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
-    "y3_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P(Y3Tensor), C.c_void_p]),
-    "y3_nhwc_to_nchw": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_maxpool2d": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_spp_pyramid": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p]),
-    "y3_upsample2x": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p]),
-    "y3_copy_slice": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p]),
-    "y3_detect_decode": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, _P(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
-    "y3_detect_decode_levels": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float), _P(C.c_void_p), C.c_void_p, _P(C.c_int64),
-                                          C.c_int64, C.c_void_p]),
-    "y3_nms_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, _P(Y3NmsParams), C.c_int64]),
-    "y3_nms": (
-        C.c_int,
-        [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(Y3NmsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p],
-    ),
-    "y3_bneck_pair_fwd": (C.c_int, [_P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(Y3Tensor), C.c_void_p]),
-    "y3_stem_pair_fwd": (
-        C.c_int,
-        [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(Y3Tensor),
-         C.c_void_p],
-    ),
-    "y3_letterbox_u8": (
-        C.c_int,
-        [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
-    ),
-    "y3_scale_boxes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_match_detections": (
-        C.c_int,
-        [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
-    ),
-    "y3_val_stats_append": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
-    ),
-    "y3_val_stats_count_labels": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
-    "y3_val_stats_out_elems": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "y3_val_stats_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "y3_val_stats_compute": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-         C.c_void_p],
-    ),
-    "y3_confusion_matrix": (
-        C.c_int,
-        [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p],
-    ),
-    "y3_labels_to_native": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_label_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_export_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
-    "y3_anchor_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "y3_anchor_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_anchor_evolve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_kmeans_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_label_histogram": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
-    "y3_image_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_weighted_choices_workspace_bytes": (C.c_size_t, [C.c_int64]),
-    "y3_weighted_choices": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_coco_eval_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
-    "y3_coco_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_coco_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_dataset_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_dataset_targets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                     C.c_void_p]),
-    "y3_augment_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_augment_targets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "y3_loss_workspace_bytes": (C.c_size_t, [_P(Y3LossParams), C.c_int32]),
-    "y3_loss_fwd": (C.c_int, [_P(Y3LossParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_loss_bwd": (C.c_int, [_P(Y3LossParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_bn_stats": (C.c_int, [_P(Y3Tensor), C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_bn_finalize": (
-        C.c_int,
-        [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    ),
-    "y3_scale_img": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
-    "y3_descale_pred": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
-                                  C.c_void_p]),
-    "y3_resize_bilinear": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "y3_quad_collate_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_loss_level_obj": (C.c_int, [_P(Y3LossParams), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "y3_conv2d_fwd_stats_rows": (C.c_int64, [_P(Y3ConvDesc), _P(Y3Tensor), _P(Y3Tensor)]),
-    "y3_conv2d_fwd_stats": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "y3_conv2d_fwd_stats_rows_ws": (C.c_int64, [_P(Y3ConvDesc), _P(Y3Tensor), _P(Y3Tensor), C.c_size_t]),
-    "y3_conv2d_fwd_stats_ws": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_bn_finalize_rows": (
-        C.c_int,
-        [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-         C.c_void_p],
-    ),
-    "y3_bn_stats_finalize": (
-        C.c_int,
-        [_P(Y3Tensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    ),
-    "y3_bn_act_fwd": (C.c_int, [_P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_bn_sum_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_bn_finalize_devcount": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    ),
-    "y3_bn_act_bwd_reduce": (
-        C.c_int,
-        [_P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    ),
-    "y3_bn_act_bwd_apply": (
-        C.c_int,
-        [_P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_void_p],
-    ),
-    "y3_bn_act_bwd": (
-        C.c_int,
-        [_P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p],
-    ),
-    "y3_bn_act_bwd_res": (
-        C.c_int,
-        [_P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _P(Y3Tensor), C.c_void_p, C.c_void_p, _P(Y3Tensor), C.c_int32,
-         C.c_void_p],
-    ),
-    "y3_pack_filter_dgrad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_pack_filter_pair": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_pack_job_blocks": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "y3_pack_filter_jobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
-    "y3_fold_pack_jobs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
-    "y3_packed_filter_dgrad_s2_elems": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "y3_pack_filter_dgrad_s2": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_conv2d_dgrad_s2": (C.c_int, [C.c_int32, _P(Y3Tensor), C.c_void_p, _P(Y3Tensor), _P(Y3Tensor), C.c_void_p]),
-    "y3_conv2d_wgrad_workspace_bytes": (C.c_size_t, [_P(Y3ConvDesc), _P(Y3Tensor)]),
-    "y3_conv2d_wgrad_plan": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_conv2d_wgrad": (C.c_int, [_P(Y3ConvDesc), _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_conv2d_wgrad_last_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_upsample2x_bwd": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_maxpool2d_bwd": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "y3_maxpool2d_bwd_workspace_bytes": (C.c_size_t, [_P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "y3_maxpool2d_bwd_ws": (C.c_int, [_P(Y3Tensor), _P(Y3Tensor), _P(Y3Tensor), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
-                                      C.c_void_p]),
-    "y3_detect_raw_bwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(Y3Tensor), C.c_void_p]),
-    "y3_packed_filter_stem_elems": (C.c_size_t, [C.c_int32]),
-    "y3_pack_filter_stem": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "y3_stem_conv_fwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(Y3Tensor), C.c_void_p]),
-    "y3_stem_bn_bwd_wgrad_workspace_bytes": (C.c_size_t, []),
-    "y3_stem_bn_bwd_wgrad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P(Y3Tensor), _P(Y3Tensor), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "y3_stem_conv_stats_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
-    "y3_stem_conv_fwd_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(Y3Tensor),
-                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "y3_sgd_tensor_record_bytes": (C.c_size_t, []),
-    "y3_sgd_step_dynamic": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_loss_scale_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p]),
-    "y3_shard_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
-    "y3_optim_tensor_record_bytes": (C.c_size_t, []),
-    "y3_adam_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_rmsprop_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_ema_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
-    "y3_ema_update_counted": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "y3_sgd_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-}
-
-_lib = None
+HEADER_PATH = _PKG.parent / "include" / "yolov3_hip.h"
 
 
 class Y3Error(RuntimeError):
     pass
+
+
+# Constants, structs, signatures and queries are all read, once per process, from the one file the C side is compiled against.
+if not HEADER_PATH.exists():
+    raise Y3Error(f"{HEADER_PATH} is missing: the bindings are read from the header the library is compiled against")
+_H = _header.parse(HEADER_PATH.read_text())
+_K = _H.constants
+ABI_VERSION = _K["Y3_ABI_VERSION"]
+Y3_F16, Y3_BF16, Y3_F32, Y3_U8 = _K["Y3_F16"], _K["Y3_BF16"], _K["Y3_F32"], _K["Y3_U8"]
+Y3_ACT_NONE, Y3_ACT_SILU = _K["Y3_ACT_NONE"], _K["Y3_ACT_SILU"]
+Y3_ALGO_AUTO, Y3_ALGO_MFMA, Y3_ALGO_DIRECT = _K["Y3_ALGO_AUTO"], _K["Y3_ALGO_MFMA"], _K["Y3_ALGO_DIRECT"]
+Y3_EXPORT_TARGET, Y3_EXPORT_TXT, Y3_EXPORT_JSON = _K["Y3_EXPORT_TARGET"], _K["Y3_EXPORT_TXT"], _K["Y3_EXPORT_JSON"]   # y3_export_rows `form`
+Y3Tensor = _H.structs["y3_tensor"]
+Y3ConvDesc = _H.structs["y3_conv_desc"]
+Y3NmsParams = _H.structs["y3_nms_params"]
+Y3LossParams = _H.structs["y3_loss_params"]
+Y3PackJob = _H.structs["y3_pack_job"]             # one record of the device table of y3_pack_filter_jobs
+Y3FoldPackJob = _H.structs["y3_fold_pack_job"]    # one record of the device table of y3_fold_pack_jobs
+Y3DatasetImage = _H.structs["y3_dataset_image"]   # the device records of dataset.py / augment.py, filled through np.dtype(...)
+Y3AugmentTile = _H.structs["y3_augment_tile"]
+Y3AugmentMosaic = _H.structs["y3_augment_mosaic"]
+Y3AugmentItem = _H.structs["y3_augment_item"]
+_SIGNATURES = _H.signatures   # symbol -> (restype, argtypes): every export the header declares, all REQUIRED
+_QUERIES = _H.queries         # exports without a trailing `void* stream` launch nothing (sizes, plans, names, knobs): CallTimer does not time them
+
+_lib = None
 
 
 def exported_symbols():
@@ -301,13 +76,6 @@ def lib() -> C.CDLL:
 
 
 _call_timer = None
-# exports that launch nothing (sizes, plans, names, knobs): not timed
-_QUERIES = frozenset((
-    "y3_abi_version", "y3_last_error", "y3_tune_set", "y3_tune_get", "y3_tune_reset", "y3_packed_filter_elems", "y3_conv_workspace_bytes", "y3_conv_last_variant",
-    "y3_conv2d_fwd_variant", "y3_nms_workspace_bytes", "y3_loss_workspace_bytes", "y3_conv2d_fwd_stats_rows", "y3_conv2d_fwd_stats_rows_ws", "y3_conv2d_fwd_bnin_rows", "y3_pack_job_blocks",
-    "y3_packed_filter_dgrad_s2_elems", "y3_conv2d_wgrad_workspace_bytes", "y3_conv2d_wgrad_plan", "y3_conv2d_wgrad_last_plan", "y3_packed_filter_stem_elems", "y3_stem_bn_bwd_wgrad_workspace_bytes",
-    "y3_stem_conv_stats_rows", "y3_conv_v10_tiles", "y3_sgd_tensor_record_bytes", "y3_optim_tensor_record_bytes", "y3_maxpool2d_bwd_workspace_bytes", "y3_val_stats_out_elems",
-    "y3_val_stats_workspace_bytes", "y3_anchor_workspace_bytes", "y3_weighted_choices_workspace_bytes", "y3_coco_eval_workspace_bytes"))
 
 
 class CallTimer:

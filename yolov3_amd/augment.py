@@ -34,10 +34,8 @@ from .dataset import DeviceDataset
 
 HYP_KEYS = ("mosaic", "mixup", "degrees", "translate", "scale", "shear", "perspective", "hsv_h", "hsv_s", "hsv_v", "flipud", "fliplr", "copy_paste")
 
-# y3_augment_tile / y3_augment_mosaic / y3_augment_item of include/yolov3_hip.h
-TILE = np.dtype([("img", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("padw", "<i4"), ("padh", "<i4"), ("lpadw", "<f4"), ("lpadh", "<f4"), ("reserved", "<i4")])
-MOSAIC = np.dtype([("inv", "<f8", (6,)), ("m", "<f8", (6,)), ("scale", "<f8"), ("ntiles", "<i4"), ("canvas", "<i4"), ("clip", "<i4"), ("reserved", "<i4"), ("tiles", TILE, (4,))])
-ITEM = np.dtype([("mosaics", MOSAIC, (2,)), ("ratio", "<f8"), ("ratio1", "<f8"), ("nmos", "<i4"), ("flipud", "<i4"), ("fliplr", "<i4"), ("hsv", "<i4"), ("lut", "u1", (3, 256))])
+# y3_augment_tile / y3_augment_mosaic / y3_augment_item as include/yolov3_hip.h declares them
+TILE, MOSAIC, ITEM = np.dtype(ops.Y3AugmentTile), np.dtype(ops.Y3AugmentMosaic), np.dtype(ops.Y3AugmentItem)
 assert (TILE.itemsize, MOSAIC.itemsize, ITEM.itemsize) == (40, 280, 1360)
 
 

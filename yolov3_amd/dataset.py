@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 
-_RECORD = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("bh", "<i4"), ("bw", "<i4")])   # y3_dataset_image
+_RECORD = np.dtype(ops.Y3DatasetImage)   # y3_dataset_image as include/yolov3_hip.h declares it
 _ALIGN = 16
 _CHUNK = 64 << 20   # bytes of the pinned staging buffer
 _DTYPES = (torch.uint8, torch.float16, torch.bfloat16, torch.float32)

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import Y3ConvDesc, Y3NmsParams, Y3Tensor, check
+from ._lib import Y3AugmentItem, Y3AugmentMosaic, Y3AugmentTile, Y3ConvDesc, Y3DatasetImage, Y3NmsParams, Y3Tensor, check   # (the record structs: for dataset.py / augment.py)
 
 DTYPE_CODE = {torch.float16: _lib.Y3_F16, torch.bfloat16: _lib.Y3_BF16, torch.float32: _lib.Y3_F32, torch.uint8: _lib.Y3_U8}
 
