@@ -422,7 +422,20 @@ int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const 
  *   clip to [0, canvas] when clip != 0, the four corners through m in fp64, min / max, the clip to [0, S], box_candidates against the unwarped box times `scale`
  *   (wh_thr 2, ar_thr 100, area_thr 0.1, eps 1e-16), xyxy2xywhn(clip=True, eps=1e-3) and the flips.  Survivors are compacted in that order into targets, DEVICE
  *   fp32 (n_rows, 6) [item in batch, cls, x, y, w, h]; offsets, DEVICE int64 (count + 1), holds where every item's rows begin and, last, the survivor count.
- *   n_rows is the caller's upper bound (the label count of all tiles); rows past the survivor count are not written. */
+ *   n_rows is the caller's upper bound (the label count of all tiles); rows past the survivor count are not written.
+ * augment_polygons (a set with polygon labels; one launch ahead of the targets): vertices DEVICE fp32 (n_vertices, 2) normalised, vertex_offsets DEVICE int64
+ *   (n_label_rows + 1): row r of the label table owns the vertices [vertex_offsets[r], vertex_offsets[r + 1]), an empty range meaning a row without a polygon; a range
+ *   is clamped to [0, n_vertices].  Every label row of the tiles of every mosaic with clip != 0, at its position j in the order of augment_targets (item, mosaic, tile,
+ *   row): per vertex x = w vx + lpadw, y = h vy + lpadh and the clip to [0, canvas] in fp32 (xyn2xy, np.clip); the polygon closed with vertex 0 and resampled to 1000
+ *   points in fp64 as np.linspace(0, k, 1000) and np.interp give them (t_i = i (k / 999), t_999 = k; at t with q = floor(t): a = v_q where t == q, else
+ *   (v_{q+1} - v_q) (t - q) + v_q); X = x m00 + y m01 + m02 and Y likewise, plain left-to-right fp64 sums; segment2box: over the points with 0 <= X <= S and
+ *   0 <= Y <= S, boxes[j] = (min X, min Y, max X, max Y) and inside[j] = 1, or zeros and 0 when no point is kept or every kept X is zero.  paths, DEVICE int32
+ *   (count, 2) per item and mosaic: bit 0 when some clipped coordinate of the mosaic's polygons is not zero, bit 1 when some label row of it has no polygon; 0 for a
+ *   mosaic with clip == 0 or beyond nmos.  boxes DEVICE fp64 (n_rows, 4) and inside DEVICE int32 (n_rows), n_rows as for augment_targets; positions past n_rows are
+ *   not written.  No read leaves the tables whatever the items and the offsets hold.
+ * augment_targets_polygons: augment_targets, except that every row of a mosaic whose paths word is 1 (every row has a polygon, something is not zero) takes boxes[j]
+ *   unclipped in place of the four warped corners and area_thr 0.01 in place of 0.1 (a row with inside[j] == 0 has a zero box and is dropped); every other mosaic runs
+ *   the arithmetic of augment_targets. */
 typedef struct {
     int32_t img;            /* index into the record table */
     int32_t x1, y1, x2, y2; /* the rectangle on the canvas */
@@ -446,6 +459,12 @@ int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset
                      int32_t dst_dtype, int32_t S, void* stream);
 int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
                        int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
+int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                        const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
+                        int32_t* paths, int64_t n_rows, void* stream);
+int y3_augment_targets_polygons(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                int32_t count, int32_t S, const double* boxes, const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows,
+                                int64_t* offsets, void* stream);
 
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.

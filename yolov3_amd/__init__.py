@@ -21,7 +21,7 @@ Public surface mirrors the reference's own Python signatures:
                                          memory -- rect batch shapes on the host once, every letterboxed CHW RGB batch and its targets in one launch each, no host loader)
     DeviceTrainDataset / draw_item       (reference utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283: the augment=True loader -- mosaic, affine
                                          warp, HSV, flips and mixup sampled straight from the cached images in one launch per batch, the labels in another; the host keeps
-                                         the reference's random stream)
+                                         the reference's random stream; polygon labels (segments=) warp as 1000 resampled points per polygon in one more launch)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)

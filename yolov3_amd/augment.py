@@ -12,13 +12,23 @@ item (y3_augment_item); a batch is one pinned host -> device copy of bs records.
 every output pixel straight from the image arena (the 2s x 2s canvas is never materialised) and y3_augment_targets transforms, filters and compacts the labels.  The
 survivor count is known only on the device: the host reads the bs + 1 offsets once per batch.
 
-What rests on what: the draws, the geometry, M, the tables, the whole label path, the blend, the flips and the layout are pinned by the unmodified reference
-(tests/golden/make_augment_golden.py).  The pixel sampler of cv2.warpAffine and the two cv2.cvtColor conversions follow the integer / fp32 statements of
-tests/augment_cases.py, which restate the published 8-bit algorithms and have not been compared with a cv2 build.
+Polygon labels (segments=..., what the reference's parser makes of label rows with more than six numbers): segments[i] is empty or holds one (k, 2) float32 array of
+normalised vertices per label row of image i.  The vertices go up once with the labels, as one fp32 (V, 2) table and one int64 offset per label row plus one
+(pack_polygons); per batch one more launch, y3_augment_polygons ahead of the targets, carries every polygon of every mosaic through xyn2xy, the clip, the 1000 samples
+of resample_segments, M and segment2box in fp64, and y3_augment_targets_polygons takes those boxes with area_thr 0.01 for a mosaic in which every label row has a
+polygon and some clipped coordinate is not zero (random_perspective's use_segments) -- every other mosaic, and every letterbox item, runs the four-corner box path
+with 0.10.  Polygons draw no random numbers and touch no pixel.  A set without polygons makes the two launches it always made.
 
-Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0, polygon labels (a non-empty segments[i]), rect=True, an image whose
-long side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; KeyError for a missing hyp key.  Albumentations is a
-no-op, as in the reference when the package is absent.  Out of scope: warpPerspective, copy-paste, polygon labels, load_mosaic9, cutout, prefetching.
+What rests on what: the draws, the geometry, M, the tables, the whole label path, the blend, the flips and the layout are pinned by the unmodified reference
+(tests/golden/make_augment_golden.py; the polygon label path by tests/golden/make_augment_polygons_golden.py over label files with polygon rows, through the NumPy
+statement of tests/augment_polygon_cases.py, which the generator asserts equal to the reference item by item).  The pixel sampler of cv2.warpAffine and the two
+cv2.cvtColor conversions follow the integer / fp32 statements of tests/augment_cases.py, which restate the published 8-bit algorithms and have not been compared with
+a cv2 build.
+
+Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0, polygon labels whose count is neither 0 nor the image's label rows
+(the reference would send such a mosaic down the box path; here it is an error: a stated difference) or that hold an empty polygon, rect=True, an image whose long
+side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; KeyError for a missing hyp key.  Albumentations is a no-op, as
+in the reference when the package is absent.  Out of scope: warpPerspective, copy-paste, load_mosaic9, cutout, prefetching, returning the warped polygons.
 """
 from __future__ import annotations
 
@@ -30,6 +40,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import dataset as _dataset
 from .dataset import DeviceDataset
 
 HYP_KEYS = ("mosaic", "mixup", "degrees", "translate", "scale", "shear", "perspective", "hsv_h", "hsv_s", "hsv_v", "flipud", "fliplr", "copy_paste")
@@ -181,10 +192,41 @@ def pack_items(items, out=None) -> np.ndarray:
     return rec
 
 
+def pack_polygons(labels, segments, paths=None):
+    """The polygons of a set as the device reads them -> (vertices (V, 2) float32, offsets (rows + 1,) int64): the vertices of every polygon back to back in the order of
+    the label table, row r of the table owning vertices[offsets[r] : offsets[r + 1]]; the rows of an image without polygons own nothing.  segments[i] is empty or holds
+    one (k, 2) array, k >= 1, per label row of image i (what the reference's parser and its filters keep): ValueError for any other count and for an empty polygon
+    (np.interp raises on one)."""
+    if len(segments) != len(labels):
+        raise ValueError(f"DeviceTrainDataset: polygon labels for {len(segments)} images, but {len(labels)} label arrays")
+    verts, counts = [], []
+    for i, (lb, sg) in enumerate(zip(labels, segments)):
+        name = paths[i] if paths is not None else i
+        if len(sg) == 0:
+            counts.extend([0] * len(lb))
+            continue
+        if len(sg) != len(lb):
+            raise ValueError(f"DeviceTrainDataset: image {name} holds {len(sg)} polygon labels for {len(lb)} label rows; segments[i] is empty or has one polygon per row")
+        for p in sg:
+            p = np.asarray(p)
+            if p.ndim != 2 or p.shape[1] != 2 or len(p) < 1:
+                raise ValueError(f"DeviceTrainDataset: image {name}: a polygon of its polygon labels has shape {p.shape}, not (k, 2) with k >= 1")
+            verts.append(p.astype(np.float32))
+            counts.append(len(p))
+    offsets = np.zeros(len(counts) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    vertices = np.concatenate(verts, 0) if verts else np.zeros((0, 2), dtype=np.float32)
+    if (np.diff(offsets) < 0).any() or offsets[0] != 0 or offsets[-1] != len(vertices) or len(vertices) > 0x3FFFFFFF:
+        raise ValueError(f"DeviceTrainDataset: the polygon labels do not pack ({len(vertices)} vertices, offsets ending at {offsets[-1]})")
+    return np.ascontiguousarray(vertices), offsets
+
+
 class DeviceTrainDataset(DeviceDataset):
     """The cached images and labels of an augment=True, rect=False dataset in device memory (the arena, the record table, the label table and the chunked upload of
     DeviceDataset); iterating yields the reference loader's 4-tuples with mosaic, random_perspective (affine), augment_hsv, the flips and mixup applied on the
-    device.  shapes[i] is None for a mosaic item, the letterbox tuple otherwise.  hyp: the reference's hyperparameter dict (HYP_KEYS are read)."""
+    device.  shapes[i] is None for a mosaic item, the letterbox tuple otherwise.  hyp: the reference's hyperparameter dict (HYP_KEYS are read).  segments: the
+    reference's dataset.segments (per image an empty list, or one (k, 2) float32 polygon per label row); after a batch of a set with polygons `.polygons` holds the
+    (boxes, inside, path words) ops.augment_polygons wrote for it."""
 
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, mosaic=True, device="cuda", dtype=torch.uint8,
                  rect=False, segments=None):
@@ -194,8 +236,9 @@ class DeviceTrainDataset(DeviceDataset):
             raise ValueError(f"DeviceTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
         if hyp["copy_paste"] != 0:
             raise ValueError(f"DeviceTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        polygons = None
         if segments is not None and any(len(sg) for sg in segments):
-            raise ValueError("DeviceTrainDataset: the dataset holds polygon labels (a non-empty segments[i]); they warp differently and are not built")
+            polygons = pack_polygons(labels, segments, paths)   # (host only: the vertex table goes up after the images)
         if rect:
             raise ValueError("DeviceTrainDataset: rect=True; the reference sets mosaic = augment and not rect, use DeviceDataset for rectangular batches")
         if int(img_size) != img_size or int(img_size) < 16 or int(img_size) % 16:
@@ -211,6 +254,9 @@ class DeviceTrainDataset(DeviceDataset):
         self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
         self._stage_rec = self._stage.numpy().view(ITEM)
         self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
+        self._vertices = self._vertex_offsets = self.polygons = None   # a box-only set: the two launches per batch and nothing else
+        if polygons is not None:
+            self._vertices, self._vertex_offsets = _dataset._upload(polygons[0], self.device), _dataset._upload(polygons[1], self.device)
 
     @classmethod
     def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False):
@@ -243,6 +289,10 @@ class DeviceTrainDataset(DeviceDataset):
         self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
         upper = int(sum(self._counts[j] for it in items for mo in it.mosaics for j in mo.indices))
         im = ops.augment_batch(self._arena, self._records, self.n, self._items_dev, count, self.img_size, self.dtype, out)
-        targets, offsets = ops.augment_targets(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
+        if self._vertices is None:
+            targets, offsets = ops.augment_targets(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
+        else:   # polygon labels: the boxes of the warped polygons first, then the targets that choose per mosaic between them and the four corners
+            self.polygons = ops.augment_polygons(self._vertices, self._vertex_offsets, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
+            targets, offsets = ops.augment_targets_polygons(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper, *self.polygons)
         nl = int(offsets.cpu()[count])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
         return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)

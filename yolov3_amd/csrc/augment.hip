@@ -3,7 +3,9 @@
 //   * load_mosaic's paste of four images into a 2s x 2s canvas of 114 (or letterbox's border around one), random_perspective's cv2.warpAffine, mixup's blend, augment_hsv,
 //     np.flipud / np.fliplr, transpose((2, 0, 1))[::-1] and torch.stack                      -> augment_batch_kernel, ONE launch per batch; the canvas is never materialised;
 //   * xywhn2xyxy per tile, the clip to the canvas, the four-corner transform, box_candidates, xyxy2xywhn(clip=True, eps=1e-3), the flips of the labels, mixup's
-//     concatenation and collate_fn                                                            -> augment_targets_kernel, ONE launch per batch.
+//     concatenation and collate_fn                                                            -> augment_targets_kernel, ONE launch per batch;
+//   * for a set with polygon labels, xyn2xy per tile, the clip, resample_segments, the transform of the 1000 points and segment2box per label row
+//                                                                                             -> augment_polygons_kernel, ONE more launch ahead of the targets.
 // The host draws the random numbers and sends one y3_augment_item per item (yolov3_amd/augment.py); the images lie in the arena of csrc/dataset.hip with its record table.
 // Every arena read is bounded by the arena whatever the records hold: a tile is cut down, when the block starts, to the part of its rectangle whose source pixels lie
 // inside its image, and an image that does not lie inside the arena gives no tile at all (its pixels read as 114).
@@ -241,10 +243,155 @@ Y3_DEV void tile_rows(const TargetArgs& a, long long total, int slot, long long&
     if (end - beg > (1 << 20)) end = beg + (1 << 20);
 }
 
+// Polygon labels (random_perspective's use_segments branch, utils/augmentations.py:183-194 with resample_segments and segment2box of utils/general.py): the vertex table
+// of the set and what augment_polygons_kernel leaves per label position j of the batch for the polygon form of augment_targets_kernel.
+struct PolyTables {
+    const float* verts;              // (n_verts, 2) normalised
+    const long long* vert_offsets;   // n_vert_rows + 1: row r of the label table owns vertices [vert_offsets[r], vert_offsets[r + 1])
+    long long n_verts, n_vert_rows;
+    double* boxes;                   // (ws_rows, 4) segment2box of the warped polygon, zeros when it has no point inside
+    int* inside;                     // (ws_rows): 1 when that box was taken from points
+    int* paths;                      // (count, 2) per item and mosaic: PATH_NONZERO | PATH_LACKS; the polygon path is taken when the word is PATH_NONZERO alone
+    long long ws_rows;
+};
+
+constexpr int SAMPLES = 1000;        // resample_segments' n
+constexpr int PATH_NONZERO = 1;      // some clipped coordinate of some polygon of the mosaic is not zero: any(x.any() for x in segments)
+constexpr int PATH_LACKS = 2;        // some label row of the mosaic has no polygon: len(segments) != n
+
+// vertex `idx` of the table on the canvas: xyn2xy(w, h, padw, padh) and np.clip(0, 2 s), both fp32
+Y3_DEV void canvas_vertex(const float* verts, long long idx, float wf, float hf, float padw, float padh, float c, float& x, float& y) {
+    x = wf * verts[2 * idx] + padw;
+    y = hf * verts[2 * idx + 1] + padh;
+    x = x < 0.0f ? 0.0f : x; x = x > c ? c : x;
+    y = y < 0.0f ? 0.0f : y; y = y > c ? c : y;
+}
+
+// One block per (item, mosaic), one wave per label row at a time: the rows of the mosaic's tiles in tile order, at the positions j augment_targets_kernel gives them (the
+// label counts of every slot before the mosaic are summed by the block).  A lane takes samples lane, lane + 64, ... of the 1000 of np.linspace(0, k, 1000) over the
+// closed polygon (vertex k is vertex 0), interpolates as np.interp does in fp64 -- (b - a) (x - j) + a, a itself where x == j -- forms X = x m00 + y m01 + m02 and Y
+// likewise as plain sums, keeps the points with 0 <= X, Y <= S, and the wave reduces min / max.  Vertices are read by index from the table, never staged: a polygon may
+// have more vertices than samples.  Mosaics of the letterbox branch (clip == 0) hand no segments to random_perspective: their word is 0 and their rows are not touched.
+__global__ __launch_bounds__(BT) void augment_polygons_kernel(const TargetArgs a, const PolyTables p) {
+    __shared__ long long s_sum[BT / 64];
+    __shared__ int s_flag[BT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, mslot = blockIdx.x, b = mslot >> 1, m = mslot & 1;
+    const long long total = a.label_offsets[a.n_images];
+    long long before = 0;
+    for (int s = tid; s < mslot * 4; s += BT) {
+        long long beg, end;
+        tile_rows(a, total, s, beg, end);
+        before += end - beg;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) before += __shfl_xor(before, d);
+    if (lane == 0) s_sum[wave] = before;
+    __syncthreads();
+    long long base = 0;
+#pragma unroll
+    for (int w = 0; w < BT / 64; ++w) base += s_sum[w];
+    base = base > 0x3fffffff ? 0x3fffffff : base;   // (the saturating prefix of augment_targets_kernel)
+    const y3_augment_item* it = a.items + b;
+    const y3_augment_mosaic* mo = &it->mosaics[m];
+    if (m >= clampi(it->nmos, 0, 2) || !mo->clip) {
+        if (tid == 0) p.paths[mslot] = 0;
+        return;
+    }
+    const int ntiles = clampi(mo->ntiles, 0, 4);
+    const float c = (float)mo->canvas;
+    const double Sd = (double)a.S;
+    const double m00 = mo->m[0], m01 = mo->m[1], m02 = mo->m[2], m10 = mo->m[3], m11 = mo->m[4], m12 = mo->m[5];
+    int flags = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        long long beg, end;
+        tile_rows(a, total, mslot * 4 + t, beg, end);
+        if (end > beg) {
+            const y3_augment_tile tl = mo->tiles[t];
+            const y3_dataset_image im = a.images[tl.img];   // (tile_rows found the image inside the table)
+            const float wf = (float)im.w, hf = (float)im.h;
+            for (long long r = wave; r < end - beg; r += BT / 64) {
+                const long long row = beg + r, j = base + r;
+                long long vb = 0, ve = 0;
+                if (row < p.n_vert_rows) {   // an offset table that does not describe `verts` reads nothing outside it
+                    vb = p.vert_offsets[row];
+                    ve = p.vert_offsets[row + 1];
+                    vb = vb < 0 ? 0 : (vb > p.n_verts ? p.n_verts : vb);
+                    ve = ve < vb ? vb : (ve > p.n_verts ? p.n_verts : ve);
+                }
+                const int k = (int)(ve - vb);   // n_verts < 2^31
+                bool nonzero = false, anyx = false;
+                double x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+                bool have = false;
+                if (k == 0) {
+                    flags |= PATH_LACKS;
+                } else {
+                    for (int v = lane; v < k; v += 64) {
+                        float x, y;
+                        canvas_vertex(p.verts, vb + v, wf, hf, tl.lpadw, tl.lpadh, c, x, y);
+                        nonzero = nonzero || x != 0.0f || y != 0.0f;
+                    }
+                    const double step = (double)k / (double)(SAMPLES - 1);
+                    for (int i = lane; i < SAMPLES; i += 64) {
+                        const double x = i == SAMPLES - 1 ? (double)k : (double)i * step;
+                        int q = (int)x;
+                        q = q > k ? k : q;
+                        const int q0 = q == k ? 0 : q;   // the closing vertex
+                        float ax, ay;
+                        canvas_vertex(p.verts, vb + q0, wf, hf, tl.lpadw, tl.lpadh, c, ax, ay);
+                        double px = (double)ax, py = (double)ay;
+                        if (q < k && x != (double)q) {
+                            float bx, by;
+                            canvas_vertex(p.verts, vb + (q + 1 == k ? 0 : q + 1), wf, hf, tl.lpadw, tl.lpadh, c, bx, by);
+                            const double f = x - (double)q;
+                            px = ((double)bx - px) * f + px;
+                            py = ((double)by - py) * f + py;
+                        }
+                        const double X = px * m00 + py * m01 + m02, Y = px * m10 + py * m11 + m12;
+                        if (X >= 0.0 && Y >= 0.0 && X <= Sd && Y <= Sd) {
+                            x1 = !have || X < x1 ? X : x1; x2 = !have || X > x2 ? X : x2;
+                            y1 = !have || Y < y1 ? Y : y1; y2 = !have || Y > y2 ? Y : y2;
+                            have = true;
+                            anyx = anyx || X != 0.0;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const double ox1 = __shfl_xor(x1, d), oy1 = __shfl_xor(y1, d), ox2 = __shfl_xor(x2, d), oy2 = __shfl_xor(y2, d);
+                    const int oh = __shfl_xor((int)have, d);
+                    if (oh) {
+                        x1 = !have || ox1 < x1 ? ox1 : x1; x2 = !have || ox2 > x2 ? ox2 : x2;
+                        y1 = !have || oy1 < y1 ? oy1 : y1; y2 = !have || oy2 > y2 ? oy2 : y2;
+                        have = true;
+                    }
+                }
+                if (__any(nonzero)) flags |= PATH_NONZERO;
+                const bool taken = __any(anyx) != 0;   // segment2box's any(x): with no kept point, or every kept X zero, the box is zeros
+                if (lane == 0 && j < p.ws_rows) {
+                    double* o = p.boxes + j * 4;
+                    o[0] = taken ? x1 : 0.0; o[1] = taken ? y1 : 0.0; o[2] = taken ? x2 : 0.0; o[3] = taken ? y2 : 0.0;
+                    p.inside[j] = taken ? 1 : 0;
+                }
+            }
+        }
+        base += end - beg;
+    }
+    if (lane == 0) s_flag[wave] = flags;
+    __syncthreads();
+    if (tid == 0) {
+        int f = 0;
+#pragma unroll
+        for (int w = 0; w < BT / 64; ++w) f |= s_flag[w];
+        p.paths[mslot] = f;
+    }
+}
+
 // ONE block per batch.  The prefix of the label counts of the batch's tiles (item, mosaic, tile: the reference's order) lives in LDS; the block walks the rows 256 at
 // a time: a lane transforms one label and decides whether box_candidates keeps it, a ballot and the waves' counts give every survivor its place behind the
 // survivors before it, and the per-item counts become the bs + 1 offsets.  Survivors past n_rows are dropped (and not counted).
-__global__ __launch_bounds__(BT) void augment_targets_kernel(const TargetArgs a) {
+// POLY: a row of a mosaic whose word is PATH_NONZERO takes the box augment_polygons_kernel left at its position (no further clip) and area_thr 0.01; every other row,
+// and every row of the plain form, runs the four-corner arithmetic.
+template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kernel(const TargetArgs a, const PolyTables p) {
     __shared__ int s_pref[MAX_BS * SLOTS + 1];
     __shared__ int s_cnt[MAX_BS];
     __shared__ int s_wave[BT / 64];
@@ -313,23 +460,32 @@ __global__ __launch_bounds__(BT) void augment_targets_kernel(const TargetArgs a)
                 const double m00 = mo->m[0], m01 = mo->m[1], m02 = mo->m[2], m10 = mo->m[3], m11 = mo->m[4], m12 = mo->m[5];
                 const double px[4] = {(double)x1, (double)x2, (double)x1, (double)x2}, py[4] = {(double)y1, (double)y2, (double)y2, (double)y1};
                 double nx1 = 0, ny1 = 0, nx2 = 0, ny2 = 0;
+                bool poly = false;
+                if constexpr (POLY) poly = p.paths[(lo >> 2)] == PATH_NONZERO;   // (lo >> 2 is item * 2 + mosaic)
+                if (poly) {   // segment2box of the warped polygon (all zeros without a point inside: the row fails w2 > 2)
+                    if (j < p.ws_rows && p.inside[j]) {
+                        const double* q = p.boxes + (long long)j * 4;
+                        nx1 = q[0]; ny1 = q[1]; nx2 = q[2]; ny2 = q[3];
+                    }
+                } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const double X = px[q] * m00 + py[q] * m01 + m02, Y = px[q] * m10 + py[q] * m11 + m12;
-                    nx1 = q == 0 || X < nx1 ? X : nx1; nx2 = q == 0 || X > nx2 ? X : nx2;
-                    ny1 = q == 0 || Y < ny1 ? Y : ny1; ny2 = q == 0 || Y > ny2 ? Y : ny2;
+                    for (int q = 0; q < 4; ++q) {
+                        const double X = px[q] * m00 + py[q] * m01 + m02, Y = px[q] * m10 + py[q] * m11 + m12;
+                        nx1 = q == 0 || X < nx1 ? X : nx1; nx2 = q == 0 || X > nx2 ? X : nx2;
+                        ny1 = q == 0 || Y < ny1 ? Y : ny1; ny2 = q == 0 || Y > ny2 ? Y : ny2;
+                    }
+                    nx1 = nx1 < 0.0 ? 0.0 : nx1; nx1 = nx1 > Sd ? Sd : nx1;
+                    nx2 = nx2 < 0.0 ? 0.0 : nx2; nx2 = nx2 > Sd ? Sd : nx2;
+                    ny1 = ny1 < 0.0 ? 0.0 : ny1; ny1 = ny1 > Sd ? Sd : ny1;
+                    ny2 = ny2 < 0.0 ? 0.0 : ny2; ny2 = ny2 > Sd ? Sd : ny2;
                 }
-                nx1 = nx1 < 0.0 ? 0.0 : nx1; nx1 = nx1 > Sd ? Sd : nx1;
-                nx2 = nx2 < 0.0 ? 0.0 : nx2; nx2 = nx2 > Sd ? Sd : nx2;
-                ny1 = ny1 < 0.0 ? 0.0 : ny1; ny1 = ny1 > Sd ? Sd : ny1;
-                ny2 = ny2 < 0.0 ? 0.0 : ny2; ny2 = ny2 > Sd ? Sd : ny2;
-                // box_candidates(box1 = targets * s (fp32), box2 = new (fp64), wh_thr 2, ar_thr 100, area_thr 0.1, eps 1e-16)
+                // box_candidates(box1 = targets * s (fp32), box2 = new (fp64), wh_thr 2, ar_thr 100, area_thr 0.1 (0.01 on the polygon path), eps 1e-16)
                 const float sc = (float)mo->scale;
                 const float w1 = x2 * sc - x1 * sc, h1 = y2 * sc - y1 * sc;
                 const double w2 = nx2 - nx1, h2 = ny2 - ny1, eps = 1e-16;
                 const double r1 = w2 / (h2 + eps), r2 = h2 / (w2 + eps), ar = r1 > r2 ? r1 : r2;
                 const float den = w1 * h1 + (float)eps;
-                keep = w2 > 2.0 && h2 > 2.0 && w2 * h2 / (double)den > 0.1 && ar < 100.0;
+                keep = w2 > 2.0 && h2 > 2.0 && w2 * h2 / (double)den > (poly ? 0.01 : 0.1) && ar < 100.0;
                 // the survivor as fp32, xyxy2xywhn(clip=True, eps=1e-3), the flips
                 float fx1 = (float)nx1, fy1 = (float)ny1, fx2 = (float)nx2, fy2 = (float)ny2;
                 fx1 = fx1 < 0.0f ? 0.0f : fx1; fx1 = fx1 > a.clip_s ? a.clip_s : fx1;
@@ -421,7 +577,46 @@ extern "C" int y3_augment_targets(const float* labels, const int64_t* label_offs
     a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
     a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.S = S;
     a.clip_s = (float)((double)S - 1e-3);
-    hipLaunchKernelGGL(augment_targets_kernel, dim3(1), dim3(BT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(augment_targets_kernel<false>, dim3(1), dim3(BT), 0, (hipStream_t)stream, a, PolyTables{});
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                                   const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
+                                   int32_t* paths, int64_t n_rows, void* stream) {
+    if (!vertex_offsets || !label_offsets || (count > 0 && !paths) || (n_vertices > 0 && !vertices) || (n_rows > 0 && (!boxes || !inside))) Y3_FAIL("y3_augment_polygons: null argument");
+    if (check_set("y3_augment_polygons", images, n_images, items, count, S)) return -1;
+    if (n_vertices < 0 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL || n_rows < 0 || n_rows > 0x7fffffffLL / 6)
+        Y3_FAIL("y3_augment_polygons: bad geometry (%lld vertices, %lld label rows, a workspace of %lld rows)", (long long)n_vertices, (long long)n_label_rows, (long long)n_rows);
+    if (!aligned(vertex_offsets, 8) || !aligned(label_offsets, 8) || !aligned(boxes, 8) || !aligned(vertices, 4) || !aligned(inside, 4) || !aligned(paths, 4))
+        Y3_FAIL("y3_augment_polygons: the offsets and the boxes must be 8-byte, the vertices and the int32 words 4-byte aligned");
+    if (count == 0) return 0;
+    TargetArgs a = {};
+    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.S = S;
+    PolyTables p = {};
+    p.verts = vertices; p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
+    p.boxes = boxes; p.inside = inside; p.paths = paths; p.ws_rows = n_rows;
+    hipLaunchKernelGGL(augment_polygons_kernel, dim3((unsigned)count * 2), dim3(BT), 0, (hipStream_t)stream, a, p);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int y3_augment_targets_polygons(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                           int32_t count, int32_t S, const double* boxes, const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows,
+                                           int64_t* offsets, void* stream) {
+    if (!label_offsets || !offsets || (count > 0 && !paths) || (n_rows > 0 && (!labels || !targets || !boxes || !inside))) Y3_FAIL("y3_augment_targets_polygons: null argument");
+    if (check_set("y3_augment_targets_polygons", images, n_images, items, count, S)) return -1;
+    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("y3_augment_targets_polygons: bad geometry (%lld rows)", (long long)n_rows);
+    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(boxes, 8) || !aligned(labels, 4) || !aligned(targets, 4) || !aligned(inside, 4) || !aligned(paths, 4))
+        Y3_FAIL("y3_augment_targets_polygons: the offsets and the boxes must be 8-byte, the fp32 tables and the int32 words 4-byte aligned");
+    TargetArgs a;
+    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
+    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.S = S;
+    a.clip_s = (float)((double)S - 1e-3);
+    PolyTables p = {};
+    p.boxes = const_cast<double*>(boxes); p.inside = const_cast<int*>(inside); p.paths = const_cast<int*>(paths); p.ws_rows = n_rows;
+    hipLaunchKernelGGL(augment_targets_kernel<true>, dim3(1), dim3(BT), 0, (hipStream_t)stream, a, p);
     Y3_CHECK_LAUNCH();
     return 0;
 }

@@ -1077,6 +1077,57 @@ def augment_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: t
     return targets, offsets
 
 
+def augment_polygons(vertices: torch.Tensor, vertex_offsets: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int,
+                     size: int, n_rows: int):
+    """The polygon boxes of one augmented batch (y3_augment_polygons), the launch ahead of augment_targets_polygons: `vertices` fp32 (V, 2) and `vertex_offsets` int64
+    (label rows + 1,) of the set on the device, `n_rows` as for augment_targets -> (DEVICE fp64 (n_rows, 4) segment2box of every label position of the batch's mosaics,
+    DEVICE int32 (n_rows,) whether a point lay inside, DEVICE int32 (count, 2) the path word per item and mosaic: 1 = the polygon path).  Positions of letterbox items
+    are not written."""
+    what = "augment_polygons"
+    require_gpu(vertices, what)
+    require_gpu(vertex_offsets, what)
+    require_gpu(label_offsets, what)
+    _augment_args(what, images, n, items, count, size)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 2 or not vertices.is_contiguous():
+        raise TypeError("augment_polygons expects the contiguous fp32 (V, 2) vertex table")
+    if vertex_offsets.dtype != torch.int64 or vertex_offsets.dim() != 1 or vertex_offsets.numel() < 1 or not vertex_offsets.is_contiguous():
+        raise TypeError("augment_polygons expects contiguous int64 vertex offsets, one per label row plus one")
+    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
+        raise TypeError(f"augment_polygons expects {n + 1} contiguous int64 label offsets")
+    dev = vertices.device
+    boxes = torch.empty(int(n_rows), 4, dtype=torch.float64, device=dev)
+    inside = torch.empty(int(n_rows), dtype=torch.int32, device=dev)
+    paths = torch.empty(int(count), 2, dtype=torch.int32, device=dev)
+    check(_lib.lib().y3_augment_polygons(vertices.data_ptr() if vertices.numel() else None, vertices.shape[0], vertex_offsets.data_ptr(), vertex_offsets.numel() - 1,
+                                         label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count), int(size), boxes.data_ptr() if n_rows else None,
+                                         inside.data_ptr() if n_rows else None, paths.data_ptr() if count else None, int(n_rows), stream_ptr()), "y3_augment_polygons")
+    return boxes, inside, paths
+
+
+def augment_targets_polygons(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int, n_rows: int,
+                             boxes: torch.Tensor, inside: torch.Tensor, paths: torch.Tensor):
+    """augment_targets for a set with polygon labels (y3_augment_targets_polygons): `boxes`, `inside`, `paths` as augment_polygons returned them for this batch; a mosaic
+    whose path word is 1 takes the polygon boxes with area_thr 0.01, every other the four corners with 0.10."""
+    what = "augment_targets_polygons"
+    require_gpu(labels, what)
+    require_gpu(label_offsets, what)
+    _augment_args(what, images, n, items, count, size)
+    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
+        raise TypeError("augment_targets_polygons expects the contiguous fp32 (total, 5) label table")
+    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
+        raise TypeError(f"augment_targets_polygons expects {n + 1} contiguous int64 label offsets")
+    for t, dt, shape in ((boxes, torch.float64, (int(n_rows), 4)), (inside, torch.int32, (int(n_rows),)), (paths, torch.int32, (int(count), 2))):
+        require_gpu(t, what)
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"augment_targets_polygons expects the contiguous {dt} {shape} workspace of augment_polygons")
+    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
+    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
+    check(_lib.lib().y3_augment_targets_polygons(labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count),
+                                                 int(size), boxes.data_ptr() if n_rows else None, inside.data_ptr() if n_rows else None, paths.data_ptr() if count else None,
+                                                 targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr()), "y3_augment_targets_polygons")
+    return targets, offsets
+
+
 _coco_ws: dict = {}
 
 
