@@ -408,10 +408,11 @@ int y3_dataset_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset
 int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const int64_t* indices, int64_t first,
                        int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
 
-/* The train-mode loader over the same arena and record table (csrc/augment.hip): the augment=True, rect=False path of reference utils/dataloaders.py:659-735, 764-822
+/* The train-mode loader over the same arena and record table (csrc/augment.hip): the augment=True path of reference utils/dataloaders.py:659-735, 764-822
  * and utils/augmentations.py:57-73, 137-216, 270-283 -- mosaic, random_perspective (affine only), mixup, augment_hsv, the flips, collate_fn.  The host draws the random
  * numbers and sends one y3_augment_item per item of the batch (DEVICE, 8-byte aligned); nothing here allocates or synchronises.
- * A mosaic is a square canvas of `canvas` pixels (2 S, or S for the letterbox branch) filled with 114 on which tile t shows image `img`: canvas pixel (X, Y) of the
+ * A mosaic is a canvas of `canvas` x `canvas` pixels (2 S, or S for the letterbox branch) -- or, with canvas_h != 0, `canvas` wide and `canvas_h` high: the (W, H) of
+ *   a rect=True batch, whose items take the letterbox branch -- filled with 114 on which tile t shows image `img`: canvas pixel (X, Y) of the
  *   rectangle [x1, x2) x [y1, y2) is image pixel (X - padw, Y - padh).  inv is the inverse of the affine matrix m (both row-major 2 x 3, float64).  An item blends
  *   two mosaics when nmos == 2: trunc(a * ratio + b * ratio1) in float64.  lut: the hue, saturation and value tables of augment_hsv, applied when hsv != 0.
  * augment_batch: dst is DEVICE (count, 3, S, S) of dst_dtype, contiguous, 16-byte aligned, written in one launch: per output pixel the flips undone, the source
@@ -435,18 +436,24 @@ int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const 
  *   not written.  No read leaves the tables whatever the items and the offsets hold.
  * augment_targets_polygons: augment_targets, except that every row of a mosaic whose paths word is 1 (every row has a polygon, something is not zero) takes boxes[j]
  *   unclipped in place of the four warped corners and area_thr 0.01 in place of 0.1 (a row with inside[j] == 0 has a zero box and is dropped); every other mosaic runs
- *   the arithmetic of augment_targets. */
+ *   the arithmetic of augment_targets.
+ * augment_batch_hw / augment_targets_hw: the same two launches for items of H rows and W columns (the batch shape of a rect=True set): dst is (count, 3, H, W), the
+ *   flips are W - 1 - x and H - 1 - y, the warped boxes are clipped to [0, W] x [0, H], then to [0, W - 1e-3] x [0, H - 1e-3] (formed in double, rounded to fp32
+ *   once) and normalised per axis.  The reference's letterbox takes a rect batch's shape from a NumPy array, so its ratio and halves are float64 scalars and NumPy (>= 2)
+ *   forms the product and the sum of xywhn2xyxy in float64: the tiles of such items carry wide != 0.  Limits: H % 16 == 0, W % 16 == 0, both in 16 .. 4096.  The square exports are these with H = W = S.  The polygon exports are
+ *   square only. */
 typedef struct {
     int32_t img;            /* index into the record table */
     int32_t x1, y1, x2, y2; /* the rectangle on the canvas */
     int32_t padw, padh;     /* canvas position of image pixel (0, 0) */
     float lpadw, lpadh;     /* the same for the labels (letterbox's halves may end in .5) */
-    int32_t reserved;
+    int32_t wide;           /* != 0: xywhn2xyxy forms w (x - bw / 2) + lpadw in float64 and rounds to fp32 once (a rect item, below); 0: fp32 throughout */
 } y3_augment_tile;          /* 40 bytes */
 typedef struct {
     double inv[6], m[6];
     double scale;           /* random_perspective's s */
-    int32_t ntiles, canvas, clip, reserved;
+    int32_t ntiles, canvas, clip;
+    int32_t canvas_h;       /* the canvas height where it is not `canvas`; 0: a square canvas */
     y3_augment_tile tiles[4];
 } y3_augment_mosaic;        /* 280 bytes */
 typedef struct {
@@ -459,6 +466,10 @@ int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset
                      int32_t dst_dtype, int32_t S, void* stream);
 int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
                        int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
+int y3_augment_batch_hw(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, void* dst,
+                        int32_t dst_dtype, int32_t H, int32_t W, void* stream);
+int y3_augment_targets_hw(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                          int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
 int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
                         const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
                         int32_t* paths, int64_t n_rows, void* stream);

@@ -22,6 +22,8 @@ Public surface mirrors the reference's own Python signatures:
     DeviceTrainDataset / draw_item       (reference utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283: the augment=True loader -- mosaic, affine
                                          warp, HSV, flips and mixup sampled straight from the cached images in one launch per batch, the labels in another; the host keeps
                                          the reference's random stream; polygon labels (segments=) warp as 1000 resampled points per polygon in one more launch)
+    DeviceRectTrainDataset               (reference utils/dataloaders.py:547-570, 659-735; utils/augmentations.py:104-216: the augment=True, rect=True loader of train.py --rect --
+                                         the set in aspect-ratio order, every batch letterboxed to its own (H, W), affine warp, HSV and flips in the same two launches)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
@@ -39,7 +41,7 @@ from .backend import DetectMultiBackend  # noqa: F401
 from .autoanchor import anchor_metrics, check_anchor_order, check_anchors, kmean_anchors  # noqa: F401
 from .label_weights import LabelTable, image_weight_indices, labels_to_class_weights, labels_to_image_weights  # noqa: F401
 from .dataset import DeviceDataset, rect_batch_shapes  # noqa: F401
-from .augment import DeviceTrainDataset, draw_item  # noqa: F401
+from .augment import DeviceRectTrainDataset, DeviceTrainDataset, draw_item  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
 from .coco_eval import CocoEval, CocoGroundTruth, CocoResult  # noqa: F401

@@ -25,10 +25,28 @@ statement of tests/augment_polygon_cases.py, which the generator asserts equal t
 cv2.cvtColor conversions follow the integer / fp32 statements of tests/augment_cases.py, which restate the published 8-bit algorithms and have not been compared with
 a cv2 build.
 
+Rectangular training (train.py --rect; LoadImagesAndLabels(augment=True, rect=True), dataloaders.py:547-570):
+
+    ds = DeviceRectTrainDataset(images, labels, hyp, img_size=640, batch_size=64, stride=32)   # or DeviceRectTrainDataset.from_dataset(train_loader.dataset, batch_size=64)
+    for im, targets, paths, shapes in ds: ...                                                  # im (bs, 3, H_k, W_k): batch k has its own shape
+
+The set is sorted by aspect ratio and laid out as a rect DeviceDataset with pad=0.0 (rect_batch_shapes: every H_k and W_k a multiple of stride, [maxi, 1] for a batch of
+wide images, [1, 1 / mini] for one of tall images, else square).  The reference sets mosaic = augment and not rect and forces shuffle off: every item is the letterbox
+branch -- pasted at round(dh - 0.1), round(dw - 0.1) on its batch's H x W canvas, random_perspective with C = (-W / 2, -H / 2) and T = (u W, u H), the labels clipped to
+[0, W] x [0, H], area_thr 0.10 (segments are accepted and not used, as __getitem__ hands none on), xyxy2xywhn per axis, HSV, the flips; no mixup, and `shapes` is the
+letterbox tuple of every item.  draw_item and draw_perspective take the pair (H, W) for this.  The same two launches per batch through y3_augment_batch_hw /
+y3_augment_targets_hw: the kernels of csrc/augment.hip work on H x W items, and the square exports call them with H = W = S.  One difference of the reference's own
+arithmetic is reproduced: letterbox takes a rect batch's shape from a NumPy array, so its ratio and halves are float64 scalars and NumPy (>= 2) forms xywhn2xyxy's
+product and sum in float64 before the fp32 label array rounds them once; the tiles of rect items carry `wide` and the kernel does the same (a square set's labels
+stay fp32 throughout, as there).  Pinned by tests/golden/make_augment_rect_golden.py (stride 16, batches of (48, 64), (64, 64) and (64, 48)).
+
 Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0, polygon labels whose count is neither 0 nor the image's label rows
-(the reference would send such a mosaic down the box path; here it is an error: a stated difference) or that hold an empty polygon, rect=True, an image whose long
-side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; KeyError for a missing hyp key.  Albumentations is a no-op, as
-in the reference when the package is absent.  Out of scope: warpPerspective, copy-paste, load_mosaic9, cutout, prefetching, returning the warped polygons.
+(the reference would send such a mosaic down the box path; here it is an error: a stated difference) or that hold an empty polygon, rect=True on DeviceTrainDataset
+(DeviceRectTrainDataset is that loader), an image whose long side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; on a
+rect set an image that letterbox(scaleup=True) would resize (r = min(H / h, W / w) != 1; the message names the image, its size and the batch shape), an img_size or
+stride that is no multiple of 16, and set_indices (the batch shapes belong to the order); KeyError for a missing hyp key.  Albumentations is a no-op, as in the
+reference when the package is absent.  Out of scope: warpPerspective, copy-paste, a resize inside letterbox, load_mosaic9, cutout, prefetching, returning the warped
+polygons.
 """
 from __future__ import annotations
 
@@ -53,7 +71,8 @@ assert (TILE.itemsize, MOSAIC.itemsize, ITEM.itemsize) == (40, 280, 1360)
 @dataclass
 class Mosaic:
     """One canvas and its warp: `indices` the images of the tiles in paste order, `rects` per tile (x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b), `M` the 3 x 3 float64
-    matrix of random_perspective, `scale` its s, `canvas` the side of the canvas (2 s, or s for the letterbox branch), `pad` per tile the (padw, padh) of its labels."""
+    matrix of random_perspective, `scale` its s, `canvas` the side of the canvas (2 s, or s for the letterbox branch), `pad` per tile the (padw, padh) of its labels;
+    `canvas_h` the height of the canvas of a rect item (`canvas` is then its width; the labels of such an item go through xywhn2xyxy in float64), else None."""
 
     indices: list
     rects: list
@@ -62,6 +81,7 @@ class Mosaic:
     canvas: int
     pad: list
     center: tuple | None = None   # (yc, xc)
+    canvas_h: int | None = None
 
 
 @dataclass
@@ -82,12 +102,18 @@ def rotation_matrix_2d(angle, scale):
     return [[alpha, beta, (1 - alpha) * 0 - beta * 0], [-beta, alpha, beta * 0 + (1 - alpha) * 0]]
 
 
+def _hw(size):
+    """img_size, or the (H, W) of a rect batch -> (H, W)"""
+    return (int(size[0]), int(size[1])) if isinstance(size, (tuple, list, np.ndarray)) else (int(size), int(size))
+
+
 def draw_perspective(hyp, side, border):
-    """random_perspective's eight draws and its matrix for a (side, side) image: -> (M (3, 3) float64, s)"""
-    height = width = side + border * 2
+    """random_perspective's eight draws and its matrix for a (side, side) image, or the (H, W) image `side` names as a pair: -> (M (3, 3) float64, s)"""
+    h, w = side if isinstance(side, (tuple, list, np.ndarray)) else (side, side)
+    height, width = h + border * 2, w + border * 2
     C, P, R, S, T = (np.eye(3) for _ in range(5))
-    C[0, 2] = -side / 2
-    C[1, 2] = -side / 2
+    C[0, 2] = -w / 2
+    C[1, 2] = -h / 2
     perspective = hyp["perspective"]
     P[2, 0] = random.uniform(-perspective, perspective)
     P[2, 1] = random.uniform(-perspective, perspective)
@@ -133,8 +159,15 @@ def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
     the reference's order: random.random() for mosaic; load_mosaic (two uniforms, yc then xc, choices(pool, k=3), shuffle) and random_perspective's eight uniforms;
     random.random() for mixup and, on mixup, randint(0, n - 1), a second load_mosaic and np.random.beta(32, 32) -- or the letterbox branch with its one
     random_perspective; np.random.uniform(-1, 1, 3) if an HSV gain is non-zero; random.random() for flipud, then for fliplr.
-    hw: the cached (h, w) of every image; pool: the epoch's order (default range(n)); n: the number of images (default len(hw))."""
-    s = int(img_size)
+    hw: the cached (h, w) of every image; pool: the epoch's order (default range(n)); n: the number of images (default len(hw)).
+    img_size: the side of the square item, or the (H, W) of a rect batch, whose items are drawn with mosaic=False (the reference's mosaic = augment and not rect).
+    The shape of a rect batch is an element of a NumPy array in the reference, so letterbox's ratio and halves are float64 scalars there and NumPy (>= 2) forms
+    xywhn2xyxy's product and sum in float64 before the label array rounds them: such an item's Mosaic carries canvas_h, and the kernel does the same."""
+    H, W = _hw(img_size)
+    rect = isinstance(img_size, (tuple, list, np.ndarray))   # the batch shape of a rect set, a square one included
+    if mosaic and H != W:
+        raise ValueError(f"draw_item: a {H}x{W} item is a rect batch's; load_mosaic is square (mosaic=False)")
+    s = W
     n = len(hw) if n is None else int(n)
     pool = range(n) if pool is None else pool
     ratio = None
@@ -147,10 +180,10 @@ def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
     else:
         is_mosaic = False
         h, w = hw[index]
-        dw, dh = (s - w) / 2, (s - h) / 2
+        dw, dh = (W - w) / 2, (H - h) / 2
         top, left = round(dh - 0.1), round(dw - 0.1)
-        M, scale = draw_perspective(hyp, s, 0)
-        mosaics = [Mosaic([int(index)], [(left, top, left + w, top + h, 0, 0, w, h)], M, scale, s, [(dw, dh)])]
+        M, scale = draw_perspective(hyp, (H, W) if rect else s, 0)
+        mosaics = [Mosaic([int(index)], [(left, top, left + w, top + h, 0, 0, w, h)], M, scale, s, [(dw, dh)], None, H if rect else None)]
     luts = None
     if hyp["hsv_h"] or hyp["hsv_s"] or hyp["hsv_v"]:
         r = np.random.uniform(-1, 1, 3) * [hyp["hsv_h"], hyp["hsv_s"], hyp["hsv_v"]] + 1
@@ -186,9 +219,10 @@ def pack_items(items, out=None) -> np.ndarray:
             m = r["mosaics"][k]
             m["inv"], m["m"], m["scale"] = invert_affine(mo.M), mo.M[:2].reshape(-1), mo.scale
             m["ntiles"], m["canvas"], m["clip"] = len(mo.indices), mo.canvas, int(it.mosaic)
+            m["canvas_h"] = 0 if mo.canvas_h is None else mo.canvas_h
             for t, (j, rect, (padw, padh)) in enumerate(zip(mo.indices, mo.rects, mo.pad)):
                 x1a, y1a, x2a, y2a, x1b, y1b = rect[:6]
-                m["tiles"][t] = (j, x1a, y1a, x2a, y2a, x1a - x1b, y1a - y1b, padw, padh, 0)
+                m["tiles"][t] = (j, x1a, y1a, x2a, y2a, x1a - x1b, y1a - y1b, padw, padh, int(mo.canvas_h is not None))
     return rec
 
 
@@ -240,7 +274,8 @@ class DeviceTrainDataset(DeviceDataset):
         if segments is not None and any(len(sg) for sg in segments):
             polygons = pack_polygons(labels, segments, paths)   # (host only: the vertex table goes up after the images)
         if rect:
-            raise ValueError("DeviceTrainDataset: rect=True; the reference sets mosaic = augment and not rect, use DeviceDataset for rectangular batches")
+            raise ValueError("DeviceTrainDataset: rect=True; the reference sets mosaic = augment and not rect, use DeviceRectTrainDataset for augmented rectangular batches "
+                             "(DeviceDataset for augment=False)")
         if int(img_size) != img_size or int(img_size) < 16 or int(img_size) % 16:
             raise ValueError(f"DeviceTrainDataset: img_size = {img_size} must be a multiple of 16 (hence even: the mosaic border is img_size / 2)")
         for i, im in enumerate(images):
@@ -296,3 +331,87 @@ class DeviceTrainDataset(DeviceDataset):
             targets, offsets = ops.augment_targets_polygons(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper, *self.polygons)
         nl = int(offsets.cpu()[count])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
         return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
+
+
+class DeviceRectTrainDataset(DeviceDataset):
+    """The cached images and labels of an augment=True, rect=True dataset in device memory (train.py --rect): the set sorted by aspect ratio and every batch k
+    letterboxed to its own batch_shapes[k] = (H_k, W_k), as a rect DeviceDataset with pad=0.0 lays it out; no mosaic and no mixup, every item the letterbox branch
+    with random_perspective (affine), augment_hsv and the flips on the device.  Iterating yields (im (bs, 3, H_k, W_k), targets (nl, 6), paths, shapes), shapes[i] the
+    letterbox tuple of every item.  hyp: the reference's dict (HYP_KEYS are read; `mosaic` and `mixup` are not used).  segments: accepted and not used, as the
+    reference hands none to random_perspective on this branch (area_thr stays 0.10).  The order is the set's: set_indices raises."""
+
+    def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, device="cuda", dtype=torch.uint8,
+                 segments=None, _adopt=None):
+        # every refusal comes before anything is uploaded
+        hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
+        if hyp["perspective"] != 0:
+            raise ValueError(f"DeviceRectTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
+        if hyp["copy_paste"] != 0:
+            raise ValueError(f"DeviceRectTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        for name, v in (("img_size", img_size), ("stride", stride)):
+            if int(v) != v or int(v) < 16 or int(v) % 16:
+                raise ValueError(f"DeviceRectTrainDataset: {name} = {v} must be a multiple of 16 (both sides of every batch shape are multiples of stride)")
+        if all(isinstance(im, np.ndarray) and im.ndim == 3 for im in images) and (shapes0 is None or len(shapes0) == len(images)):   # (else the shared constructor refuses)
+            self._refuse_resize(images, [im.shape[:2] for im in images] if shapes0 is None else shapes0, int(img_size), int(batch_size), int(stride), paths, _adopt)
+        super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=True, shapes0=shapes0, paths=paths, single_cls=single_cls,
+                         device=device, dtype=dtype, _adopt=_adopt)
+        self.hyp = hyp
+        self.hw = [tuple(int(v) for v in images[i].shape[:2]) for i in self.order]   # in the set's order, as the record table is
+        self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
+        self._stage_rec = self._stage.numpy().view(ITEM)
+        self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
+
+    @staticmethod
+    def _refuse_resize(images, hw0, img_size, batch_size, stride, paths, adopt):
+        """letterbox(scaleup=True) resizes unless r = min(H / h, W / w) is exactly 1: ValueError for the first image of the set's order for which it is not"""
+        n = len(images)
+        if n < 1 or int(batch_size) < 1:
+            return   # (the shared constructor refuses these)
+        if adopt is not None:
+            order, batch, batch_shapes = np.arange(n), np.asarray(adopt[0]).astype(int), np.asarray(adopt[1]).astype(int).reshape(-1, 2)
+            if len(batch) != n or batch.min() < 0 or batch.max() >= len(batch_shapes):
+                return   # (layout refuses a batch index that was not built for this set)
+        else:
+            order, batch, batch_shapes = _dataset.rect_batch_shapes([(w0, h0) for h0, w0 in hw0], img_size, batch_size, stride, 0.0)
+        for j, i in enumerate(order):
+            (h, w), (H, W) = images[i].shape[:2], (int(v) for v in batch_shapes[batch[j]])
+            if h < 1 or w < 1 or min(H / h, W / w) != 1.0:
+                raise ValueError(f"DeviceRectTrainDataset: image {paths[i] if paths is not None else i} is {h}x{w} and its batch shape {H}x{W}: letterbox(scaleup=True) "
+                                 "would resize it (r != 1), and cv2.resize is out of scope")
+
+    @classmethod
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False):
+        """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=True: reads .ims, .im_hw0, .im_hw, .labels, .im_files, .hyp, .img_size,
+        .stride, .rect, .augment and, where present, .segments and .batch / .batch_shapes (the aspect-ratio order the dataset is already in is adopted)."""
+        ims = list(dataset.ims)
+        if any(im is None for im in ims):
+            raise ValueError('DeviceRectTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
+        if not getattr(dataset, "augment", False):
+            raise ValueError("DeviceRectTrainDataset.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
+        if not dataset.rect:
+            raise ValueError("DeviceRectTrainDataset.from_dataset: the dataset is not rectangular (rect=False); use DeviceTrainDataset")
+        for i, (im, hw) in enumerate(zip(ims, dataset.im_hw)):
+            if isinstance(im, np.ndarray) and tuple(im.shape[:2]) != tuple(int(v) for v in hw):
+                raise ValueError(f"DeviceRectTrainDataset.from_dataset: im_hw[{i}] = {tuple(hw)} is not the cached image's {im.shape[:2]}")
+        adopt = (dataset.batch, dataset.batch_shapes) if hasattr(dataset, "batch") and hasattr(dataset, "batch_shapes") else None
+        return cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
+                   paths=dataset.im_files, single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), _adopt=adopt)
+
+    def draw_batch(self, k: int):
+        """the items of batch k, drawn now from the global generators: a list of Item"""
+        shape = tuple(int(v) for v in self.batch_shapes[k])
+        return [draw_item(i, self.hw, self.hyp, shape, None, self.n, False) for i in self.batch_images(k)]
+
+    def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
+        """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
+        items = self.draw_batch(k) if items is None else items
+        count = len(items)
+        H, W = (int(v) for v in self.batch_shapes[k])
+        pack_items(items, self._stage_rec[:count])
+        nbytes = count * ITEM.itemsize
+        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
+        upper = int(sum(self._counts[it.index] for it in items))
+        im = ops.augment_batch_hw(self._arena, self._records, self.n, self._items_dev, count, H, W, self.dtype, out)
+        targets, offsets = ops.augment_targets_hw(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, H, W, upper)
+        nl = int(offsets.cpu()[count])   # the one device -> host read (it also frees the staging buffer for the next batch)
+        return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(self.shapes[it.index] for it in items)

@@ -1,5 +1,6 @@
-// The train-mode loader on the device (gfx950): what the reference's LoadImagesAndLabels.__getitem__ does per item on the host for an augment=True, rect=False set whose
-// images are cached already resized (utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283) --
+// The train-mode loader on the device (gfx950): what the reference's LoadImagesAndLabels.__getitem__ does per item on the host for an augment=True set whose images are
+// cached already resized (utils/dataloaders.py:659-735, 764-822; utils/augmentations.py:57-73, 137-216, 270-283) -- rect=False with its S x S items, and rect=True,
+// whose items are letterboxed to their batch's H x W and take the letterbox branch only (the _hw exports; the square exports run the same kernels with H = W = S) --
 //   * load_mosaic's paste of four images into a 2s x 2s canvas of 114 (or letterbox's border around one), random_perspective's cv2.warpAffine, mixup's blend, augment_hsv,
 //     np.flipud / np.fliplr, transpose((2, 0, 1))[::-1] and torch.stack                      -> augment_batch_kernel, ONE launch per batch; the canvas is never materialised;
 //   * xywhn2xyxy per tile, the clip to the canvas, the four-corner transform, box_candidates, xyxy2xywhn(clip=True, eps=1e-3), the flips of the labels, mixup's
@@ -34,8 +35,8 @@ struct BatchArgs {
     long long n_images;
     const y3_augment_item* items;
     void* dst;
-    int count, S, pixels;          // pixels = S * S
-    y3_divisor s_div;
+    int count, H, W, pixels;       // pixels = H * W
+    y3_divisor w_div;
 };
 
 template <typename D> Y3_DEV void store_px(D* d, const float* v);   // 16 bytes: 16 / sizeof(D) values
@@ -68,18 +69,18 @@ Y3_DEV void setup_tile(Tiles& T, int slot, const BatchArgs& a, const y3_augment_
     const y3_augment_mosaic* mo = &it->mosaics[m];
     if (m < clampi(it->nmos, 0, 2) && t < clampi(mo->ntiles, 0, 4)) {
         const y3_augment_tile tl = mo->tiles[t];
-        const int canvas = clampi(mo->canvas, 0, 2 * MAX_S);
+        const int canvas_w = clampi(mo->canvas, 0, 2 * MAX_S), canvas_h = mo->canvas_h ? clampi(mo->canvas_h, 0, 2 * MAX_S) : canvas_w;   // canvas_h 0: a square canvas
         if (tl.img >= 0 && tl.img < a.n_images) {
             const y3_dataset_image r = a.images[tl.img];
             if (r.w >= 1 && r.h >= 1 && r.w <= 0xffff && r.h <= 0xffff && r.offset >= 0 && r.offset <= a.arena_bytes && 3LL * r.w * r.h <= a.arena_bytes - r.offset) {
                 // the part of the rectangle that lies on the canvas AND whose source pixel (X - padw, Y - padh) lies in the image
                 const long long lx = tl.padw > 0 ? tl.padw : 0, ly = tl.padh > 0 ? tl.padh : 0;
                 long long hx = (long long)tl.padw + r.w, hy = (long long)tl.padh + r.h;
-                hx = hx < canvas ? hx : canvas;
-                hy = hy < canvas ? hy : canvas;
+                hx = hx < canvas_w ? hx : canvas_w;
+                hy = hy < canvas_h ? hy : canvas_h;
                 const long long ax1 = tl.x1 > lx ? tl.x1 : lx, ay1 = tl.y1 > ly ? tl.y1 : ly, ax2 = tl.x2 < hx ? tl.x2 : hx, ay2 = tl.y2 < hy ? tl.y2 : hy;
                 if (ax1 < ax2 && ay1 < ay2) {
-                    x1 = (int)ax1; y1 = (int)ay1; x2 = (int)ax2; y2 = (int)ay2;   // all in [0, canvas]
+                    x1 = (int)ax1; y1 = (int)ay1; x2 = (int)ax2; y2 = (int)ay2;   // inside the canvas
                     pitch = 3 * r.w;
                     base = r.offset - ((long long)tl.padh * r.w + tl.padw) * 3;
                 }
@@ -143,12 +144,12 @@ template <typename D> __global__ __launch_bounds__(BT) void augment_batch_kernel
         s_hdiv[tid] = tid ? (int)rint((double)(180 << 12) / (6.0 * tid)) : 0;
     }
     __syncthreads();
-    const int valid = a.pixels - first < CHUNK ? a.pixels - first : CHUNK;   // a multiple of 256: S is one of 16
+    const int valid = a.pixels - first < CHUNK ? a.pixels - first : CHUNK;   // a multiple of 256: H and W are multiples of 16
     const double r0 = it->ratio, r1 = it->ratio1;
     for (int k = tid; k < valid; k += BT) {
         const int p = first + k;
-        const int y = y3_fdiv(p, a.s_div), x = p - y * a.S;
-        const int ox = lr ? a.S - 1 - x : x, oy = ud ? a.S - 1 - y : y;
+        const int y = y3_fdiv(p, a.w_div), x = p - y * a.W;
+        const int ox = lr ? a.W - 1 - x : x, oy = ud ? a.H - 1 - y : y;
         int c0[3] = {BORDER, BORDER, BORDER};
         if (nmos >= 1) sample(T, a.arena, &it->mosaics[0], 0, ox, oy, c0);
         if (nmos == 2) {   // mixup: (im * r + im2 * (1 - r)).astype(uint8) in float64
@@ -223,8 +224,8 @@ struct TargetArgs {
     float* out;
     long long n_rows;
     long long* out_offsets;
-    int count, S;
-    float clip_s;   // S - eps: computed in double, rounded to fp32 once
+    int count, H, W;
+    float clip_w, clip_h;   // W - eps, H - eps: computed in double, rounded to fp32 once
 };
 
 // the label rows of tile `slot` of the batch: [beg, end) of the table, or nothing
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(BT) void augment_polygons_kernel(const TargetArgs a
     }
     const int ntiles = clampi(mo->ntiles, 0, 4);
     const float c = (float)mo->canvas;
-    const double Sd = (double)a.S;
+    const double Sd = (double)a.W;   // (square only: H == W)
     const double m00 = mo->m[0], m01 = mo->m[1], m02 = mo->m[2], m10 = mo->m[3], m11 = mo->m[4], m12 = mo->m[5];
     int flags = 0;
     for (int t = 0; t < ntiles; ++t) {
@@ -415,8 +416,8 @@ template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kerne
     }
     __syncthreads();
     const int have = s_pref[nslots];
-    const float Sf = (float)a.S;
-    const double Sd = (double)a.S;
+    const float Wf = (float)a.W, Hf = (float)a.H;
+    const double Wd = (double)a.W, Hd = (double)a.H;
     long long running = 0;
     for (int base = 0; base < have; base += BT) {
         const int j = base + tid;
@@ -445,16 +446,24 @@ template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kerne
                 const float wf = (float)im.w, hf = (float)im.h;
                 // xywhn2xyxy with the tile's w, h, padw, padh (fp32)
                 const float hw2 = bw / 2.0f, hh2 = bh / 2.0f;
-                float x1 = wf * (xc - hw2) + tl.lpadw;
-                float y1 = hf * (yc - hh2) + tl.lpadh;
-                float x2 = wf * (xc + hw2) + tl.lpadw;
-                float y2 = hf * (yc + hh2) + tl.lpadh;
+                float x1, y1, x2, y2;
+                if (tl.wide) {   // a rect item: letterbox took its shape from a NumPy array, so the ratio and the halves are float64 scalars: product and sum in fp64, one rounding
+                    x1 = (float)((double)wf * (double)(xc - hw2) + (double)tl.lpadw);
+                    y1 = (float)((double)hf * (double)(yc - hh2) + (double)tl.lpadh);
+                    x2 = (float)((double)wf * (double)(xc + hw2) + (double)tl.lpadw);
+                    y2 = (float)((double)hf * (double)(yc + hh2) + (double)tl.lpadh);
+                } else {
+                    x1 = wf * (xc - hw2) + tl.lpadw;
+                    y1 = hf * (yc - hh2) + tl.lpadh;
+                    x2 = wf * (xc + hw2) + tl.lpadw;
+                    y2 = hf * (yc + hh2) + tl.lpadh;
+                }
                 if (mo->clip) {   // np.clip(x, 0, 2 s) of load_mosaic
-                    const float c = (float)mo->canvas;
+                    const float c = (float)mo->canvas, ch = mo->canvas_h ? (float)mo->canvas_h : c;
                     x1 = x1 < 0.0f ? 0.0f : x1; x1 = x1 > c ? c : x1;
-                    y1 = y1 < 0.0f ? 0.0f : y1; y1 = y1 > c ? c : y1;
+                    y1 = y1 < 0.0f ? 0.0f : y1; y1 = y1 > ch ? ch : y1;
                     x2 = x2 < 0.0f ? 0.0f : x2; x2 = x2 > c ? c : x2;
-                    y2 = y2 < 0.0f ? 0.0f : y2; y2 = y2 > c ? c : y2;
+                    y2 = y2 < 0.0f ? 0.0f : y2; y2 = y2 > ch ? ch : y2;
                 }
                 // the four corners through M in fp64, each coordinate a plain left-to-right sum of three terms
                 const double m00 = mo->m[0], m01 = mo->m[1], m02 = mo->m[2], m10 = mo->m[3], m11 = mo->m[4], m12 = mo->m[5];
@@ -474,10 +483,10 @@ template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kerne
                         nx1 = q == 0 || X < nx1 ? X : nx1; nx2 = q == 0 || X > nx2 ? X : nx2;
                         ny1 = q == 0 || Y < ny1 ? Y : ny1; ny2 = q == 0 || Y > ny2 ? Y : ny2;
                     }
-                    nx1 = nx1 < 0.0 ? 0.0 : nx1; nx1 = nx1 > Sd ? Sd : nx1;
-                    nx2 = nx2 < 0.0 ? 0.0 : nx2; nx2 = nx2 > Sd ? Sd : nx2;
-                    ny1 = ny1 < 0.0 ? 0.0 : ny1; ny1 = ny1 > Sd ? Sd : ny1;
-                    ny2 = ny2 < 0.0 ? 0.0 : ny2; ny2 = ny2 > Sd ? Sd : ny2;
+                    nx1 = nx1 < 0.0 ? 0.0 : nx1; nx1 = nx1 > Wd ? Wd : nx1;
+                    nx2 = nx2 < 0.0 ? 0.0 : nx2; nx2 = nx2 > Wd ? Wd : nx2;
+                    ny1 = ny1 < 0.0 ? 0.0 : ny1; ny1 = ny1 > Hd ? Hd : ny1;
+                    ny2 = ny2 < 0.0 ? 0.0 : ny2; ny2 = ny2 > Hd ? Hd : ny2;
                 }
                 // box_candidates(box1 = targets * s (fp32), box2 = new (fp64), wh_thr 2, ar_thr 100, area_thr 0.1 (0.01 on the polygon path), eps 1e-16)
                 const float sc = (float)mo->scale;
@@ -488,14 +497,14 @@ template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kerne
                 keep = w2 > 2.0 && h2 > 2.0 && w2 * h2 / (double)den > (poly ? 0.01 : 0.1) && ar < 100.0;
                 // the survivor as fp32, xyxy2xywhn(clip=True, eps=1e-3), the flips
                 float fx1 = (float)nx1, fy1 = (float)ny1, fx2 = (float)nx2, fy2 = (float)ny2;
-                fx1 = fx1 < 0.0f ? 0.0f : fx1; fx1 = fx1 > a.clip_s ? a.clip_s : fx1;
-                fx2 = fx2 < 0.0f ? 0.0f : fx2; fx2 = fx2 > a.clip_s ? a.clip_s : fx2;
-                fy1 = fy1 < 0.0f ? 0.0f : fy1; fy1 = fy1 > a.clip_s ? a.clip_s : fy1;
-                fy2 = fy2 < 0.0f ? 0.0f : fy2; fy2 = fy2 > a.clip_s ? a.clip_s : fy2;
-                ox = ((fx1 + fx2) / 2.0f) / Sf;
-                oy = ((fy1 + fy2) / 2.0f) / Sf;
-                ow = (fx2 - fx1) / Sf;
-                oh = (fy2 - fy1) / Sf;
+                fx1 = fx1 < 0.0f ? 0.0f : fx1; fx1 = fx1 > a.clip_w ? a.clip_w : fx1;
+                fx2 = fx2 < 0.0f ? 0.0f : fx2; fx2 = fx2 > a.clip_w ? a.clip_w : fx2;
+                fy1 = fy1 < 0.0f ? 0.0f : fy1; fy1 = fy1 > a.clip_h ? a.clip_h : fy1;
+                fy2 = fy2 < 0.0f ? 0.0f : fy2; fy2 = fy2 > a.clip_h ? a.clip_h : fy2;
+                ox = ((fx1 + fx2) / 2.0f) / Wf;
+                oy = ((fy1 + fy2) / 2.0f) / Hf;
+                ow = (fx2 - fx1) / Wf;
+                oh = (fy2 - fy1) / Hf;
                 if (it->flipud) oy = 1.0f - oy;
                 if (it->fliplr) ox = 1.0f - ox;
             }
@@ -530,31 +539,28 @@ template <bool POLY> __global__ __launch_bounds__(BT) void augment_targets_kerne
 
 bool aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
-int check_set(const char* fn, const void* images, int64_t n_images, const void* items, int32_t count, int32_t S) {
+int check_set(const char* fn, const void* images, int64_t n_images, const void* items, int32_t count, int32_t H, int32_t W) {
     if (!images || !items) Y3_FAIL("%s: null argument", fn);
-    if (n_images < 1 || n_images > 0x7fffffffLL || count < 0 || count > MAX_BS || S < 16 || S > MAX_S)
-        Y3_FAIL("%s: bad geometry (%lld images in 1 .. 2^31 - 1, a batch of %d in 0 .. %d items of %d x %d in 16 .. %d)", fn, (long long)n_images, count, MAX_BS, S, S, MAX_S);
-    if (S % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, S);
+    if (n_images < 1 || n_images > 0x7fffffffLL || count < 0 || count > MAX_BS || H < 16 || H > MAX_S || W < 16 || W > MAX_S)
+        Y3_FAIL("%s: bad geometry (%lld images in 1 .. 2^31 - 1, a batch of %d in 0 .. %d items of %d x %d in 16 .. %d)", fn, (long long)n_images, count, MAX_BS, H, W, MAX_S);
+    if (H % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, H);
+    if (W % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, W);
     if (!aligned(images, 8) || !aligned(items, 8)) Y3_FAIL("%s: the record table and the items must be 8-byte aligned", fn);
     return 0;
 }
 
-}  // namespace
-
-static_assert(sizeof(y3_augment_tile) == 40 && sizeof(y3_augment_mosaic) == 280 && sizeof(y3_augment_item) == 1360, "the records yolov3_amd/augment.py packs");
-
-extern "C" int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
-                                void* dst, int32_t dst_dtype, int32_t S, void* stream) {
-    if (!arena || !dst) Y3_FAIL("y3_augment_batch: null argument");
-    if (check_set("y3_augment_batch", images, n_images, items, count, S)) return -1;
-    if (arena_bytes < 4 || (arena_bytes & 3)) Y3_FAIL("y3_augment_batch: the arena's %lld bytes are not a positive multiple of 4", (long long)arena_bytes);
-    if (!aligned(arena, 16) || !aligned(dst, 16)) Y3_FAIL("y3_augment_batch: the arena and the output must be 16-byte aligned");
-    if (dst_dtype != Y3_U8 && dst_dtype != Y3_F16 && dst_dtype != Y3_BF16 && dst_dtype != Y3_F32) Y3_FAIL("y3_augment_batch: unsupported output dtype %d (uint8 / float16 / bfloat16 / float32)", dst_dtype);
+int launch_batch(const char* fn, const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                 void* dst, int32_t dst_dtype, int32_t H, int32_t W, void* stream) {
+    if (!arena || !dst) Y3_FAIL("%s: null argument", fn);
+    if (check_set(fn, images, n_images, items, count, H, W)) return -1;
+    if (arena_bytes < 4 || (arena_bytes & 3)) Y3_FAIL("%s: the arena's %lld bytes are not a positive multiple of 4", fn, (long long)arena_bytes);
+    if (!aligned(arena, 16) || !aligned(dst, 16)) Y3_FAIL("%s: the arena and the output must be 16-byte aligned", fn);
+    if (dst_dtype != Y3_U8 && dst_dtype != Y3_F16 && dst_dtype != Y3_BF16 && dst_dtype != Y3_F32) Y3_FAIL("%s: unsupported output dtype %d (uint8 / float16 / bfloat16 / float32)", fn, dst_dtype);
     if (count == 0) return 0;
     BatchArgs a;
     a.arena = arena; a.arena_bytes = arena_bytes; a.images = images; a.n_images = n_images; a.items = items; a.dst = dst;
-    a.count = count; a.S = S; a.pixels = S * S;
-    a.s_div = y3_make_divisor(S);
+    a.count = count; a.H = H; a.W = W; a.pixels = H * W;   // <= 2^24, a multiple of 256
+    a.w_div = y3_make_divisor(W);
     const dim3 grid((unsigned)((a.pixels + CHUNK - 1) / CHUNK), (unsigned)count);
     hipStream_t st = (hipStream_t)stream;
     switch (dst_dtype) {
@@ -567,33 +573,58 @@ extern "C" int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const
     return 0;
 }
 
-extern "C" int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
-                                  int32_t count, int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
-    if (!label_offsets || !offsets || (n_rows > 0 && (!labels || !targets))) Y3_FAIL("y3_augment_targets: null argument");
-    if (check_set("y3_augment_targets", images, n_images, items, count, S)) return -1;
-    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("y3_augment_targets: bad geometry (%lld rows)", (long long)n_rows);
-    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(labels, 4) || !aligned(targets, 4)) Y3_FAIL("y3_augment_targets: the offsets must be 8-byte, the fp32 tables 4-byte aligned");
+int launch_targets(const char* fn, const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                   int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
+    if (!label_offsets || !offsets || (n_rows > 0 && (!labels || !targets))) Y3_FAIL("%s: null argument", fn);
+    if (check_set(fn, images, n_images, items, count, H, W)) return -1;
+    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("%s: bad geometry (%lld rows)", fn, (long long)n_rows);
+    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(labels, 4) || !aligned(targets, 4)) Y3_FAIL("%s: the offsets must be 8-byte, the fp32 tables 4-byte aligned", fn);
     TargetArgs a;
     a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
-    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.S = S;
-    a.clip_s = (float)((double)S - 1e-3);
+    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = H; a.W = W;
+    a.clip_w = (float)((double)W - 1e-3);
+    a.clip_h = (float)((double)H - 1e-3);
     hipLaunchKernelGGL(augment_targets_kernel<false>, dim3(1), dim3(BT), 0, (hipStream_t)stream, a, PolyTables{});
     Y3_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+static_assert(sizeof(y3_augment_tile) == 40 && sizeof(y3_augment_mosaic) == 280 && sizeof(y3_augment_item) == 1360, "the records yolov3_amd/augment.py packs");
+
+extern "C" int y3_augment_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                                void* dst, int32_t dst_dtype, int32_t S, void* stream) {
+    return launch_batch("y3_augment_batch", arena, arena_bytes, images, n_images, items, count, dst, dst_dtype, S, S, stream);
+}
+
+extern "C" int y3_augment_batch_hw(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                                   void* dst, int32_t dst_dtype, int32_t H, int32_t W, void* stream) {
+    return launch_batch("y3_augment_batch_hw", arena, arena_bytes, images, n_images, items, count, dst, dst_dtype, H, W, stream);
+}
+
+extern "C" int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                  int32_t count, int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
+    return launch_targets("y3_augment_targets", labels, label_offsets, images, n_images, items, count, S, S, targets, n_rows, offsets, stream);
+}
+
+extern "C" int y3_augment_targets_hw(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                     int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
+    return launch_targets("y3_augment_targets_hw", labels, label_offsets, images, n_images, items, count, H, W, targets, n_rows, offsets, stream);
 }
 
 extern "C" int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
                                    const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
                                    int32_t* paths, int64_t n_rows, void* stream) {
     if (!vertex_offsets || !label_offsets || (count > 0 && !paths) || (n_vertices > 0 && !vertices) || (n_rows > 0 && (!boxes || !inside))) Y3_FAIL("y3_augment_polygons: null argument");
-    if (check_set("y3_augment_polygons", images, n_images, items, count, S)) return -1;
+    if (check_set("y3_augment_polygons", images, n_images, items, count, S, S)) return -1;
     if (n_vertices < 0 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL || n_rows < 0 || n_rows > 0x7fffffffLL / 6)
         Y3_FAIL("y3_augment_polygons: bad geometry (%lld vertices, %lld label rows, a workspace of %lld rows)", (long long)n_vertices, (long long)n_label_rows, (long long)n_rows);
     if (!aligned(vertex_offsets, 8) || !aligned(label_offsets, 8) || !aligned(boxes, 8) || !aligned(vertices, 4) || !aligned(inside, 4) || !aligned(paths, 4))
         Y3_FAIL("y3_augment_polygons: the offsets and the boxes must be 8-byte, the vertices and the int32 words 4-byte aligned");
     if (count == 0) return 0;
     TargetArgs a = {};
-    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.S = S;
+    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.H = S; a.W = S;
     PolyTables p = {};
     p.verts = vertices; p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
     p.boxes = boxes; p.inside = inside; p.paths = paths; p.ws_rows = n_rows;
@@ -606,14 +637,14 @@ extern "C" int y3_augment_targets_polygons(const float* labels, const int64_t* l
                                            int32_t count, int32_t S, const double* boxes, const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows,
                                            int64_t* offsets, void* stream) {
     if (!label_offsets || !offsets || (count > 0 && !paths) || (n_rows > 0 && (!labels || !targets || !boxes || !inside))) Y3_FAIL("y3_augment_targets_polygons: null argument");
-    if (check_set("y3_augment_targets_polygons", images, n_images, items, count, S)) return -1;
+    if (check_set("y3_augment_targets_polygons", images, n_images, items, count, S, S)) return -1;
     if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("y3_augment_targets_polygons: bad geometry (%lld rows)", (long long)n_rows);
     if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(boxes, 8) || !aligned(labels, 4) || !aligned(targets, 4) || !aligned(inside, 4) || !aligned(paths, 4))
         Y3_FAIL("y3_augment_targets_polygons: the offsets and the boxes must be 8-byte, the fp32 tables and the int32 words 4-byte aligned");
     TargetArgs a;
     a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
-    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.S = S;
-    a.clip_s = (float)((double)S - 1e-3);
+    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = S; a.W = S;
+    a.clip_w = a.clip_h = (float)((double)S - 1e-3);
     PolyTables p = {};
     p.boxes = const_cast<double*>(boxes); p.inside = const_cast<int*>(inside); p.paths = const_cast<int*>(paths); p.ws_rows = n_rows;
     hipLaunchKernelGGL(augment_targets_kernel<true>, dim3(1), dim3(BT), 0, (hipStream_t)stream, a, p);

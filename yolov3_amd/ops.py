@@ -1036,45 +1036,74 @@ def _augment_args(what: str, images: torch.Tensor, n: int, items: torch.Tensor, 
         raise ValueError(f"{what}: the image size {size} is not a multiple of 16")
 
 
+def _augment_batch(what: str, arena, images, n, items, count, height, width, dtype, out):
+    """augment_batch / augment_batch_hw: the square export for the one, the (H, W) export for the other"""
+    require_gpu(arena, what)
+    for side in dict.fromkeys((height, width)):
+        _augment_args(what, images, n, items, count, side)
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous uint8 arena of the set")
+    if dtype not in DTYPE_CODE:
+        raise TypeError(f"{what} writes uint8 / float16 / bfloat16 / float32, not {dtype}")
+    shape = (int(count), 3, int(height), int(width))
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=arena.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
+        raise TypeError(f"{what}: `out` must be a contiguous {shape} {dtype} tensor on {arena.device}")
+    if count:
+        head = (arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), items.data_ptr(), int(count), out.data_ptr(), DTYPE_CODE[dtype])
+        if what == "augment_batch":
+            check(_lib.lib().y3_augment_batch(*head, int(height), stream_ptr()), "y3_augment_batch")
+        else:
+            check(_lib.lib().y3_augment_batch_hw(*head, int(height), int(width), stream_ptr()), "y3_augment_batch_hw")
+    return out
+
+
 def augment_batch(arena: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int, dtype: torch.dtype = torch.uint8,
                   out: torch.Tensor | None = None) -> torch.Tensor:
     """One augmented batch of a device-resident dataset in one launch (y3_augment_batch): `arena` / `images` as for dataset_batch, `items` the batch's
     y3_augment_item records as bytes (1360 each, what augment.pack_items forms) -> (count, 3, size, size) in `dtype`: mosaic, affine warp, mixup, HSV and the flips
     applied, CHW, RGB.  `out`: a contiguous, 16-byte aligned tensor of that shape and dtype to write into."""
-    what = "augment_batch"
-    require_gpu(arena, what)
-    _augment_args(what, images, n, items, count, size)
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
-        raise TypeError("augment_batch expects the contiguous uint8 arena of the set")
-    if dtype not in DTYPE_CODE:
-        raise TypeError(f"augment_batch writes uint8 / float16 / bfloat16 / float32, not {dtype}")
-    shape = (int(count), 3, int(size), int(size))
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=arena.device)
-    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
-        raise TypeError(f"augment_batch: `out` must be a contiguous {shape} {dtype} tensor on {arena.device}")
-    if count:
-        check(_lib.lib().y3_augment_batch(arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), items.data_ptr(), int(count), out.data_ptr(), DTYPE_CODE[dtype], int(size),
-                                          stream_ptr()), "y3_augment_batch")
-    return out
+    return _augment_batch("augment_batch", arena, images, n, items, count, size, size, dtype, out)
+
+
+def augment_batch_hw(arena: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, height: int, width: int, dtype: torch.dtype = torch.uint8,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """augment_batch for items of `height` rows and `width` columns, the batch shape of a rect=True set (y3_augment_batch_hw; both multiples of 16) ->
+    (count, 3, height, width) in `dtype`."""
+    return _augment_batch("augment_batch_hw", arena, images, n, items, count, height, width, dtype, out)
+
+
+def _augment_targets(what: str, labels, label_offsets, images, n, items, count, height, width, n_rows):
+    """augment_targets / augment_targets_hw: the square export for the one, the (H, W) export for the other"""
+    require_gpu(labels, what)
+    require_gpu(label_offsets, what)
+    for side in dict.fromkeys((height, width)):
+        _augment_args(what, images, n, items, count, side)
+    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous fp32 (total, 5) label table")
+    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
+        raise TypeError(f"{what} expects {n + 1} contiguous int64 label offsets")
+    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
+    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
+    head = (labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count))
+    tail = (targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr())
+    if what == "augment_targets":
+        check(_lib.lib().y3_augment_targets(*head, int(height), *tail), "y3_augment_targets")
+    else:
+        check(_lib.lib().y3_augment_targets_hw(*head, int(height), int(width), *tail), "y3_augment_targets_hw")
+    return targets, offsets
 
 
 def augment_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int, n_rows: int):
     """The targets of one augmented batch (y3_augment_targets): `n_rows` the label count of all tiles of the batch, an upper bound of the survivors ->
     (DEVICE fp32 (n_rows, 6) [item in batch, cls, x, y, w, h], DEVICE int64 (count + 1,) offsets); only the first offsets[count] rows are written."""
-    what = "augment_targets"
-    require_gpu(labels, what)
-    require_gpu(label_offsets, what)
-    _augment_args(what, images, n, items, count, size)
-    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
-        raise TypeError("augment_targets expects the contiguous fp32 (total, 5) label table")
-    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
-        raise TypeError(f"augment_targets expects {n + 1} contiguous int64 label offsets")
-    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
-    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
-    check(_lib.lib().y3_augment_targets(labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count), int(size),
-                                        targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr()), "y3_augment_targets")
-    return targets, offsets
+    return _augment_targets("augment_targets", labels, label_offsets, images, n, items, count, size, size, n_rows)
+
+
+def augment_targets_hw(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, height: int, width: int, n_rows: int):
+    """augment_targets for items of `height` rows and `width` columns (y3_augment_targets_hw): the boxes are clipped and normalised per axis."""
+    return _augment_targets("augment_targets_hw", labels, label_offsets, images, n, items, count, height, width, n_rows)
 
 
 def augment_polygons(vertices: torch.Tensor, vertex_offsets: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int,
