@@ -210,8 +210,9 @@ typedef struct {
 /* capacity = candidate slots for the whole batch; <= 0 picks the default (bs*16384, clamped to the
  * worst case bs*n_rows*nc).  Pass the same capacity to both calls. */
 size_t y3_nms_workspace_bytes(int32_t bs, int32_t n_rows, int32_t nc, const y3_nms_params* p, int64_t capacity);
-/* out_status (device, 2 x int32): [0] = 1 if the candidate capacity overflowed (results invalid: call
- * again with a workspace sized for capacity >= out_status[1]); [1] = total candidates found. */
+/* out_status (device, 2 x int32): [0] bit 0 = 1 if the candidate capacity overflowed (results invalid: call
+ * again with a workspace sized for capacity >= out_status[1]), the bits above it = the number of images that took
+ * the second round (knob nms_head; diagnostics); [1] = total candidates found. */
 int y3_nms(const void* pred, int32_t dtype, int32_t bs, int32_t n_rows, int32_t nc, const y3_nms_params* p,
            const int32_t* classes, float* out_rows, int32_t* out_counts, int32_t* out_status, int64_t capacity,
            void* workspace, size_t workspace_bytes, void* stream);

@@ -15,6 +15,8 @@
 //              inter/(a_i+a_j-inter) > thr (strict, compared in double like torchvision's CPU kernel);
 //              IoU rows are evaluated lazily for kept boxes only; stop after max_det kept per segment.
 //   6 gather   block per image: kept flags back in score order, first max_det rows -> (bs, max_det, 6) fp32.
+//   Steps 4-5 run head first (knob nms_head): a first round over the head of every image's score ranks, a second over the full range of the images whose head kept
+//   fewer than max_det boxes (nms_sort_kernel).
 #include "y3_common.h"
 
 #include <rocprim/rocprim.hpp>
@@ -289,8 +291,11 @@ constexpr unsigned long long KEY_UNUSED = ~0ull;
 struct NmsWs {  // device pointers carved from the caller's workspace
     int* row_count;                // bs*n_rows (+1)
     int* row_off;                  // bs*n_rows + 1 (exclusive scan, last = total)
-    unsigned* img_maxabs;          // bs  (float bits of max |coord| among the image's candidates)
+    // control words: ONE block behind row_count[scan_n], cleared by one fill per call (carve)
+    unsigned* img_maxabs;          // bs * 64: float bits of max |coord| among the image's candidates, spread over 64 slots by wave id like img_total (emit pass; img_max_coord reduces them)
     unsigned* img_total;           // bs * 64: candidates of the image, spread over 64 slots by wave id (count pass; own scan) -- one slot per image serialised 1575 atomics on one address
+    unsigned* img_head;            // bs: score ranks that round 1 prepared and suppressed (knob nms_head)
+    unsigned* img_kept;            // bs: boxes kept by round 1, summed over the image's segments
     unsigned long long* key_a;     // cap
     unsigned long long* key_b;     // cap
     unsigned* val_a;               // cap
@@ -505,8 +510,20 @@ __global__ __launch_bounds__(256) void nms_candidates_kernel(const T* __restrict
             if (lane == 0 && t > 0) atomicAdd(&ws.img_total[img * 64 + (int)(wave_id & 63)], (unsigned)t);
         }
     } else {
-        if (lane == 0 && maxabs > 0.0f) atomicMax(&ws.img_maxabs[img], __float_as_uint(maxabs));
+        // (non-negative floats and +inf order like their bits; one word per image put every wave's atomic of the batch -- bs words = one 128-byte line -- on the same line)
+        if (lane == 0 && maxabs > 0.0f) atomicMax(&ws.img_maxabs[img * 64 + (int)(wave_id & 63)], __float_as_uint(maxabs));
     }
+}
+
+// max |coord| among the image's candidates: the maximum of the 64 slots the emit pass spread it over (any order: the same bits).  Whole wave; every lane gets the value.
+Y3_DEV float img_max_coord(const NmsWs& ws, int img) {
+    unsigned m = ws.img_maxabs[img * 64 + (threadIdx.x & 63)];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    return __uint_as_float(m);
 }
 
 // exclusive scan of the per-row label counts -> emission slots (round 6; rounds 1-5: rocprim::exclusive_scan, two launches).  One block per image: the image's first
@@ -585,7 +602,9 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(NmsWs ws, int bs, int n_r
             const unsigned g = idx1[i];
             const int cls = ws.ccls[g];
             const float4 b = ws.cbox[g];
-            const bool part = !agnostic && (__uint_as_float(ws.img_maxabs[img]) < max_wh * 0.5f);
+            unsigned mx = 0u;   // (divergent here: every thread reduces the image's 64 slots itself)
+            for (int s = 0; s < 64; ++s) mx = ws.img_maxabs[img * 64 + s] > mx ? ws.img_maxabs[img * 64 + s] : mx;
+            const bool part = !agnostic && (__uint_as_float(mx) < max_wh * 0.5f);
             const float c = (float)cls * (agnostic ? 0.0f : max_wh);  // x[:, 5:6] * (0 if agnostic else max_wh)  (:731)
             ws.sbox[i] = make_float4(b.x + c, b.y + c, b.z + c, b.w + c);
             const unsigned seg = part ? (unsigned)cls : 0u;
@@ -614,11 +633,13 @@ constexpr int SORT_WAVES = 16, SORT_NB = 512;
 struct SortLds {
     unsigned hist[SORT_WAVES * SORT_NB];   // [wave][digit]: counts (A), then the wave's running offset inside the digit (B, C)
     unsigned tot[SORT_NB];                 // per digit: count, then the digit's first slot
+    unsigned cut[3];                       // head_cutoff: the cutoff digit, the number of members at or below it, the number below it
 };
 Y3_DEV unsigned ld_l2(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <typename Load, typename Digit, typename Put>
-Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, Digit digit, Put put) {
+// `member` (of the key) filters the pass: an element that fails it is neither counted nor put anywhere (the head-first score ordering scatters only the head's candidates)
+template <typename Load, typename Digit, typename Put, typename Member>
+Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, Digit digit, Put put, Member member) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int nb = 1 << bits;
     for (int i = tid; i < SORT_WAVES * nb; i += SORT_WAVES * 64) L.hist[(i >> bits) * SORT_NB + (i & (nb - 1))] = 0u;
@@ -636,7 +657,7 @@ Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int r = c0 + 64 * u + lane;
-            if (r < hi) atomicAdd(&L.hist[wv * SORT_NB + digit(e[u].x)], 1u);
+            if (r < hi && member(e[u].x)) atomicAdd(&L.hist[wv * SORT_NB + digit(e[u].x)], 1u);
         }
     }
     __syncthreads();
@@ -689,7 +710,7 @@ Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, 
         for (int u = 0; u < 4; ++u) {
             if (c0 + 64 * u >= hi) break;   // (uniform)
             const int r = c0 + 64 * u + lane;
-            const bool valid = r < hi;
+            const bool valid = r < hi && member(e[u].x);
             const unsigned d = digit(e[u].x);
             unsigned long long peers = __ballot(valid);
             for (int b = 0; b < bits; ++b) {
@@ -706,18 +727,91 @@ Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, 
     }
     __syncthreads();   // the slots are written (workgroup scope); L is free
 }
+template <typename Load, typename Digit, typename Put>
+Y3_DEV void counting_pass(SortLds& L, const int cnt, const int bits, Load load, Digit digit, Put put) {
+    counting_pass(L, cnt, bits, load, digit, put, [](unsigned) { return true; });
+}
 
+// The histogram phase alone, over one digit of the elements that pass `member`: the smallest digit `cut` whose cumulative count (digits 0 .. cut) reaches `want`
+// -> L.cut[0], that count -> L.cut[1], the count below the digit -> L.cut[2].  Needs want >= 1 and at least `want` members.  Over the MOST significant digit the
+// elements at or below the cutoff are the first L.cut[1] of the full ordering, whatever their lower digits are; a second call over the next digit, of the members
+// that hold the cutoff digit, narrows them down the same way.
+template <typename Load, typename Digit, typename Member>
+Y3_DEV void head_cutoff(SortLds& L, const int cnt, const int bits, const unsigned want, Load load, Digit digit, Member member) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nb = 1 << bits;
+    for (int i = tid; i < nb; i += SORT_WAVES * 64) L.tot[i] = 0u;
+    __syncthreads();
+    for (int c0 = 0; c0 < cnt; c0 += SORT_WAVES * 64 * 4) {
+        uint2 e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = c0 + SORT_WAVES * 64 * u + tid;
+            e[u] = load(r < cnt ? r : 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (c0 + SORT_WAVES * 64 * u + tid < cnt && member(e[u].x)) atomicAdd(&L.tot[digit(e[u].x)], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {   // inclusive prefix of the digit totals: 8 consecutive digits per lane
+        unsigned v[SORT_NB / 64], sum = 0;
+#pragma unroll
+        for (int k = 0; k < SORT_NB / 64; ++k) {
+            const int d = lane * (SORT_NB / 64) + k;
+            v[k] = d < nb ? L.tot[d] : 0u;
+            sum += v[k];
+        }
+        unsigned inc = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        unsigned run = inc - sum;
+#pragma unroll
+        for (int k = 0; k < SORT_NB / 64; ++k) {
+            if (run < want && run + v[k] >= want) {   // (exactly one digit: the prefix is monotone and ends at the members' count >= want)
+                L.cut[0] = (unsigned)(lane * (SORT_NB / 64) + k);
+                L.cut[1] = run + v[k];
+                L.cut[2] = run;
+            }
+            run += v[k];
+        }
+    }
+    __syncthreads();
+}
+
+//
+// Head first (knob nms_head; `round` 1 and 2, 0 = the single full round).  The output is the first max_det kept boxes in score order, and a box's fate depends only on
+// boxes of its own segment that rank above it.  Round 1 therefore orders, prepares and suppresses only a HEAD of the image's score ranks:
+//   * head > 0: the histogram of the MOST significant score digit gives the smallest digit cutoff whose cumulative count reaches `head`, a second histogram over the
+//     next digit, of the candidates that hold the cutoff digit, the cutoff inside it (head_cutoff).  The candidates S at or above the two cutoffs are the first |S|
+//     ranks of the full ordering whatever their lower bits are, so the usual LSD passes run over S only (the first of them reads every candidate and scatters the
+//     members; it is stable, so ties keep nonzero order).  The head is the first min(|S|, max_nms, head) ranks.  (The benchmark model's scores share the top digit
+//     -- exponent and one mantissa bit of an f16 --: with that digit alone S was the whole image, and a head of all of S the whole range.)
+//   * head < 0: the full score ordering, the head is min(cnt, max_nms, -head) ranks (A/B of the step above).
+// The class pass, the class-offset boxes and the cleared keep flags cover the head only; img_head[img] = its size.  nms_greedy_kernel (round 1) suppresses inside the
+// head and adds every segment's kept count to img_kept[img].  The kept flags of the head's ranks are the full run's flags (same boxes, same order, same test; a
+// segment stops at max_det kept exactly where the full run stops), so img_kept >= max_det means the first max_det kept rows lie in the head and are the full run's.
+// Round 2 is always launched -- no host decision, no block waits for another: the blocks of an image whose round 1 settled the answer (img_kept >= max_det, or the
+// head was the whole range) return at once, the others redo ordering, preparation and suppression over the full range from scratch, which is the single-round path.
 __global__ __launch_bounds__(SORT_WAVES * 64) void nms_sort_kernel(NmsWs ws, int bs, int n_rows, int max_nms, float max_wh, int agnostic, int nseg, int sbit0, int sbits,
-                                                                     int n_sp, int* __restrict__ status) {
+                                                                     int n_sp, int head, int round, int max_det, int* __restrict__ status) {
     __shared__ SortLds L;
     const int img = blockIdx.x, tid = threadIdx.x;
     const long long total = ws.row_off[(long long)bs * n_rows];
-    if (img == 0 && tid == 0) status[1] = (int)(total > 0x7fffffffLL ? 0x7fffffff : total);
+    if (img == 0 && tid == 0 && round < 2) status[1] = (int)(total > 0x7fffffffLL ? 0x7fffffff : total);
     const long long start = ws.row_off[(long long)img * n_rows];
     long long cnt_ll = (long long)ws.row_off[(long long)(img + 1) * n_rows] - start;
     if (start + cnt_ll > ws.cap) cnt_ll = ws.cap - start > 0 ? ws.cap - start : 0;   // (overflow: status[0] is set by the emit pass, the caller grows the workspace)
     const int cnt = (int)cnt_ll;
     if (cnt <= 0) return;   // (uniform)
+    const int cntm = cnt < max_nms ? cnt : max_nms;
+    if (round == 2) {
+        if (ws.img_kept[img] >= (unsigned)max_det || (int)ws.img_head[img] == cntm) return;   // (uniform) round 1 settled this image
+        if (tid == 0) atomicAdd(&status[0], 2);   // images that took round 2, above the overflow bit (diagnostics; the tests assert that the fallback runs)
+    }
     // scratch, 32-bit views: key_a = X0 | X1, key_b = X2 | X3, key_c = X4 (the segment id per slot of the final order) | X5
     unsigned* const X0 = (unsigned*)ws.key_a + start, * const X1 = (unsigned*)ws.key_a + ws.cap + start;
     unsigned* const X2 = (unsigned*)ws.key_b + start, * const X3 = (unsigned*)ws.key_b + ws.cap + start;
@@ -727,6 +821,26 @@ __global__ __launch_bounds__(SORT_WAVES * 64) void nms_sort_kernel(NmsWs ws, int
 
     // ---- per-image descending-score order (ties keep nonzero order): VB[rank] = candidate slot
     const unsigned dmask = (1u << sbits) - 1u;
+    const int top = sbit0 + (n_sp - 1) * sbits;   // the most significant digit
+    auto fresh = [&](int r) { return make_uint2(~__float_as_uint(score[r]), (unsigned)(start + r)); };
+    // the candidates S that take part: all of them, or round 1's head -- top digit below cut1, or equal to it with the next digit <= cut2 (two histogram phases: the
+    // top digit alone is the exponent and one mantissa bit of an f16 score, and a head whose scores share it would be the whole image)
+    unsigned cut1 = dmask, cut2 = dmask;
+    int ns = cnt;
+    auto top_of = [&](unsigned k) { return (k >> top) & dmask; };
+    auto next_of = [&](unsigned k) { return (k >> (top - sbits)) & dmask; };
+    if (round == 1 && head > 0 && cnt > head) {
+        head_cutoff(L, cnt, sbits, (unsigned)head, fresh, top_of, [](unsigned) { return true; });
+        cut1 = L.cut[0];
+        const unsigned below = L.cut[2];
+        head_cutoff(L, cnt, sbits, (unsigned)head - below, fresh, next_of, [&](unsigned k) { return top_of(k) == cut1; });
+        cut2 = L.cut[0];
+        ns = (int)(below + L.cut[1]);
+    }
+    auto in_head = [&](unsigned k) {
+        const unsigned t = top_of(k);
+        return t < cut1 || (t == cut1 && next_of(k) <= cut2);
+    };
     for (int p = 0; p < n_sp; ++p) {
         const int shift = sbit0 + p * sbits;
         const bool last = p == n_sp - 1;
@@ -735,19 +849,24 @@ __global__ __launch_bounds__(SORT_WAVES * 64) void nms_sort_kernel(NmsWs ws, int
         unsigned* kout = p == 0 ? X0 : p == 1 ? X2 : X5;
         unsigned* vout = last ? VB : p == 0 ? X1 : p == 1 ? X3 : VA;
         counting_pass(
-            L, cnt, sbits,
-            [&](int r) { return p == 0 ? make_uint2(~__float_as_uint(score[r]), (unsigned)(start + r)) : make_uint2(ld_l2(kin + r), ld_l2(vin + r)); },
+            L, p == 0 ? cnt : ns, sbits, [&](int r) { return p == 0 ? fresh(r) : make_uint2(ld_l2(kin + r), ld_l2(vin + r)); },
             [&](unsigned k) { return (k >> shift) & dmask; },
             [&](unsigned pos, unsigned k, unsigned v) {
                 if (!last) kout[pos] = k;
                 vout[pos] = v;
-            });
+            },
+            in_head);
     }
 
-    // ---- the first max_nms of the image: class-offset boxes in score order, keep flags (nms_rank_kernel), then per-(image, segment) runs in score order
-    const int cntm = cnt < max_nms ? cnt : max_nms;
-    const bool part = !agnostic && nseg > 1 && (__uint_as_float(ws.img_maxabs[img]) < max_wh * 0.5f);
-    for (int r = tid; r < cntm; r += SORT_WAVES * 64) {
+    // ---- the first max_nms of the image (round 1: of its head): class-offset boxes in score order, keep flags (nms_rank_kernel), then per-(image, segment) runs in score order
+    int prep = ns < max_nms ? ns : max_nms;
+    if (round == 1) {
+        const int h = head < 0 ? -head : head;   // S ends with whole digit classes: the head is cut at the knob's ranks
+        if (prep > h) prep = h;
+        if (tid == 0) ws.img_head[img] = (unsigned)prep;
+    }
+    const bool part = !agnostic && nseg > 1 && (img_max_coord(ws, img) < max_wh * 0.5f);
+    for (int r = tid; r < prep; r += SORT_WAVES * 64) {
         const unsigned g = ld_l2(VB + r);
         const float4 b = ws.cbox[g];
         const float c = (float)ws.ccls[g] * (agnostic ? 0.0f : max_wh);   // x[:, 5:6] * (0 if agnostic else max_wh)  (:731)
@@ -760,11 +879,11 @@ __global__ __launch_bounds__(SORT_WAVES * 64) void nms_sort_kernel(NmsWs ws, int
     while ((1 << cbits) < nseg) ++cbits;
     auto seg_of = [&](int r) { return make_uint2((unsigned)ws.ccls[ld_l2(VB + r)], (unsigned)(start + r)); };
     if (cbits <= 9) {
-        counting_pass(L, cntm, cbits, seg_of, [&](unsigned k) { return k; }, [&](unsigned pos, unsigned k, unsigned v) { X4[pos] = k; VC[pos] = v; });
+        counting_pass(L, prep, cbits, seg_of, [&](unsigned k) { return k; }, [&](unsigned pos, unsigned k, unsigned v) { X4[pos] = k; VC[pos] = v; });
     } else {
-        counting_pass(L, cntm, 9, seg_of, [&](unsigned k) { return k & 511u; }, [&](unsigned pos, unsigned k, unsigned v) { X0[pos] = k; X1[pos] = v; });
+        counting_pass(L, prep, 9, seg_of, [&](unsigned k) { return k & 511u; }, [&](unsigned pos, unsigned k, unsigned v) { X0[pos] = k; X1[pos] = v; });
         counting_pass(
-            L, cntm, cbits - 9, [&](int r) { return make_uint2(ld_l2(X0 + r), ld_l2(X1 + r)); }, [&](unsigned k) { return k >> 9; },
+            L, prep, cbits - 9, [&](int r) { return make_uint2(ld_l2(X0 + r), ld_l2(X1 + r)); }, [&](unsigned k) { return k >> 9; },
             [&](unsigned pos, unsigned k, unsigned v) { X4[pos] = k; VC[pos] = v; });
     }
 }
@@ -800,7 +919,7 @@ Y3_DEV long long lower_bound_u32(const unsigned* __restrict__ a, long long n, un
 // The same IoU expression on the same operands decides every bit (inter / (area_i + area_j - inter) as a float, compared with the double threshold), so the
 // kept set is the loop's, bit for bit; four barriers per 64 boxes instead of three per kept box.
 __global__ __launch_bounds__(256) void nms_greedy_kernel(NmsWs ws, int nseg, double iou_thr, int max_det, int max_nms, const unsigned long long* __restrict__ key2,
-                                                          const unsigned* __restrict__ pos2, const unsigned* __restrict__ seg_sorted, int n_rows) {
+                                                          const unsigned* __restrict__ pos2, const unsigned* __restrict__ seg_sorted, int n_rows, int round) {
     __shared__ unsigned removed[(1 << RANK_BITS) / 32];  // 32768 bits = 4 KiB
     __shared__ float4 blk[64];                            // the current block's boxes
     __shared__ unsigned long long srow[64];               // their suppression rows inside the block
@@ -813,6 +932,8 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(NmsWs ws, int nseg, dou
         long long cnt = (long long)ws.row_off[(long long)(img + 1) * n_rows] - start;
         if (start + cnt > ws.cap) cnt = ws.cap - start > 0 ? ws.cap - start : 0;
         if (cnt > max_nms) cnt = max_nms;
+        if (round == 1) cnt = ws.img_head[img];   // (nms_sort_kernel: the head's ranks only)
+        else if (round == 2 && (ws.img_kept[img] >= (unsigned)max_det || (long long)ws.img_head[img] == cnt)) return;   // (uniform) round 1 settled this image
         lo = start + lower_bound_u32(seg_sorted + start, cnt, (unsigned)seg);
         hi = start + lower_bound_u32(seg_sorted + start, cnt, (unsigned)seg + 1u);
     } else {
@@ -894,11 +1015,13 @@ __global__ __launch_bounds__(256) void nms_greedy_kernel(NmsWs ws, int nseg, dou
                 }
             }
     }
+    // round 1: the segment's kept boxes towards the image's total (thread 0 wrote s_kept itself; integer adds: any order, same sum)
+    if (round == 1 && tid == 0 && s_kept > 0) atomicAdd(&ws.img_kept[img], (unsigned)s_kept);
 }
 
 // per image: kept candidates in descending-score order, first max_det -> out rows
 __global__ __launch_bounds__(256) void nms_gather_kernel(NmsWs ws, int n_rows, int max_det, int max_nms, const unsigned* __restrict__ idx1,
-                                                          float* __restrict__ out_rows, int* __restrict__ out_counts) {
+                                                          float* __restrict__ out_rows, int* __restrict__ out_counts, int rounds) {
     __shared__ int wave_cnt[4];
     __shared__ int s_base;
     const int img = blockIdx.x;
@@ -906,6 +1029,7 @@ __global__ __launch_bounds__(256) void nms_gather_kernel(NmsWs ws, int n_rows, i
     long long cnt = (long long)ws.row_off[(long long)(img + 1) * n_rows] - start;
     if (start + cnt > ws.cap) cnt = ws.cap - start > 0 ? ws.cap - start : 0;
     if (cnt > max_nms) cnt = max_nms;
+    if (rounds == 2 && ws.img_kept[img] >= (unsigned)max_det) cnt = ws.img_head[img];   // the range that was finally covered: round 1's head, or round 2's full range
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) s_base = 0;
     __syncthreads();
@@ -955,6 +1079,8 @@ size_t temp_bytes(long long cap, size_t scan_n) {
     return align_up(a > b ? a : b);
 }
 
+size_t ctrl_words(int bs) { return 1 + (size_t)(64 + 64 + 1 + 1) * bs; }   // row_count[scan_n], img_maxabs, img_total, img_head, img_kept
+
 size_t carve(NmsWs& ws, unsigned char* base, int bs, long long cap, size_t scan_n) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -963,10 +1089,13 @@ size_t carve(NmsWs& ws, unsigned char* base, int bs, long long cap, size_t scan_
         return p;
     };
     ws.cap = cap;
-    ws.row_count = (int*)take((scan_n + 1) * sizeof(int));
+    // row_count, its closing word row_count[scan_n] and the control words behind it: [scan_n, scan_n + ctrl_words(bs)) is what a call clears
+    ws.row_count = (int*)take((scan_n + ctrl_words(bs)) * sizeof(int));
+    ws.img_maxabs = ws.row_count ? (unsigned*)ws.row_count + scan_n + 1 : nullptr;
+    ws.img_total = ws.img_maxabs ? ws.img_maxabs + (size_t)64 * bs : nullptr;
+    ws.img_head = ws.img_maxabs ? ws.img_total + (size_t)64 * bs : nullptr;
+    ws.img_kept = ws.img_maxabs ? ws.img_head + bs : nullptr;
     ws.row_off = (int*)take((scan_n + 1) * sizeof(int));
-    ws.img_maxabs = (unsigned*)take((size_t)65 * bs * sizeof(unsigned));
-    ws.img_total = ws.img_maxabs ? ws.img_maxabs + bs : nullptr;
     ws.key_a = (unsigned long long*)take((size_t)cap * 8);
     ws.key_b = (unsigned long long*)take((size_t)cap * 8);
     ws.key_c = (unsigned long long*)take((size_t)cap * 8);
@@ -1007,10 +1136,9 @@ int run_nms(const void* pred, int bs, int n_rows, int nc, const y3_nms_params* p
     const int nseg = one_seg ? 1 : nc;
 
     Y3_HIP(hipMemsetAsync(out_status, 0, 2 * sizeof(int), st));
-    Y3_HIP(hipMemsetAsync(ws.img_maxabs, 0, (size_t)65 * bs * sizeof(unsigned), st));   // (+ img_total)
+    Y3_HIP(hipMemsetAsync(ws.row_count + scan_n, 0, ctrl_words(bs) * sizeof(int), st));   // row_count[scan_n] and every control word: one fill
     ws.own_sort = y3_knob(Y3K_NMS_SORT) != 0 ? 1 : 0;
     if (!ws.own_sort) Y3_HIP(hipMemsetAsync(ws.key_a, 0xff, (size_t)cap * 8, st));
-    Y3_HIP(hipMemsetAsync(ws.row_count + scan_n, 0, sizeof(int), st));
 
     const long long waves = (long long)bs * ((n_rows + 63) / 64);
     const unsigned cblocks = (unsigned)((waves + 3) / 4);
@@ -1026,13 +1154,19 @@ int run_nms(const void* pred, int bs, int n_rows, int nc, const y3_nms_params* p
     if (ws.own_sort) {
         // conf is a value of T: below the sign an f16 / bf16 value has 18 bits that can differ (fp32 bits 13 .. 30), an fp32 value all of them
         const bool narrow = sizeof(T) == 2;
-        hipLaunchKernelGGL(nms_sort_kernel, dim3((unsigned)bs), dim3(SORT_WAVES * 64), 0, st, ws, bs, n_rows, p->max_nms, p->max_wh, p->agnostic, nseg, narrow ? 13 : 0,
-                           narrow ? 9 : 8, narrow ? 2 : 4, out_status);
-        Y3_CHECK_LAUNCH();
-        hipLaunchKernelGGL(nms_greedy_kernel, dim3((unsigned)(bs * nseg)), dim3(256), 0, st, ws, nseg, p->iou_thres, p->max_det, p->max_nms,
-                           (const unsigned long long*)nullptr, ws.val_c, (const unsigned*)ws.key_c, n_rows);
-        Y3_CHECK_LAUNCH();
-        hipLaunchKernelGGL(nms_gather_kernel, dim3((unsigned)bs), dim3(256), 0, st, ws, n_rows, p->max_det, p->max_nms, ws.val_b, out_rows, out_counts);
+        long long head = y3_knob(Y3K_NMS_HEAD);   // 0: one full round; otherwise round 1 over the head, round 2 over the rest of the images that need it (nms_sort_kernel)
+        if (head > (1 << RANK_BITS)) head = 1 << RANK_BITS;   // (max_nms is below that: such a head is the whole range)
+        if (head < -(1 << RANK_BITS)) head = -(1 << RANK_BITS);
+        const int rounds = head != 0 ? 2 : 1;
+        for (int r = rounds == 2 ? 1 : 0; r <= (rounds == 2 ? 2 : 0); ++r) {
+            hipLaunchKernelGGL(nms_sort_kernel, dim3((unsigned)bs), dim3(SORT_WAVES * 64), 0, st, ws, bs, n_rows, p->max_nms, p->max_wh, p->agnostic, nseg,
+                               narrow ? 13 : 0, narrow ? 9 : 8, narrow ? 2 : 4, (int)head, r, p->max_det, out_status);
+            Y3_CHECK_LAUNCH();
+            hipLaunchKernelGGL(nms_greedy_kernel, dim3((unsigned)(bs * nseg)), dim3(256), 0, st, ws, nseg, p->iou_thres, p->max_det, p->max_nms,
+                               (const unsigned long long*)nullptr, ws.val_c, (const unsigned*)ws.key_c, n_rows, r);
+            Y3_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(nms_gather_kernel, dim3((unsigned)bs), dim3(256), 0, st, ws, n_rows, p->max_det, p->max_nms, ws.val_b, out_rows, out_counts, rounds);
         Y3_CHECK_LAUNCH();
         return 0;
     }
@@ -1047,9 +1181,9 @@ int run_nms(const void* pred, int bs, int n_rows, int nc, const y3_nms_params* p
     if (rocprim::radix_sort_pairs(ws.tmp, tb, ws.key_a, ws.key_c, ws.val_a, ws.val_c, (size_t)cap, 0u, (unsigned)(IMG_BITS + CLS_BITS + RANK_BITS), st) != hipSuccess)
         Y3_FAIL("y3_nms: sort-2 failed");
     hipLaunchKernelGGL(nms_greedy_kernel, dim3((unsigned)(bs * nseg)), dim3(256), 0, st, ws, nseg, p->iou_thres, p->max_det, p->max_nms, ws.key_c, ws.val_c,
-                       (const unsigned*)nullptr, n_rows);
+                       (const unsigned*)nullptr, n_rows, 0);
     Y3_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nms_gather_kernel, dim3((unsigned)bs), dim3(256), 0, st, ws, n_rows, p->max_det, p->max_nms, ws.val_b, out_rows, out_counts);
+    hipLaunchKernelGGL(nms_gather_kernel, dim3((unsigned)bs), dim3(256), 0, st, ws, n_rows, p->max_det, p->max_nms, ws.val_b, out_rows, out_counts, 1);
     Y3_CHECK_LAUNCH();
     return 0;
 }

@@ -26,6 +26,11 @@ enum y3_knob_id {
     Y3K_DECODE_TILE,    // "decode_tile": 1 the Detect decode of the 2-byte types by the tiled kernel (detect_nms.hip::decode_tile_kernel: 16-byte loads and stores, layout change through LDS, all levels of
                         //                y3_detect_decode_levels in one launch), sigmoid from the 64 Ki-entry table in LDS when the launch is large enough to pay for loading it; 0 decode_vec_kernel / decode_kernel per
                         //                level (the path before the tiled kernel: A/B, cross-check in the tests); 2 / 3 / 4 tiled with the sigmoid always from the LDS table / always computed / from the table in global memory
+    Y3K_NMS_HEAD,       // "nms_head":    N > 0 y3_nms (nms_sort = 1) orders, prepares and suppresses only a head of every image's score ranks first -- the first N ranks, ordered among the candidates at or above
+                        //                the smallest cutoff of the two most significant score digits that N of them reach -- and redoes the images that kept fewer than max_det boxes there over their full range in a
+                        //                second round (exact: detect_nms.hip::nms_sort_kernel); 0 one full round (the path before; A/B, cross-check in the tests); N < 0 the first -N ranks of the FULL score ordering (A/B of
+                        //                the head-first ordering).  The default is 4 x val.py's max_det, rounded up to whole groups of 64: the smallest of 4 / 8 / 16 x at which no image of the benchmark's
+                        //                loads needs the second round (profiles/nms_head_kernel_stats.md); results do not depend on N
     Y3K_COUNT
 };
 long long y3_knob(int id);

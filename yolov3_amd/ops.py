@@ -480,7 +480,8 @@ def nms_raw(pred: torch.Tensor, conf_thres: float, iou_thres: float, classes, ag
         )
         m = meta.tolist()  # the single device->host sync of the call
         nms_raw.last_candidates = m[bs + 1]   # candidates (rows above conf_thres, one per class under multi_label) of the whole batch: bench.py reports it
-        if m[bs] == 0:
+        nms_raw.last_round2 = m[bs] >> 1     # images that took the second round (knob nms_head): above the overflow bit of the status word
+        if (m[bs] & 1) == 0:
             return rows, m[:bs]
         capacity = max(m[bs + 1], 1)  # overflow: rerun with room for every candidate
     raise _lib.Y3Error("y3_nms: candidate capacity overflow persisted")
