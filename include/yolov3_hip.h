@@ -478,6 +478,36 @@ int y3_augment_targets_polygons(const float* labels, const int64_t* label_offset
                                 int32_t count, int32_t S, const double* boxes, const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows,
                                 int64_t* offsets, void* stream);
 
+/* Copy-paste inside load_mosaic (csrc/augment.hip; reference utils/augmentations.py:219-240) for a set with polygon labels, launched only for a batch in which some
+ * mosaic drew candidates; every other batch makes the launches above.  The host draws js = random.sample(range(n), k = round(p n)) per mosaic, n its polygons.
+ * paste, DEVICE int32 (4 count + 1 + n_paste): 2 count + 1 offsets into js per (item, mosaic), then 2 count mask indices (-1: no paste), then the n_paste js of
+ *   the batch.  A mosaic owns k positions directly after its tile rows in the position space of the polygon and targets launches: n_rows grows by n_paste.
+ * copy_paste_select: one block per mosaic walks its js in order: label row j of labels4 (xywhn2xyxy and the clip of augment_targets) gives
+ *   box = (2S - x2, y1, 2S - x1, y2) in fp32; it is accepted when ioa < 0.30 (fp32: the intersection, clip(0) per axis, over area(row) + 1e-7: bbox_ioa) against every
+ *   row, rows appended by earlier candidates included.  sel_i DEVICE int32 (n_paste, 4): accepted, j, the label-table row of polygon j of the mosaic's list of
+ *   polygons (not that of label row j in a mosaic that mixes polygon and box-only images), its tile; sel_f DEVICE fp32 (n_paste, 5): [cls, box].
+ * copy_paste_raster: one block per accepted slot fills polygon j -- xyn2xy, the clip, the truncation of astype(int32) -- into masks, DEVICE int32 words
+ *   (n_masks, 2S, 2S / 32) the caller has zeroed, bit x & 31 of word (y, x >> 5): drawContours(FILLED), 8-bit, shift 0, line_type 8, as
+ *   tests/augment_copy_paste_cases.py::fill_mask restates it (8-connected boundary lines, scan-line spans (x_left + 65535) >> 16 .. x_right >> 16 over edges in 16.16).
+ * batch_paste: augment_batch, except that a tap at canvas pixel (x, y) of a mosaic with a mask reads canvas pixel (2S - 1 - x, y) where bit (2S - 1 - x, y) is set.
+ * polygons_paste / targets_paste: augment_polygons / augment_targets_polygons over the grown position space: an accepted slot carries the row [cls, box] and
+ *   polygon j mirrored (fp32(2S) - x of the clipped vertex), an unaccepted slot is a dropped row; the path word is formed over the segments after the paste.
+ * No read or write leaves the tables whatever the items, the offsets and the paste table hold.  Square items only; 2S % 32 == 0. */
+int y3_augment_copy_paste_select(const float* labels, const int64_t* label_offsets, const int64_t* vertex_offsets, int64_t n_vertices, int64_t n_label_rows,
+                                 const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
+                                 int32_t n_paste, int32_t* sel_i, float* sel_f, void* stream);
+int y3_augment_copy_paste_raster(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                                 const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
+                                 int32_t n_paste, const int32_t* sel_i, int32_t* masks, int32_t n_masks, void* stream);
+int y3_augment_batch_paste(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                           void* dst, int32_t dst_dtype, int32_t S, const int32_t* paste, const int32_t* masks, int32_t n_masks, void* stream);
+int y3_augment_polygons_paste(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                              const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
+                              int32_t n_paste, const int32_t* sel_i, const float* sel_f, double* boxes, int32_t* inside, int32_t* paths, int64_t n_rows, void* stream);
+int y3_augment_targets_paste(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                             int32_t count, int32_t S, const int32_t* paste, int32_t n_paste, const int32_t* sel_i, const float* sel_f, const double* boxes,
+                             const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

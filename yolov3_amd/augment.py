@@ -19,11 +19,22 @@ of resample_segments, M and segment2box in fp64, and y3_augment_targets_polygons
 polygon and some clipped coordinate is not zero (random_perspective's use_segments) -- every other mosaic, and every letterbox item, runs the four-corner box path
 with 0.10.  Polygons draw no random numbers and touch no pixel.  A set without polygons makes the two launches it always made.
 
+Copy-paste (copy_paste=True; copy_paste(img4, labels4, segments4, p=hyp["copy_paste"]) of load_mosaic, dataloaders.py:809, augmentations.py:219-240): on a set with
+polygons draw_mosaic makes random.sample(range(n), k=round(p n)) over the mosaic's polygons at the reference's place, the candidates of a batch go up behind its records
+as one int32 table (pack_paste; no new record), and a batch in which some mosaic drew candidates makes five launches (ops.augment_copy_paste): the selection walks the
+candidates in order -- box = (w - x2, y1, w - x1, y2) of label row j, accepted when bbox_ioa < 0.30 against every current row; label row j is paired with polygon j of
+the list of polygons, as the reference pairs them -- the raster fills the accepted polygons into a 1-bit mask of the canvas, the sampler reads canvas pixel
+(w - 1 - x, y) where the mask bit there is set, and the polygon and targets kernels carry the appended rows and mirrored polygons at k reserved positions after the
+mosaic's tile rows.  Every other batch -- no candidates, a set without polygons, a letterbox item, copy_paste=False -- makes exactly the launches it made before.
+
 What rests on what: the draws, the geometry, M, the tables, the whole label path, the blend, the flips and the layout are pinned by the unmodified reference
 (tests/golden/make_augment_golden.py; the polygon label path by tests/golden/make_augment_polygons_golden.py over label files with polygon rows, through the NumPy
 statement of tests/augment_polygon_cases.py, which the generator asserts equal to the reference item by item).  The pixel sampler of cv2.warpAffine and the two
 cv2.cvtColor conversions follow the integer / fp32 statements of tests/augment_cases.py, which restate the published 8-bit algorithms and have not been compared with
-a cv2 build.
+a cv2 build.  Copy-paste is pinned by the unmodified reference likewise (tests/golden/make_augment_copy_paste_golden.py: the draws, the pairing, the appended rows, the pasted
+canvas given the mask, the targets) and rests on two more restatements, tests/augment_copy_paste_cases.py: bbox_ioa of the un-vendored ultralytics package, on which every
+acceptance decision rests, and cv2.drawContours(FILLED) (fill_mask), which has not been compared with a cv2 build either: a difference from one, if there is one, lies in
+boundary pixels of a paste and never in a label.
 
 Rectangular training (train.py --rect; LoadImagesAndLabels(augment=True, rect=True), dataloaders.py:547-570):
 
@@ -40,12 +51,12 @@ arithmetic is reproduced: letterbox takes a rect batch's shape from a NumPy arra
 product and sum in float64 before the fp32 label array rounds them once; the tiles of rect items carry `wide` and the kernel does the same (a square set's labels
 stay fp32 throughout, as there).  Pinned by tests/golden/make_augment_rect_golden.py (stride 16, batches of (48, 64), (64, 64) and (64, 48)).
 
-Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0, polygon labels whose count is neither 0 nor the image's label rows
+Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["copy_paste"] != 0 without copy_paste=True, polygon labels whose count is neither 0 nor the image's label rows
 (the reference would send such a mosaic down the box path; here it is an error: a stated difference) or that hold an empty polygon, rect=True on DeviceTrainDataset
 (DeviceRectTrainDataset is that loader), an image whose long side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; on a
 rect set an image that letterbox(scaleup=True) would resize (r = min(H / h, W / w) != 1; the message names the image, its size and the batch shape), an img_size or
 stride that is no multiple of 16, and set_indices (the batch shapes belong to the order); KeyError for a missing hyp key.  Albumentations is a no-op, as in the
-reference when the package is absent.  Out of scope: warpPerspective, copy-paste, a resize inside letterbox, load_mosaic9, cutout, prefetching, returning the warped
+reference when the package is absent.  Out of scope: warpPerspective, a resize inside letterbox, load_mosaic9, cutout, prefetching, returning the warped
 polygons.
 """
 from __future__ import annotations
@@ -82,6 +93,7 @@ class Mosaic:
     pad: list
     center: tuple | None = None   # (yc, xc)
     canvas_h: int | None = None
+    paste: tuple = ()             # copy_paste's js: random.sample over the polygons of the mosaic, in the order drawn
 
 
 @dataclass
@@ -127,8 +139,9 @@ def draw_perspective(hyp, side, border):
     return T @ S @ R @ P @ C, s   # (NumPy's matrix product, as the reference forms it)
 
 
-def draw_mosaic(index, hw, hyp, s, pool) -> Mosaic:
-    """load_mosaic's draws and geometry (dataloaders.py:764-822)"""
+def draw_mosaic(index, hw, hyp, s, pool, poly_counts=None) -> Mosaic:
+    """load_mosaic's draws and geometry (dataloaders.py:764-822).  poly_counts: the number of polygons of every image, for copy_paste's draw (augmentations.py:223-227:
+    n = len(segments4), nothing unless p and n, else random.sample(range(n), k=round(p * n)), between the shuffle and random_perspective's uniforms); None: no draw."""
     border = -s // 2
     yc, xc = (int(random.uniform(-x, 2 * s + x)) for x in (border, border))
     indices = [index, *random.choices(pool, k=3)]
@@ -150,11 +163,16 @@ def draw_mosaic(index, hw, hyp, s, pool) -> Mosaic:
             x1b, y1b, x2b, y2b = 0, 0, min(w, x2a - x1a), min(y2a - y1a, h)
         rects.append((x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b))
         pad.append((x1a - x1b, y1a - y1b))
+    paste = ()
+    if poly_counts is not None:
+        p, n = hyp["copy_paste"], sum(int(poly_counts[j]) for j in indices)
+        if p and n:
+            paste = tuple(random.sample(range(n), k=round(p * n)))
     M, scale = draw_perspective(hyp, 2 * s, border)
-    return Mosaic([int(j) for j in indices], rects, M, scale, 2 * s, pad, (yc, xc))
+    return Mosaic([int(j) for j in indices], rects, M, scale, 2 * s, pad, (yc, xc), None, paste)
 
 
-def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
+def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True, poly_counts=None) -> Item:
     """The draws of one __getitem__ (dataloaders.py:659-735) for image `index` (already looked up in the epoch's order), from the global `random` and `np.random`, in
     the reference's order: random.random() for mosaic; load_mosaic (two uniforms, yc then xc, choices(pool, k=3), shuffle) and random_perspective's eight uniforms;
     random.random() for mixup and, on mixup, randint(0, n - 1), a second load_mosaic and np.random.beta(32, 32) -- or the letterbox branch with its one
@@ -162,7 +180,8 @@ def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
     hw: the cached (h, w) of every image; pool: the epoch's order (default range(n)); n: the number of images (default len(hw)).
     img_size: the side of the square item, or the (H, W) of a rect batch, whose items are drawn with mosaic=False (the reference's mosaic = augment and not rect).
     The shape of a rect batch is an element of a NumPy array in the reference, so letterbox's ratio and halves are float64 scalars there and NumPy (>= 2) forms
-    xywhn2xyxy's product and sum in float64 before the label array rounds them: such an item's Mosaic carries canvas_h, and the kernel does the same."""
+    xywhn2xyxy's product and sum in float64 before the label array rounds them: such an item's Mosaic carries canvas_h, and the kernel does the same.
+    poly_counts: per image its number of polygons, for a set built with copy_paste=True: every load_mosaic then makes copy_paste's random.sample (draw_mosaic)."""
     H, W = _hw(img_size)
     rect = isinstance(img_size, (tuple, list, np.ndarray))   # the batch shape of a rect set, a square one included
     if mosaic and H != W:
@@ -173,9 +192,9 @@ def draw_item(index, hw, hyp, img_size, pool=None, n=None, mosaic=True) -> Item:
     ratio = None
     if mosaic and random.random() < hyp["mosaic"]:
         is_mosaic = True
-        mosaics = [draw_mosaic(index, hw, hyp, s, pool)]
+        mosaics = [draw_mosaic(index, hw, hyp, s, pool, poly_counts)]
         if random.random() < hyp["mixup"]:
-            mosaics.append(draw_mosaic(random.randint(0, n - 1), hw, hyp, s, pool))
+            mosaics.append(draw_mosaic(random.randint(0, n - 1), hw, hyp, s, pool, poly_counts))
             ratio = float(np.random.beta(32.0, 32.0))
     else:
         is_mosaic = False
@@ -226,6 +245,20 @@ def pack_items(items, out=None) -> np.ndarray:
     return rec
 
 
+def pack_paste(items):
+    """The copy-paste candidates of a batch as the device reads them -> (table int32 (4 count + 1 + nk,), nk, masks): 2 count + 1 offsets into the candidates per
+    (item, mosaic), 2 count mask indices (the mosaics with candidates numbered in order, -1 for the others), then the js of all mosaics back to back; nk their number,
+    masks the number of mosaics with candidates.  No new record: y3_augment_item keeps its 1360 bytes."""
+    count = len(items)
+    ks = [len(it.mosaics[m].paste) if m < len(it.mosaics) and it.mosaic else 0 for it in items for m in range(2)]
+    table = np.zeros(4 * count + 1 + sum(ks), dtype=np.int32)
+    np.cumsum(ks, out=table[1 : 2 * count + 1])
+    has = np.array(ks) > 0
+    table[2 * count + 1 : 4 * count + 1] = np.where(has, np.cumsum(has) - 1, -1)
+    table[4 * count + 1 :] = [j for it in items if it.mosaic for mo in it.mosaics for j in mo.paste]
+    return table, int(sum(ks)), int(has.sum())
+
+
 def pack_polygons(labels, segments, paths=None):
     """The polygons of a set as the device reads them -> (vertices (V, 2) float32, offsets (rows + 1,) int64): the vertices of every polygon back to back in the order of
     the label table, row r of the table owning vertices[offsets[r] : offsets[r + 1]]; the rows of an image without polygons own nothing.  segments[i] is empty or holds
@@ -260,15 +293,18 @@ class DeviceTrainDataset(DeviceDataset):
     DeviceDataset); iterating yields the reference loader's 4-tuples with mosaic, random_perspective (affine), augment_hsv, the flips and mixup applied on the
     device.  shapes[i] is None for a mosaic item, the letterbox tuple otherwise.  hyp: the reference's hyperparameter dict (HYP_KEYS are read).  segments: the
     reference's dataset.segments (per image an empty list, or one (k, 2) float32 polygon per label row); after a batch of a set with polygons `.polygons` holds the
-    (boxes, inside, path words) ops.augment_polygons wrote for it."""
+    (boxes, inside, path words) ops.augment_polygons wrote for it.
+    copy_paste: False (the default) refuses a non-zero hyp["copy_paste"] as before -- the default is what it is because existing tests pin that refusal and its text;
+    a later change may flip it.  True accepts it: on a set with polygons every load_mosaic draws and pastes as the reference's copy_paste does (`.pastes` holds the
+    selection tables and the masks of the last batch that pasted, else None); a set without polygons and a letterbox item never paste, as in the reference."""
 
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, mosaic=True, device="cuda", dtype=torch.uint8,
-                 rect=False, segments=None):
+                 rect=False, segments=None, copy_paste=False):
         # every refusal comes before anything is uploaded
         hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
         if hyp["perspective"] != 0:
             raise ValueError(f"DeviceTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
-        if hyp["copy_paste"] != 0:
+        if hyp["copy_paste"] != 0 and not copy_paste:
             raise ValueError(f"DeviceTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
         polygons = None
         if segments is not None and any(len(sg) for sg in segments):
@@ -289,14 +325,20 @@ class DeviceTrainDataset(DeviceDataset):
         self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
         self._stage_rec = self._stage.numpy().view(ITEM)
         self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
-        self._vertices = self._vertex_offsets = self.polygons = None   # a box-only set: the two launches per batch and nothing else
+        self._vertices = self._vertex_offsets = self.polygons = self.pastes = self._poly_counts = None   # a box-only set: the two launches per batch and nothing else
         if polygons is not None:
             self._vertices, self._vertex_offsets = _dataset._upload(polygons[0], self.device), _dataset._upload(polygons[1], self.device)
+            if copy_paste and hyp["copy_paste"]:   # copy_paste's draw per load_mosaic; the candidates of a batch ride behind its records in the one staging buffer
+                self._poly_counts = [len(sg) for sg in segments]
+                room = 4 * (4 * self.batch_size + 1 + 8 * self.batch_size * max(self._poly_counts))
+                self._stage = torch.empty(self.batch_size * ITEM.itemsize + room, dtype=torch.uint8).pin_memory()
+                self._stage_rec = self._stage.numpy()[: self.batch_size * ITEM.itemsize].view(ITEM)
+                self._items_dev = torch.empty(self.batch_size * ITEM.itemsize + room, dtype=torch.uint8, device=self.device)
 
     @classmethod
-    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False):
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=False: reads .ims, .im_hw0, .im_hw, .labels, .segments, .im_files, .hyp,
-        .img_size, .stride, .rect, .mosaic and .indices (the epoch's order)."""
+        .img_size, .stride, .rect, .mosaic and .indices (the epoch's order).  copy_paste: as for the constructor."""
         ims = list(dataset.ims)
         if any(im is None for im in ims):
             raise ValueError('DeviceTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
@@ -304,7 +346,7 @@ class DeviceTrainDataset(DeviceDataset):
             raise ValueError("DeviceTrainDataset.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
         ds = cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
                  paths=dataset.im_files, single_cls=single_cls, mosaic=getattr(dataset, "mosaic", True), device=device, dtype=dtype, rect=bool(dataset.rect),
-                 segments=getattr(dataset, "segments", None))
+                 segments=getattr(dataset, "segments", None), copy_paste=copy_paste)
         indices = getattr(dataset, "indices", None)
         if indices is not None and list(indices) != list(range(ds.n)):
             ds.set_indices(indices)
@@ -313,7 +355,7 @@ class DeviceTrainDataset(DeviceDataset):
     def draw_batch(self, k: int):
         """the items of batch k, drawn now from the global generators: a list of Item"""
         pool = range(self.n) if self._perm is None else self._perm.tolist()
-        return [draw_item(i, self.hw, self.hyp, self.img_size, pool, self.n, self.mosaic) for i in self.batch_images(k)]
+        return [draw_item(i, self.hw, self.hyp, self.img_size, pool, self.n, self.mosaic, self._poly_counts) for i in self.batch_images(k)]
 
     def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
         """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
@@ -321,8 +363,20 @@ class DeviceTrainDataset(DeviceDataset):
         count = len(items)
         pack_items(items, self._stage_rec[:count])
         nbytes = count * ITEM.itemsize
-        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
         upper = int(sum(self._counts[j] for it in items for mo in it.mosaics for j in mo.indices))
+        if self._poly_counts is not None and any(mo.paste for it in items if it.mosaic for mo in it.mosaics):   # some mosaic pastes: the five launches of the copy-paste form
+            table, nk, masks = pack_paste(items)
+            if nbytes + table.nbytes > self._stage.numel():
+                raise ValueError(f"DeviceTrainDataset: {nk} copy-paste candidates in one batch exceed the staging buffer (items drawn for another set?)")
+            self._stage.numpy()[nbytes : nbytes + table.nbytes].view(np.int32)[:] = table
+            self._items_dev[: nbytes + table.nbytes].copy_(self._stage[: nbytes + table.nbytes], non_blocking=True)   # the one host -> device copy of the batch
+            paste = self._items_dev[nbytes : nbytes + table.nbytes].view(torch.int32)
+            im, targets, offsets, self.polygons, self.pastes = ops.augment_copy_paste(self._labels, self._label_offsets, self._vertices, self._vertex_offsets, self._arena, self._records,
+                                                                                      self.n, self._items_dev, count, self.img_size, upper + nk, paste, nk, masks, self.dtype, out)
+            nl = int(offsets.cpu()[count])
+            return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
+        self.pastes = None
+        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
         im = ops.augment_batch(self._arena, self._records, self.n, self._items_dev, count, self.img_size, self.dtype, out)
         if self._vertices is None:
             targets, offsets = ops.augment_targets(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
@@ -338,15 +392,17 @@ class DeviceRectTrainDataset(DeviceDataset):
     letterboxed to its own batch_shapes[k] = (H_k, W_k), as a rect DeviceDataset with pad=0.0 lays it out; no mosaic and no mixup, every item the letterbox branch
     with random_perspective (affine), augment_hsv and the flips on the device.  Iterating yields (im (bs, 3, H_k, W_k), targets (nl, 6), paths, shapes), shapes[i] the
     letterbox tuple of every item.  hyp: the reference's dict (HYP_KEYS are read; `mosaic` and `mixup` are not used).  segments: accepted and not used, as the
-    reference hands none to random_perspective on this branch (area_thr stays 0.10).  The order is the set's: set_indices raises."""
+    reference hands none to random_perspective on this branch (area_thr stays 0.10).  The order is the set's: set_indices raises.
+    copy_paste: False (the default) refuses a non-zero hyp["copy_paste"] as before (existing tests pin it; a later change may flip it); True accepts the hyp and
+    ignores it: the reference's rect path never calls copy_paste."""
 
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, device="cuda", dtype=torch.uint8,
-                 segments=None, _adopt=None):
+                 segments=None, _adopt=None, copy_paste=False):
         # every refusal comes before anything is uploaded
         hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
         if hyp["perspective"] != 0:
             raise ValueError(f"DeviceRectTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
-        if hyp["copy_paste"] != 0:
+        if hyp["copy_paste"] != 0 and not copy_paste:
             raise ValueError(f"DeviceRectTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
         for name, v in (("img_size", img_size), ("stride", stride)):
             if int(v) != v or int(v) < 16 or int(v) % 16:
@@ -380,9 +436,10 @@ class DeviceRectTrainDataset(DeviceDataset):
                                  "would resize it (r != 1), and cv2.resize is out of scope")
 
     @classmethod
-    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False):
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=True: reads .ims, .im_hw0, .im_hw, .labels, .im_files, .hyp, .img_size,
-        .stride, .rect, .augment and, where present, .segments and .batch / .batch_shapes (the aspect-ratio order the dataset is already in is adopted)."""
+        .stride, .rect, .augment and, where present, .segments and .batch / .batch_shapes (the aspect-ratio order the dataset is already in is adopted).
+        copy_paste: as for the constructor (True accepts a non-zero hyp["copy_paste"] and ignores it)."""
         ims = list(dataset.ims)
         if any(im is None for im in ims):
             raise ValueError('DeviceRectTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
@@ -395,7 +452,7 @@ class DeviceRectTrainDataset(DeviceDataset):
                 raise ValueError(f"DeviceRectTrainDataset.from_dataset: im_hw[{i}] = {tuple(hw)} is not the cached image's {im.shape[:2]}")
         adopt = (dataset.batch, dataset.batch_shapes) if hasattr(dataset, "batch") and hasattr(dataset, "batch_shapes") else None
         return cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
-                   paths=dataset.im_files, single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), _adopt=adopt)
+                   paths=dataset.im_files, single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), _adopt=adopt, copy_paste=copy_paste)
 
     def draw_batch(self, k: int):
         """the items of batch k, drawn now from the global generators: a list of Item"""

@@ -1158,6 +1158,71 @@ def augment_targets_polygons(labels: torch.Tensor, label_offsets: torch.Tensor, 
     return targets, offsets
 
 
+_paste_ws: dict = {}   # device -> the int32 words of the copy-paste masks, grown on demand and cleared per batch
+
+
+def augment_copy_paste(labels: torch.Tensor, label_offsets: torch.Tensor, vertices: torch.Tensor, vertex_offsets: torch.Tensor, arena: torch.Tensor, images: torch.Tensor,
+                       n: int, items: torch.Tensor, count: int, size: int, n_rows: int, paste: torch.Tensor, n_paste: int, n_masks: int,
+                       dtype: torch.dtype = torch.uint8, out: torch.Tensor | None = None):
+    """One augmented batch of a set with polygon labels in which some mosaic pastes (copy_paste inside load_mosaic): the five launches y3_augment_copy_paste_select,
+    y3_augment_copy_paste_raster, y3_augment_batch_paste, y3_augment_polygons_paste and y3_augment_targets_paste on the caller's stream.  `paste`: the DEVICE int32
+    table of the batch (augment.pack_paste: 2 count + 1 offsets, 2 count mask indices, the n_paste candidates), `n_masks` the mosaics with candidates, `n_rows` the
+    label count of all tiles plus n_paste.  The masks are a workspace of this module, (n_masks, 2 size, 2 size / 32) int32 words, cleared here: the view returned is
+    good until the next call on the same device.
+    -> (im, targets, offsets, (boxes, inside, paths), (sel_i (n_paste, 4) int32 [accepted, j, polygon row, tile], sel_f (n_paste, 5) fp32 [cls, box], masks))"""
+    what = "augment_copy_paste"
+    for t in (labels, label_offsets, vertices, vertex_offsets, arena, paste):
+        require_gpu(t, what)
+    _augment_args(what, images, n, items, count, size)
+    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous() or not labels.numel():
+        raise TypeError(f"{what} expects the contiguous, non-empty fp32 (total, 5) label table")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 2 or not vertices.is_contiguous() or not vertices.numel():
+        raise TypeError(f"{what} expects the contiguous, non-empty fp32 (V, 2) vertex table")
+    for t, k, name in ((label_offsets, n + 1, "label"), (vertex_offsets, labels.shape[0] + 1, "vertex")):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != k or not t.is_contiguous():
+            raise TypeError(f"{what} expects {k} contiguous int64 {name} offsets")
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous uint8 arena of the set")
+    if dtype not in DTYPE_CODE:
+        raise TypeError(f"{what} writes uint8 / float16 / bfloat16 / float32, not {dtype}")
+    n_paste, n_masks, count, size, n_rows = int(n_paste), int(n_masks), int(count), int(size), int(n_rows)
+    if count < 1 or n_paste < 1 or not 1 <= n_masks <= 2 * count or n_rows < n_paste:
+        raise ValueError(f"{what}: {n_paste} candidates in {n_masks} mosaics of {count} items, {n_rows} rows")
+    if paste.dtype != torch.int32 or paste.dim() != 1 or not paste.is_contiguous() or paste.numel() != 4 * count + 1 + n_paste:
+        raise TypeError(f"{what} expects the contiguous int32 paste table of the batch: {4 * count + 1 + n_paste} words")
+    dev = labels.device
+    shape = (count, 3, size, size)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise TypeError(f"{what}: `out` must be a contiguous {shape} {dtype} tensor on {dev}")
+    words = n_masks * 2 * size * (2 * size // 32)
+    ws = _paste_ws.get(dev)
+    if ws is None or ws.numel() < words:
+        ws = _paste_ws[dev] = torch.empty(words, dtype=torch.int32, device=dev)
+    masks = ws[:words].zero_()
+    sel_i = torch.empty(n_paste, 4, dtype=torch.int32, device=dev)
+    sel_f = torch.empty(n_paste, 5, dtype=torch.float32, device=dev)
+    boxes = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
+    inside = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    paths = torch.empty(count, 2, dtype=torch.int32, device=dev)
+    targets = torch.empty(n_rows, 6, dtype=torch.float32, device=dev)
+    offsets = torch.empty(count + 1, dtype=torch.int64, device=dev)
+    lib, st = _lib.lib(), stream_ptr()
+    verts = (vertices.data_ptr(), vertices.shape[0], vertex_offsets.data_ptr(), vertex_offsets.numel() - 1)
+    batch = (images.data_ptr(), int(n), items.data_ptr(), count, size, paste.data_ptr(), n_paste)
+    check(lib.y3_augment_copy_paste_select(labels.data_ptr(), label_offsets.data_ptr(), vertex_offsets.data_ptr(), vertices.shape[0], vertex_offsets.numel() - 1, *batch,
+                                           sel_i.data_ptr(), sel_f.data_ptr(), st), "y3_augment_copy_paste_select")
+    check(lib.y3_augment_copy_paste_raster(*verts, label_offsets.data_ptr(), *batch, sel_i.data_ptr(), masks.data_ptr(), n_masks, st), "y3_augment_copy_paste_raster")
+    check(lib.y3_augment_batch_paste(arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), items.data_ptr(), count, out.data_ptr(), DTYPE_CODE[dtype], size,
+                                     paste.data_ptr(), masks.data_ptr(), n_masks, st), "y3_augment_batch_paste")
+    check(lib.y3_augment_polygons_paste(*verts, label_offsets.data_ptr(), *batch, sel_i.data_ptr(), sel_f.data_ptr(), boxes.data_ptr(), inside.data_ptr(), paths.data_ptr(),
+                                        n_rows, st), "y3_augment_polygons_paste")
+    check(lib.y3_augment_targets_paste(labels.data_ptr(), label_offsets.data_ptr(), *batch, sel_i.data_ptr(), sel_f.data_ptr(), boxes.data_ptr(), inside.data_ptr(),
+                                       paths.data_ptr(), targets.data_ptr(), n_rows, offsets.data_ptr(), st), "y3_augment_targets_paste")
+    return out, targets, offsets, (boxes, inside, paths), (sel_i, sel_f, masks.view(n_masks, 2 * size, 2 * size // 32))
+
+
 _coco_ws: dict = {}
 
 
