@@ -288,7 +288,66 @@ def pack_polygons(labels, segments, paths=None):
     return np.ascontiguousarray(vertices), offsets
 
 
-class DeviceTrainDataset(DeviceDataset):
+class _DeviceAugmentDataset(DeviceDataset):
+    """What the two train-mode datasets share; every message names the class the caller used."""
+
+    @classmethod
+    def _read_hyp(cls, hyp, copy_paste):
+        hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
+        if hyp["perspective"] != 0:
+            raise ValueError(f"{cls.__name__}: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
+        if hyp["copy_paste"] != 0 and not copy_paste:
+            raise ValueError(f"{cls.__name__}: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        return hyp
+
+    @classmethod
+    def _cached(cls, dataset, batch_size, device, dtype, single_cls, copy_paste):
+        """from_dataset's shared refusals -> (the cached images, the constructor arguments both classes read from the dataset)"""
+        ims = list(dataset.ims)
+        if any(im is None for im in ims):
+            raise ValueError(f'{cls.__name__}.from_dataset: the dataset holds no cached images (build it with cache="ram")')
+        if not getattr(dataset, "augment", False):
+            raise ValueError(f"{cls.__name__}.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
+        return ims, dict(img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0], paths=dataset.im_files,
+                         single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), copy_paste=copy_paste)
+
+    def _set_up(self, hyp, images, mosaic=False, poly_counts=None):
+        """what draw_batch reads, and the pinned records of one batch with their device twin; the copy-paste candidates of a batch ride behind its records"""
+        self.hyp, self.mosaic, self._poly_counts = hyp, bool(mosaic), poly_counts
+        self.hw = [tuple(int(v) for v in images[i].shape[:2]) for i in self.order]   # in the set's order, as the record table is
+        nbytes = self.batch_size * ITEM.itemsize
+        room = 0 if poly_counts is None else 4 * (4 * self.batch_size + 1 + 8 * self.batch_size * max(poly_counts))
+        self._stage = torch.empty(nbytes + room, dtype=torch.uint8).pin_memory()
+        self._stage_rec = self._stage.numpy()[:nbytes].view(ITEM)
+        self._items_dev = torch.empty(nbytes + room, dtype=torch.uint8, device=self.device)
+
+    def _upload_items(self, items, table=None):
+        """pack the records of the batch, the int32 `table` behind them, and make the one host -> device copy of the batch -> the table on the device, or None"""
+        pack_items(items, self._stage_rec[: len(items)])
+        nbytes = end = len(items) * ITEM.itemsize
+        if table is not None:
+            end = nbytes + table.nbytes
+            if end > self._stage.numel():
+                raise ValueError(f"{type(self).__name__}: {table.size - 4 * len(items) - 1} copy-paste candidates in one batch exceed the staging buffer (items drawn for another set?)")
+            self._stage.numpy()[nbytes:end].view(np.int32)[:] = table
+        self._items_dev[:end].copy_(self._stage[:end], non_blocking=True)
+        return None if table is None else self._items_dev[nbytes:end].view(torch.int32)
+
+    def draw_batch(self, k: int):
+        """the items of batch k, drawn now from the global generators: a list of Item (a rect set draws every item for its batch's shape, without a mosaic)"""
+        pool = range(self.n) if self._perm is None else self._perm.tolist()
+        size = tuple(int(v) for v in self.batch_shapes[k]) if self.rect else self.img_size
+        return [draw_item(i, self.hw, self.hyp, size, pool, self.n, self.mosaic, self._poly_counts) for i in self.batch_images(k)]
+
+    def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
+        """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
+        items = self.draw_batch(k) if items is None else items
+        im, targets, offsets = self._launch(k, items, out)   # the upload, then the launches of the class
+        nl = int(offsets.cpu()[len(items)])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
+        return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
+
+
+class DeviceTrainDataset(_DeviceAugmentDataset):
     """The cached images and labels of an augment=True, rect=False dataset in device memory (the arena, the record table, the label table and the chunked upload of
     DeviceDataset); iterating yields the reference loader's 4-tuples with mosaic, random_perspective (affine), augment_hsv, the flips and mixup applied on the
     device.  shapes[i] is None for a mosaic item, the letterbox tuple otherwise.  hyp: the reference's hyperparameter dict (HYP_KEYS are read).  segments: the
@@ -301,11 +360,7 @@ class DeviceTrainDataset(DeviceDataset):
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, mosaic=True, device="cuda", dtype=torch.uint8,
                  rect=False, segments=None, copy_paste=False):
         # every refusal comes before anything is uploaded
-        hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
-        if hyp["perspective"] != 0:
-            raise ValueError(f"DeviceTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
-        if hyp["copy_paste"] != 0 and not copy_paste:
-            raise ValueError(f"DeviceTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        hyp = self._read_hyp(hyp, copy_paste)
         polygons = None
         if segments is not None and any(len(sg) for sg in segments):
             polygons = pack_polygons(labels, segments, paths)   # (host only: the vertex table goes up after the images)
@@ -320,74 +375,43 @@ class DeviceTrainDataset(DeviceDataset):
                                  f"{img_size} (load_image's cv2.resize is out of scope)")
         super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=False, shapes0=shapes0, paths=paths, single_cls=single_cls,
                          device=device, dtype=dtype)
-        self.hyp, self.mosaic = hyp, bool(mosaic)
-        self.hw = [tuple(int(v) for v in im.shape[:2]) for im in images]
-        self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
-        self._stage_rec = self._stage.numpy().view(ITEM)
-        self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
-        self._vertices = self._vertex_offsets = self.polygons = self.pastes = self._poly_counts = None   # a box-only set: the two launches per batch and nothing else
+        self._vertices = self._vertex_offsets = self.polygons = self.pastes = None   # a box-only set: the two launches per batch and nothing else
         if polygons is not None:
             self._vertices, self._vertex_offsets = _dataset._upload(polygons[0], self.device), _dataset._upload(polygons[1], self.device)
-            if copy_paste and hyp["copy_paste"]:   # copy_paste's draw per load_mosaic; the candidates of a batch ride behind its records in the one staging buffer
-                self._poly_counts = [len(sg) for sg in segments]
-                room = 4 * (4 * self.batch_size + 1 + 8 * self.batch_size * max(self._poly_counts))
-                self._stage = torch.empty(self.batch_size * ITEM.itemsize + room, dtype=torch.uint8).pin_memory()
-                self._stage_rec = self._stage.numpy()[: self.batch_size * ITEM.itemsize].view(ITEM)
-                self._items_dev = torch.empty(self.batch_size * ITEM.itemsize + room, dtype=torch.uint8, device=self.device)
+        pasting = polygons is not None and copy_paste and hyp["copy_paste"]   # copy_paste's draw per load_mosaic, from the polygon count of every image
+        self._set_up(hyp, images, mosaic, [len(sg) for sg in segments] if pasting else None)
 
     @classmethod
     def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=False: reads .ims, .im_hw0, .im_hw, .labels, .segments, .im_files, .hyp,
         .img_size, .stride, .rect, .mosaic and .indices (the epoch's order).  copy_paste: as for the constructor."""
-        ims = list(dataset.ims)
-        if any(im is None for im in ims):
-            raise ValueError('DeviceTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
-        if not getattr(dataset, "augment", False):
-            raise ValueError("DeviceTrainDataset.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
-        ds = cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
-                 paths=dataset.im_files, single_cls=single_cls, mosaic=getattr(dataset, "mosaic", True), device=device, dtype=dtype, rect=bool(dataset.rect),
-                 segments=getattr(dataset, "segments", None), copy_paste=copy_paste)
+        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste)
+        ds = cls(ims, dataset.labels, dataset.hyp, mosaic=getattr(dataset, "mosaic", True), rect=bool(dataset.rect), **shared)
         indices = getattr(dataset, "indices", None)
         if indices is not None and list(indices) != list(range(ds.n)):
             ds.set_indices(indices)
         return ds
 
-    def draw_batch(self, k: int):
-        """the items of batch k, drawn now from the global generators: a list of Item"""
-        pool = range(self.n) if self._perm is None else self._perm.tolist()
-        return [draw_item(i, self.hw, self.hyp, self.img_size, pool, self.n, self.mosaic, self._poly_counts) for i in self.batch_images(k)]
-
-    def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
-        """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
-        items = self.draw_batch(k) if items is None else items
-        count = len(items)
-        pack_items(items, self._stage_rec[:count])
-        nbytes = count * ITEM.itemsize
+    def _launch(self, k, items, out):
         upper = int(sum(self._counts[j] for it in items for mo in it.mosaics for j in mo.indices))
+        batch = (self._records, self.n, self._items_dev, len(items), self.img_size)
         if self._poly_counts is not None and any(mo.paste for it in items if it.mosaic for mo in it.mosaics):   # some mosaic pastes: the five launches of the copy-paste form
             table, nk, masks = pack_paste(items)
-            if nbytes + table.nbytes > self._stage.numel():
-                raise ValueError(f"DeviceTrainDataset: {nk} copy-paste candidates in one batch exceed the staging buffer (items drawn for another set?)")
-            self._stage.numpy()[nbytes : nbytes + table.nbytes].view(np.int32)[:] = table
-            self._items_dev[: nbytes + table.nbytes].copy_(self._stage[: nbytes + table.nbytes], non_blocking=True)   # the one host -> device copy of the batch
-            paste = self._items_dev[nbytes : nbytes + table.nbytes].view(torch.int32)
-            im, targets, offsets, self.polygons, self.pastes = ops.augment_copy_paste(self._labels, self._label_offsets, self._vertices, self._vertex_offsets, self._arena, self._records,
-                                                                                      self.n, self._items_dev, count, self.img_size, upper + nk, paste, nk, masks, self.dtype, out)
-            nl = int(offsets.cpu()[count])
-            return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
+            paste = self._upload_items(items, table)
+            im, targets, offsets, self.polygons, self.pastes = ops.augment_copy_paste(self._labels, self._label_offsets, self._vertices, self._vertex_offsets, self._arena, *batch,
+                                                                                      upper + nk, paste, nk, masks, self.dtype, out)
+            return im, targets, offsets
         self.pastes = None
-        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
-        im = ops.augment_batch(self._arena, self._records, self.n, self._items_dev, count, self.img_size, self.dtype, out)
+        self._upload_items(items)
+        im = ops.augment_batch(self._arena, *batch, self.dtype, out)
         if self._vertices is None:
-            targets, offsets = ops.augment_targets(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
-        else:   # polygon labels: the boxes of the warped polygons first, then the targets that choose per mosaic between them and the four corners
-            self.polygons = ops.augment_polygons(self._vertices, self._vertex_offsets, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper)
-            targets, offsets = ops.augment_targets_polygons(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, self.img_size, upper, *self.polygons)
-        nl = int(offsets.cpu()[count])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
-        return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
+            return (im, *ops.augment_targets(self._labels, self._label_offsets, *batch, upper))
+        # polygon labels: the boxes of the warped polygons first, then the targets that choose per mosaic between them and the four corners
+        self.polygons = ops.augment_polygons(self._vertices, self._vertex_offsets, self._label_offsets, *batch, upper)
+        return (im, *ops.augment_targets_polygons(self._labels, self._label_offsets, *batch, upper, *self.polygons))
 
 
-class DeviceRectTrainDataset(DeviceDataset):
+class DeviceRectTrainDataset(_DeviceAugmentDataset):
     """The cached images and labels of an augment=True, rect=True dataset in device memory (train.py --rect): the set sorted by aspect ratio and every batch k
     letterboxed to its own batch_shapes[k] = (H_k, W_k), as a rect DeviceDataset with pad=0.0 lays it out; no mosaic and no mixup, every item the letterbox branch
     with random_perspective (affine), augment_hsv and the flips on the device.  Iterating yields (im (bs, 3, H_k, W_k), targets (nl, 6), paths, shapes), shapes[i] the
@@ -399,11 +423,7 @@ class DeviceRectTrainDataset(DeviceDataset):
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, device="cuda", dtype=torch.uint8,
                  segments=None, _adopt=None, copy_paste=False):
         # every refusal comes before anything is uploaded
-        hyp = {k: hyp[k] for k in HYP_KEYS}   # KeyError for a key the path reads and does not find
-        if hyp["perspective"] != 0:
-            raise ValueError(f"DeviceRectTrainDataset: hyp['perspective'] = {hyp['perspective']}; warpPerspective is not built")
-        if hyp["copy_paste"] != 0 and not copy_paste:
-            raise ValueError(f"DeviceRectTrainDataset: hyp['copy_paste'] = {hyp['copy_paste']}; copy-paste is not built")
+        hyp = self._read_hyp(hyp, copy_paste)
         for name, v in (("img_size", img_size), ("stride", stride)):
             if int(v) != v or int(v) < 16 or int(v) % 16:
                 raise ValueError(f"DeviceRectTrainDataset: {name} = {v} must be a multiple of 16 (both sides of every batch shape are multiples of stride)")
@@ -411,11 +431,7 @@ class DeviceRectTrainDataset(DeviceDataset):
             self._refuse_resize(images, [im.shape[:2] for im in images] if shapes0 is None else shapes0, int(img_size), int(batch_size), int(stride), paths, _adopt)
         super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=True, shapes0=shapes0, paths=paths, single_cls=single_cls,
                          device=device, dtype=dtype, _adopt=_adopt)
-        self.hyp = hyp
-        self.hw = [tuple(int(v) for v in images[i].shape[:2]) for i in self.order]   # in the set's order, as the record table is
-        self._stage = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8).pin_memory()
-        self._stage_rec = self._stage.numpy().view(ITEM)
-        self._items_dev = torch.empty(self.batch_size * ITEM.itemsize, dtype=torch.uint8, device=self.device)
+        self._set_up(hyp, images)
 
     @staticmethod
     def _refuse_resize(images, hw0, img_size, batch_size, stride, paths, adopt):
@@ -440,35 +456,17 @@ class DeviceRectTrainDataset(DeviceDataset):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=True: reads .ims, .im_hw0, .im_hw, .labels, .im_files, .hyp, .img_size,
         .stride, .rect, .augment and, where present, .segments and .batch / .batch_shapes (the aspect-ratio order the dataset is already in is adopted).
         copy_paste: as for the constructor (True accepts a non-zero hyp["copy_paste"] and ignores it)."""
-        ims = list(dataset.ims)
-        if any(im is None for im in ims):
-            raise ValueError('DeviceRectTrainDataset.from_dataset: the dataset holds no cached images (build it with cache="ram")')
-        if not getattr(dataset, "augment", False):
-            raise ValueError("DeviceRectTrainDataset.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
+        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste)
         if not dataset.rect:
             raise ValueError("DeviceRectTrainDataset.from_dataset: the dataset is not rectangular (rect=False); use DeviceTrainDataset")
         for i, (im, hw) in enumerate(zip(ims, dataset.im_hw)):
             if isinstance(im, np.ndarray) and tuple(im.shape[:2]) != tuple(int(v) for v in hw):
                 raise ValueError(f"DeviceRectTrainDataset.from_dataset: im_hw[{i}] = {tuple(hw)} is not the cached image's {im.shape[:2]}")
         adopt = (dataset.batch, dataset.batch_shapes) if hasattr(dataset, "batch") and hasattr(dataset, "batch_shapes") else None
-        return cls(ims, dataset.labels, dataset.hyp, img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0],
-                   paths=dataset.im_files, single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), _adopt=adopt, copy_paste=copy_paste)
+        return cls(ims, dataset.labels, dataset.hyp, _adopt=adopt, **shared)
 
-    def draw_batch(self, k: int):
-        """the items of batch k, drawn now from the global generators: a list of Item"""
-        shape = tuple(int(v) for v in self.batch_shapes[k])
-        return [draw_item(i, self.hw, self.hyp, shape, None, self.n, False) for i in self.batch_images(k)]
-
-    def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
-        """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
-        items = self.draw_batch(k) if items is None else items
-        count = len(items)
-        H, W = (int(v) for v in self.batch_shapes[k])
-        pack_items(items, self._stage_rec[:count])
-        nbytes = count * ITEM.itemsize
-        self._items_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)   # the one host -> device copy of the batch
-        upper = int(sum(self._counts[it.index] for it in items))
-        im = ops.augment_batch_hw(self._arena, self._records, self.n, self._items_dev, count, H, W, self.dtype, out)
-        targets, offsets = ops.augment_targets_hw(self._labels, self._label_offsets, self._records, self.n, self._items_dev, count, H, W, upper)
-        nl = int(offsets.cpu()[count])   # the one device -> host read (it also frees the staging buffer for the next batch)
-        return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(self.shapes[it.index] for it in items)
+    def _launch(self, k, items, out):
+        batch = (self._records, self.n, self._items_dev, len(items), *(int(v) for v in self.batch_shapes[k]))
+        self._upload_items(items)
+        im = ops.augment_batch_hw(self._arena, *batch, self.dtype, out)
+        return (im, *ops.augment_targets_hw(self._labels, self._label_offsets, *batch, int(sum(self._counts[it.index] for it in items))))

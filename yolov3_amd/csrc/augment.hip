@@ -880,22 +880,59 @@ __global__ __launch_bounds__(BT) void copy_paste_raster_kernel(const TargetArgs 
     }
 }
 
+// ---- the host side.  An export copies its arguments into the structs its kernel takes (nothing is tested on the way) and hands them to the launcher of its kernel
+// family, which refuses in the order every export has kept -- a null pointer, the set and the paste table (check_set), a count, an alignment -- with the family's texts
+// under the export's own name, and launches.
 bool aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
-int check_set(const char* fn, const void* images, int64_t n_images, const void* items, int32_t count, int32_t H, int32_t W) {
-    if (!images || !items) Y3_FAIL("%s: null argument", fn);
-    if (n_images < 1 || n_images > 0x7fffffffLL || count < 0 || count > MAX_BS || H < 16 || H > MAX_S || W < 16 || W > MAX_S)
-        Y3_FAIL("%s: bad geometry (%lld images in 1 .. 2^31 - 1, a batch of %d in 0 .. %d items of %d x %d in 16 .. %d)", fn, (long long)n_images, count, MAX_BS, H, W, MAX_S);
-    if (H % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, H);
-    if (W % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, W);
-    if (!aligned(images, 8) || !aligned(items, 8)) Y3_FAIL("%s: the record table and the items must be 8-byte aligned", fn);
+TargetArgs target_args(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                       int32_t H, int32_t W, float* targets = nullptr, int64_t n_rows = 0, int64_t* offsets = nullptr) {
+    TargetArgs a = {};
+    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
+    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = H; a.W = W;
+    a.clip_w = (float)((double)W - 1e-3);
+    a.clip_h = (float)((double)H - 1e-3);
+    return a;
+}
+
+// PolyTables and PasteTables are filled in place, in the order of their fields (a form leaves out the tail it does not read).  What more than one family tests:
+// the extents of the vertex table (at least `least` vertices), a row count, the fp64 / int32 workspace of the polygon kernel
+bool bad_vertex_table(const PolyTables& p, long long least = 0) { return p.n_verts < least || p.n_verts > 0x7fffffffLL / 2 || p.n_vert_rows < 0 || p.n_vert_rows > 0x7fffffffLL; }
+bool bad_rows(long long n) { return n < 0 || n > 0x7fffffffLL / 6; }
+bool null_workspace(const PolyTables& p, int count) { return (count > 0 && !p.paths) || (p.ws_rows > 0 && (!p.boxes || !p.inside)); }
+bool misaligned_workspace(const PolyTables& p) { return !aligned(p.boxes, 8) || !aligned(p.inside, 4) || !aligned(p.paths, 4); }
+
+enum SelReads { SEL_I_AND_F, SEL_I_ONLY };   // what a copy-paste form reads of the selection: the raster reads sel_i alone
+
+// the set every export takes (images, items, count, H, W of `a`) and, for a copy-paste form, the table of the batch `c` and what the selection leaves
+int check_set(const char* fn, const TargetArgs& a, const PasteTables* c = nullptr, SelReads reads = SEL_I_AND_F) {
+    if (!a.images || !a.items) Y3_FAIL("%s: null argument", fn);
+    if (a.n_images < 1 || a.n_images > 0x7fffffffLL || a.count < 0 || a.count > MAX_BS || a.H < 16 || a.H > MAX_S || a.W < 16 || a.W > MAX_S)
+        Y3_FAIL("%s: bad geometry (%lld images in 1 .. 2^31 - 1, a batch of %d in 0 .. %d items of %d x %d in 16 .. %d)", fn, a.n_images, a.count, MAX_BS, a.H, a.W, MAX_S);
+    if (a.H % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, a.H);
+    if (a.W % 16) Y3_FAIL("%s: the image size %d is not a multiple of 16", fn, a.W);
+    if (!aligned(a.images, 8) || !aligned(a.items, 8)) Y3_FAIL("%s: the record table and the items must be 8-byte aligned", fn);
+    if (!c) return 0;
+    if (!c->table || !c->sel_i || (reads == SEL_I_AND_F && !c->sel_f)) Y3_FAIL("%s: null argument", fn);
+    if (c->nk < 1 || c->nk > 0x3fffffff / 6) Y3_FAIL("%s: bad geometry (%d candidates)", fn, c->nk);
+    if (a.W % 16 || 2 * a.W % 32) Y3_FAIL("%s: the canvas 2 x %d is not a multiple of 32", fn, a.W);
+    if (!aligned(c->table, 4) || !aligned(c->sel_i, 4) || !aligned(c->sel_f, 4)) Y3_FAIL("%s: the int32 and fp32 tables must be 4-byte aligned", fn);
     return 0;
+}
+
+template <typename A> void launch_sampler(int32_t dst_dtype, dim3 grid, hipStream_t st, const A& a) {
+    switch (dst_dtype) {
+        case Y3_U8: hipLaunchKernelGGL((augment_batch_kernel<unsigned char, A>), grid, dim3(BT), 0, st, a); break;
+        case Y3_F16: hipLaunchKernelGGL((augment_batch_kernel<f16_t, A>), grid, dim3(BT), 0, st, a); break;
+        case Y3_BF16: hipLaunchKernelGGL((augment_batch_kernel<bf16_t, A>), grid, dim3(BT), 0, st, a); break;
+        default: hipLaunchKernelGGL((augment_batch_kernel<float, A>), grid, dim3(BT), 0, st, a); break;
+    }
 }
 
 int launch_batch(const char* fn, const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
                  void* dst, int32_t dst_dtype, int32_t H, int32_t W, void* stream, const int32_t* paste = nullptr, const int32_t* masks = nullptr, int32_t n_masks = 0) {
     if (!arena || !dst) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, H, W)) return -1;
+    if (check_set(fn, target_args(nullptr, nullptr, images, n_images, items, count, H, W))) return -1;
     if (arena_bytes < 4 || (arena_bytes & 3)) Y3_FAIL("%s: the arena's %lld bytes are not a positive multiple of 4", fn, (long long)arena_bytes);
     if (!aligned(arena, 16) || !aligned(dst, 16)) Y3_FAIL("%s: the arena and the output must be 16-byte aligned", fn);
     if (dst_dtype != Y3_U8 && dst_dtype != Y3_F16 && dst_dtype != Y3_BF16 && dst_dtype != Y3_F32) Y3_FAIL("%s: unsupported output dtype %d (uint8 / float16 / bfloat16 / float32)", fn, dst_dtype);
@@ -906,49 +943,40 @@ int launch_batch(const char* fn, const uint8_t* arena, int64_t arena_bytes, cons
     a.w_div = y3_make_divisor(W);
     a.paste = paste; a.masks = (const unsigned*)masks; a.n_masks = n_masks;
     const dim3 grid((unsigned)((a.pixels + CHUNK - 1) / CHUNK), (unsigned)count);
+    if (paste) launch_sampler<BatchPasteArgs>(dst_dtype, grid, (hipStream_t)stream, a);
+    else launch_sampler<BatchArgs>(dst_dtype, grid, (hipStream_t)stream, a);
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+// y3_augment_polygons and, with the paste table `c`, y3_augment_polygons_paste
+int launch_polygons(const char* fn, const TargetArgs& a, const PolyTables& p, const PasteTables* c, void* stream) {
+    if (!p.vert_offsets || !a.label_offsets || null_workspace(p, a.count) || (p.n_verts > 0 && !p.verts)) Y3_FAIL("%s: null argument", fn);
+    if (check_set(fn, a, c)) return -1;
+    if (bad_vertex_table(p) || bad_rows(p.ws_rows)) Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows, a workspace of %lld rows)", fn, p.n_verts, p.n_vert_rows, p.ws_rows);
+    if (!aligned(p.vert_offsets, 8) || !aligned(a.label_offsets, 8) || !aligned(p.verts, 4) || misaligned_workspace(p))
+        Y3_FAIL("%s: the offsets and the boxes must be 8-byte, the vertices and the int32 words 4-byte aligned", fn);
+    if (a.count == 0) return 0;
+    const dim3 grid((unsigned)a.count * 2);
+    if (c) hipLaunchKernelGGL(augment_polygons_kernel<true>, grid, dim3(BT), 0, (hipStream_t)stream, a, p, *c);
+    else hipLaunchKernelGGL(augment_polygons_kernel<false>, grid, dim3(BT), 0, (hipStream_t)stream, a, p, PasteTables{});
+    Y3_CHECK_LAUNCH();
+    return 0;
+}
+
+// the four targets exports: the box form; with the workspace `p` the polygon form; with the paste table `c` besides (never without `p`), the copy-paste form.  One
+// block, for an empty batch too: it writes offsets[0].
+int launch_targets(const char* fn, const TargetArgs& a, const PolyTables* p, const PasteTables* c, void* stream) {
+    if (!a.label_offsets || !a.out_offsets || (a.n_rows > 0 && (!a.labels || !a.out)) || (p && null_workspace(*p, a.count))) Y3_FAIL("%s: null argument", fn);
+    if (check_set(fn, a, c)) return -1;
+    if (bad_rows(a.n_rows)) Y3_FAIL("%s: bad geometry (%lld rows)", fn, a.n_rows);
+    if (!aligned(a.label_offsets, 8) || !aligned(a.out_offsets, 8) || !aligned(a.labels, 4) || !aligned(a.out, 4) || (p && misaligned_workspace(*p)))
+        Y3_FAIL(p ? "%s: the offsets and the boxes must be 8-byte, the fp32 tables and the int32 words 4-byte aligned" : "%s: the offsets must be 8-byte, the fp32 tables 4-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    if (paste) {
-        switch (dst_dtype) {
-            case Y3_U8: hipLaunchKernelGGL((augment_batch_kernel<unsigned char, BatchPasteArgs>), grid, dim3(BT), 0, st, a); break;
-            case Y3_F16: hipLaunchKernelGGL((augment_batch_kernel<f16_t, BatchPasteArgs>), grid, dim3(BT), 0, st, a); break;
-            case Y3_BF16: hipLaunchKernelGGL((augment_batch_kernel<bf16_t, BatchPasteArgs>), grid, dim3(BT), 0, st, a); break;
-            default: hipLaunchKernelGGL((augment_batch_kernel<float, BatchPasteArgs>), grid, dim3(BT), 0, st, a); break;
-        }
-        Y3_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (dst_dtype) {
-        case Y3_U8: hipLaunchKernelGGL((augment_batch_kernel<unsigned char, BatchArgs>), grid, dim3(BT), 0, st, (const BatchArgs&)a); break;
-        case Y3_F16: hipLaunchKernelGGL((augment_batch_kernel<f16_t, BatchArgs>), grid, dim3(BT), 0, st, (const BatchArgs&)a); break;
-        case Y3_BF16: hipLaunchKernelGGL((augment_batch_kernel<bf16_t, BatchArgs>), grid, dim3(BT), 0, st, (const BatchArgs&)a); break;
-        default: hipLaunchKernelGGL((augment_batch_kernel<float, BatchArgs>), grid, dim3(BT), 0, st, (const BatchArgs&)a); break;
-    }
+    if (c) hipLaunchKernelGGL((augment_targets_kernel<true, true>), dim3(1), dim3(BT), 0, st, a, *p, *c);
+    else if (p) hipLaunchKernelGGL((augment_targets_kernel<true, false>), dim3(1), dim3(BT), 0, st, a, *p, PasteTables{});
+    else hipLaunchKernelGGL((augment_targets_kernel<false, false>), dim3(1), dim3(BT), 0, st, a, PolyTables{}, PasteTables{});
     Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-int launch_targets(const char* fn, const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
-                   int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
-    if (!label_offsets || !offsets || (n_rows > 0 && (!labels || !targets))) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, H, W)) return -1;
-    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("%s: bad geometry (%lld rows)", fn, (long long)n_rows);
-    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(labels, 4) || !aligned(targets, 4)) Y3_FAIL("%s: the offsets must be 8-byte, the fp32 tables 4-byte aligned", fn);
-    TargetArgs a;
-    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
-    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = H; a.W = W;
-    a.clip_w = (float)((double)W - 1e-3);
-    a.clip_h = (float)((double)H - 1e-3);
-    hipLaunchKernelGGL((augment_targets_kernel<false, false>), dim3(1), dim3(BT), 0, (hipStream_t)stream, a, PolyTables{}, PasteTables{});
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-// the arguments every copy-paste export shares: the table of the batch and what the selection leaves
-int check_paste(const char* fn, const int32_t* paste, int32_t n_paste, const void* sel_i, const void* sel_f, int32_t S) {
-    if (!paste || !sel_i || !sel_f) Y3_FAIL("%s: null argument", fn);
-    if (n_paste < 1 || n_paste > 0x3fffffff / 6) Y3_FAIL("%s: bad geometry (%d candidates)", fn, n_paste);
-    if (S % 16 || 2 * S % 32) Y3_FAIL("%s: the canvas 2 x %d is not a multiple of 32", fn, S);
-    if (!aligned(paste, 4) || !aligned(sel_i, 4) || !aligned(sel_f, 4)) Y3_FAIL("%s: the int32 and fp32 tables must be 4-byte aligned", fn);
     return 0;
 }
 
@@ -966,70 +994,65 @@ extern "C" int y3_augment_batch_hw(const uint8_t* arena, int64_t arena_bytes, co
     return launch_batch("y3_augment_batch_hw", arena, arena_bytes, images, n_images, items, count, dst, dst_dtype, H, W, stream);
 }
 
+extern "C" int y3_augment_batch_paste(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
+                                      void* dst, int32_t dst_dtype, int32_t S, const int32_t* paste, const int32_t* masks, int32_t n_masks, void* stream) {
+    if (!paste || !masks) Y3_FAIL("y3_augment_batch_paste: null argument");
+    if (n_masks < 1 || n_masks > 2 * count || 2 * S % 32 || !aligned(paste, 4) || !aligned(masks, 4)) Y3_FAIL("y3_augment_batch_paste: bad geometry (%d masks for %d items of %d) or alignment", n_masks, count, S);
+    return launch_batch("y3_augment_batch_paste", arena, arena_bytes, images, n_images, items, count, dst, dst_dtype, S, S, stream, paste, masks, n_masks);
+}
+
 extern "C" int y3_augment_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
                                   int32_t count, int32_t S, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
-    return launch_targets("y3_augment_targets", labels, label_offsets, images, n_images, items, count, S, S, targets, n_rows, offsets, stream);
+    return launch_targets("y3_augment_targets", target_args(labels, label_offsets, images, n_images, items, count, S, S, targets, n_rows, offsets), nullptr, nullptr, stream);
 }
 
 extern "C" int y3_augment_targets_hw(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
                                      int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
-    return launch_targets("y3_augment_targets_hw", labels, label_offsets, images, n_images, items, count, H, W, targets, n_rows, offsets, stream);
-}
-
-extern "C" int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
-                                   const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
-                                   int32_t* paths, int64_t n_rows, void* stream) {
-    if (!vertex_offsets || !label_offsets || (count > 0 && !paths) || (n_vertices > 0 && !vertices) || (n_rows > 0 && (!boxes || !inside))) Y3_FAIL("y3_augment_polygons: null argument");
-    if (check_set("y3_augment_polygons", images, n_images, items, count, S, S)) return -1;
-    if (n_vertices < 0 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL || n_rows < 0 || n_rows > 0x7fffffffLL / 6)
-        Y3_FAIL("y3_augment_polygons: bad geometry (%lld vertices, %lld label rows, a workspace of %lld rows)", (long long)n_vertices, (long long)n_label_rows, (long long)n_rows);
-    if (!aligned(vertex_offsets, 8) || !aligned(label_offsets, 8) || !aligned(boxes, 8) || !aligned(vertices, 4) || !aligned(inside, 4) || !aligned(paths, 4))
-        Y3_FAIL("y3_augment_polygons: the offsets and the boxes must be 8-byte, the vertices and the int32 words 4-byte aligned");
-    if (count == 0) return 0;
-    TargetArgs a = {};
-    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.H = S; a.W = S;
-    PolyTables p = {};
-    p.verts = vertices; p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
-    p.boxes = boxes; p.inside = inside; p.paths = paths; p.ws_rows = n_rows;
-    hipLaunchKernelGGL(augment_polygons_kernel<false>, dim3((unsigned)count * 2), dim3(BT), 0, (hipStream_t)stream, a, p, PasteTables{});
-    Y3_CHECK_LAUNCH();
-    return 0;
+    return launch_targets("y3_augment_targets_hw", target_args(labels, label_offsets, images, n_images, items, count, H, W, targets, n_rows, offsets), nullptr, nullptr, stream);
 }
 
 extern "C" int y3_augment_targets_polygons(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
                                            int32_t count, int32_t S, const double* boxes, const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows,
                                            int64_t* offsets, void* stream) {
-    if (!label_offsets || !offsets || (count > 0 && !paths) || (n_rows > 0 && (!labels || !targets || !boxes || !inside))) Y3_FAIL("y3_augment_targets_polygons: null argument");
-    if (check_set("y3_augment_targets_polygons", images, n_images, items, count, S, S)) return -1;
-    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("y3_augment_targets_polygons: bad geometry (%lld rows)", (long long)n_rows);
-    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(boxes, 8) || !aligned(labels, 4) || !aligned(targets, 4) || !aligned(inside, 4) || !aligned(paths, 4))
-        Y3_FAIL("y3_augment_targets_polygons: the offsets and the boxes must be 8-byte, the fp32 tables and the int32 words 4-byte aligned");
-    TargetArgs a;
-    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
-    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = S; a.W = S;
-    a.clip_w = a.clip_h = (float)((double)S - 1e-3);
-    PolyTables p = {};
-    p.boxes = const_cast<double*>(boxes); p.inside = const_cast<int*>(inside); p.paths = const_cast<int*>(paths); p.ws_rows = n_rows;
-    hipLaunchKernelGGL((augment_targets_kernel<true, false>), dim3(1), dim3(BT), 0, (hipStream_t)stream, a, p, PasteTables{});
-    Y3_CHECK_LAUNCH();
-    return 0;
+    const PolyTables p = {nullptr, nullptr, 0, 0, const_cast<double*>(boxes), const_cast<int*>(inside), const_cast<int*>(paths), n_rows};
+    return launch_targets("y3_augment_targets_polygons", target_args(labels, label_offsets, images, n_images, items, count, S, S, targets, n_rows, offsets), &p, nullptr, stream);
+}
+
+extern "C" int y3_augment_targets_paste(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
+                                        int32_t count, int32_t S, const int32_t* paste, int32_t n_paste, const int32_t* sel_i, const float* sel_f, const double* boxes,
+                                        const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
+    const PolyTables p = {nullptr, nullptr, 0, 0, const_cast<double*>(boxes), const_cast<int*>(inside), const_cast<int*>(paths), n_rows};
+    const PasteTables c = {paste, n_paste, const_cast<int*>(sel_i), const_cast<float*>(sel_f)};
+    return launch_targets("y3_augment_targets_paste", target_args(labels, label_offsets, images, n_images, items, count, S, S, targets, n_rows, offsets), &p, &c, stream);
+}
+
+extern "C" int y3_augment_polygons(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                                   const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, double* boxes, int32_t* inside,
+                                   int32_t* paths, int64_t n_rows, void* stream) {
+    return launch_polygons("y3_augment_polygons", target_args(nullptr, label_offsets, images, n_images, items, count, S, S),
+                           {vertices, (const long long*)vertex_offsets, n_vertices, n_label_rows, boxes, inside, paths, n_rows}, nullptr, stream);
+}
+
+extern "C" int y3_augment_polygons_paste(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
+                                         const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
+                                         int32_t n_paste, const int32_t* sel_i, const float* sel_f, double* boxes, int32_t* inside, int32_t* paths, int64_t n_rows, void* stream) {
+    const PasteTables c = {paste, n_paste, const_cast<int*>(sel_i), const_cast<float*>(sel_f)};
+    return launch_polygons("y3_augment_polygons_paste", target_args(nullptr, label_offsets, images, n_images, items, count, S, S),
+                           {vertices, (const long long*)vertex_offsets, n_vertices, n_label_rows, boxes, inside, paths, n_rows}, &c, stream);
 }
 
 extern "C" int y3_augment_copy_paste_select(const float* labels, const int64_t* label_offsets, const int64_t* vertex_offsets, int64_t n_vertices, int64_t n_label_rows,
                                             const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
                                             int32_t n_paste, int32_t* sel_i, float* sel_f, void* stream) {
     const char* fn = "y3_augment_copy_paste_select";
+    const TargetArgs a = target_args(labels, label_offsets, images, n_images, items, count, S, S);
+    const PolyTables p = {nullptr, (const long long*)vertex_offsets, n_vertices, n_label_rows};
+    const PasteTables c = {paste, n_paste, const_cast<int*>(sel_i), const_cast<float*>(sel_f)};
     if (!labels || !label_offsets || !vertex_offsets) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, S, S) || check_paste(fn, paste, n_paste, sel_i, sel_f, S)) return -1;
-    if (n_vertices < 0 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL) Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows)", fn, (long long)n_vertices, (long long)n_label_rows);
+    if (check_set(fn, a, &c)) return -1;
+    if (bad_vertex_table(p)) Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows)", fn, p.n_verts, p.n_vert_rows);
     if (!aligned(label_offsets, 8) || !aligned(vertex_offsets, 8) || !aligned(labels, 4)) Y3_FAIL("%s: the offsets must be 8-byte, the label table 4-byte aligned", fn);
     if (count == 0) return 0;
-    TargetArgs a = {};
-    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.H = S; a.W = S;
-    PolyTables p = {};
-    p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
-    PasteTables c = {};
-    c.table = paste; c.nk = n_paste; c.sel_i = sel_i; c.sel_f = sel_f;
     hipLaunchKernelGGL(copy_paste_select_kernel, dim3((unsigned)count * 2), dim3(BT), 0, (hipStream_t)stream, a, p, c);
     Y3_CHECK_LAUNCH();
     return 0;
@@ -1039,70 +1062,15 @@ extern "C" int y3_augment_copy_paste_raster(const float* vertices, int64_t n_ver
                                             const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
                                             int32_t n_paste, const int32_t* sel_i, int32_t* masks, int32_t n_masks, void* stream) {
     const char* fn = "y3_augment_copy_paste_raster";
+    const TargetArgs a = target_args(nullptr, label_offsets, images, n_images, items, count, S, S);
+    const PolyTables p = {vertices, (const long long*)vertex_offsets, n_vertices, n_label_rows};
+    const PasteTables c = {paste, n_paste, const_cast<int*>(sel_i), nullptr, (unsigned*)masks, n_masks};
     if (!vertices || !vertex_offsets || !label_offsets || !masks) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, S, S) || check_paste(fn, paste, n_paste, sel_i, sel_i, S)) return -1;
-    if (n_vertices < 1 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL || n_masks < 1 || n_masks > 2 * count)
-        Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows, %d masks for %d items)", fn, (long long)n_vertices, (long long)n_label_rows, n_masks, count);
+    if (check_set(fn, a, &c, SEL_I_ONLY)) return -1;
+    if (bad_vertex_table(p, 1) || n_masks < 1 || n_masks > 2 * count) Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows, %d masks for %d items)", fn, p.n_verts, p.n_vert_rows, n_masks, count);
     if (!aligned(label_offsets, 8) || !aligned(vertex_offsets, 8) || !aligned(vertices, 4) || !aligned(masks, 4)) Y3_FAIL("%s: the offsets must be 8-byte, the vertices and the masks 4-byte aligned", fn);
-    TargetArgs a = {};
-    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.H = S; a.W = S;
-    PolyTables p = {};
-    p.verts = vertices; p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
-    PasteTables c = {};
-    c.table = paste; c.nk = n_paste; c.sel_i = const_cast<int*>(sel_i); c.masks = (unsigned*)masks; c.n_masks = n_masks;
     hipLaunchKernelGGL(copy_paste_raster_kernel, dim3((unsigned)n_paste), dim3(BT), 0, (hipStream_t)stream, a, p, c);
     Y3_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int y3_augment_batch_paste(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count,
-                                      void* dst, int32_t dst_dtype, int32_t S, const int32_t* paste, const int32_t* masks, int32_t n_masks, void* stream) {
-    if (!paste || !masks) Y3_FAIL("y3_augment_batch_paste: null argument");
-    if (n_masks < 1 || n_masks > 2 * count || 2 * S % 32 || !aligned(paste, 4) || !aligned(masks, 4)) Y3_FAIL("y3_augment_batch_paste: bad geometry (%d masks for %d items of %d) or alignment", n_masks, count, S);
-    return launch_batch("y3_augment_batch_paste", arena, arena_bytes, images, n_images, items, count, dst, dst_dtype, S, S, stream, paste, masks, n_masks);
-}
-
-extern "C" int y3_augment_polygons_paste(const float* vertices, int64_t n_vertices, const int64_t* vertex_offsets, int64_t n_label_rows, const int64_t* label_offsets,
-                                         const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items, int32_t count, int32_t S, const int32_t* paste,
-                                         int32_t n_paste, const int32_t* sel_i, const float* sel_f, double* boxes, int32_t* inside, int32_t* paths, int64_t n_rows, void* stream) {
-    const char* fn = "y3_augment_polygons_paste";
-    if (!vertex_offsets || !label_offsets || (count > 0 && !paths) || (n_vertices > 0 && !vertices) || (n_rows > 0 && (!boxes || !inside))) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, S, S) || check_paste(fn, paste, n_paste, sel_i, sel_f, S)) return -1;
-    if (n_vertices < 0 || n_vertices > 0x7fffffffLL / 2 || n_label_rows < 0 || n_label_rows > 0x7fffffffLL || n_rows < 0 || n_rows > 0x7fffffffLL / 6)
-        Y3_FAIL("%s: bad geometry (%lld vertices, %lld label rows, a workspace of %lld rows)", fn, (long long)n_vertices, (long long)n_label_rows, (long long)n_rows);
-    if (!aligned(vertex_offsets, 8) || !aligned(label_offsets, 8) || !aligned(boxes, 8) || !aligned(vertices, 4) || !aligned(inside, 4) || !aligned(paths, 4))
-        Y3_FAIL("%s: the offsets and the boxes must be 8-byte, the vertices and the int32 words 4-byte aligned", fn);
-    if (count == 0) return 0;
-    TargetArgs a = {};
-    a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items; a.count = count; a.H = S; a.W = S;
-    PolyTables p = {};
-    p.verts = vertices; p.vert_offsets = (const long long*)vertex_offsets; p.n_verts = n_vertices; p.n_vert_rows = n_label_rows;
-    p.boxes = boxes; p.inside = inside; p.paths = paths; p.ws_rows = n_rows;
-    PasteTables c = {};
-    c.table = paste; c.nk = n_paste; c.sel_i = const_cast<int*>(sel_i); c.sel_f = const_cast<float*>(sel_f);
-    hipLaunchKernelGGL(augment_polygons_kernel<true>, dim3((unsigned)count * 2), dim3(BT), 0, (hipStream_t)stream, a, p, c);
-    Y3_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int y3_augment_targets_paste(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const y3_augment_item* items,
-                                        int32_t count, int32_t S, const int32_t* paste, int32_t n_paste, const int32_t* sel_i, const float* sel_f, const double* boxes,
-                                        const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows, int64_t* offsets, void* stream) {
-    const char* fn = "y3_augment_targets_paste";
-    if (!label_offsets || !offsets || (count > 0 && !paths) || (n_rows > 0 && (!labels || !targets || !boxes || !inside))) Y3_FAIL("%s: null argument", fn);
-    if (check_set(fn, images, n_images, items, count, S, S) || check_paste(fn, paste, n_paste, sel_i, sel_f, S)) return -1;
-    if (n_rows < 0 || n_rows > 0x7fffffffLL / 6) Y3_FAIL("%s: bad geometry (%lld rows)", fn, (long long)n_rows);
-    if (!aligned(label_offsets, 8) || !aligned(offsets, 8) || !aligned(boxes, 8) || !aligned(labels, 4) || !aligned(targets, 4) || !aligned(inside, 4) || !aligned(paths, 4))
-        Y3_FAIL("%s: the offsets and the boxes must be 8-byte, the fp32 tables and the int32 words 4-byte aligned", fn);
-    TargetArgs a;
-    a.labels = labels; a.label_offsets = (const long long*)label_offsets; a.images = images; a.n_images = n_images; a.items = items;
-    a.out = targets; a.n_rows = n_rows; a.out_offsets = (long long*)offsets; a.count = count; a.H = S; a.W = S;
-    a.clip_w = a.clip_h = (float)((double)S - 1e-3);
-    PolyTables p = {};
-    p.boxes = const_cast<double*>(boxes); p.inside = const_cast<int*>(inside); p.paths = const_cast<int*>(paths); p.ws_rows = n_rows;
-    PasteTables c = {};
-    c.table = paste; c.nk = n_paste; c.sel_i = const_cast<int*>(sel_i); c.sel_f = const_cast<float*>(sel_f);
-    hipLaunchKernelGGL((augment_targets_kernel<true, true>), dim3(1), dim3(BT), 0, (hipStream_t)stream, a, p, c);
-    Y3_CHECK_LAUNCH();
-    return 0;
-}

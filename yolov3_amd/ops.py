@@ -1026,37 +1026,92 @@ def dataset_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: t
 AUGMENT_ITEM_BYTES = 1360   # sizeof(y3_augment_item)
 
 
-def _augment_args(what: str, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int):
+# The augment wrappers.  Every argument group has one validator, whose refusal carries `what`, the name of the public wrapper the caller used; a public wrapper is its
+# refusals in their order, the allocation of what its export writes, and _call.  `batch`: what _augment_args returns, (images, n, items, count) as the exports take them.
+
+
+def _augment_args(what: str, images: torch.Tensor, n: int, items: torch.Tensor, count: int, *sides: int):
     require_gpu(images, what)
     require_gpu(items, what)
     if images.dtype != torch.uint8 or images.dim() != 1 or not images.is_contiguous() or images.numel() != 32 * n:
         raise TypeError(f"{what} expects the contiguous record table of the set: uint8 ({32 * n},)")
     if items.dtype != torch.uint8 or items.dim() != 1 or not items.is_contiguous() or count < 0 or items.numel() < AUGMENT_ITEM_BYTES * count:
         raise TypeError(f"{what} expects the contiguous item records of the batch: uint8, at least {AUGMENT_ITEM_BYTES * count} bytes")
-    if size < 16 or size % 16:
-        raise ValueError(f"{what}: the image size {size} is not a multiple of 16")
+    for size in sides:
+        if size < 16 or size % 16:
+            raise ValueError(f"{what}: the image size {size} is not a multiple of 16")
+    return images.data_ptr(), int(n), items.data_ptr(), int(count)
 
 
-def _augment_batch(what: str, arena, images, n, items, count, height, width, dtype, out):
-    """augment_batch / augment_batch_hw: the square export for the one, the (H, W) export for the other"""
-    require_gpu(arena, what)
-    for side in dict.fromkeys((height, width)):
-        _augment_args(what, images, n, items, count, side)
+def _table(what: str, t: torch.Tensor, cols: int, name: str, nonempty: bool = False):
+    """the label table (cols 5, name "(total, 5) label") or the vertex table (2, "(V, 2) vertex") of the set"""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous() or (nonempty and not t.numel()):
+        raise TypeError(f"{what} expects the contiguous{', non-empty' if nonempty else ''} fp32 {name} table")
+
+
+def _offsets(what: str, t: torch.Tensor, k: int | None, name: str):
+    """the int64 offsets of the label table (k = images + 1) or of the vertex table (k = label rows + 1; None: one at least)"""
+    if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or (t.numel() < 1 if k is None else t.numel() != k):
+        raise TypeError(f"{what} expects contiguous int64 {name} offsets, one per label row plus one" if k is None else f"{what} expects {k} contiguous int64 {name} offsets")
+
+
+def _arena(what: str, arena: torch.Tensor, dtype: torch.dtype):
     if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
         raise TypeError(f"{what} expects the contiguous uint8 arena of the set")
     if dtype not in DTYPE_CODE:
         raise TypeError(f"{what} writes uint8 / float16 / bfloat16 / float32, not {dtype}")
-    shape = (int(count), 3, int(height), int(width))
+
+
+def _out(what: str, out: torch.Tensor | None, shape: tuple, dtype: torch.dtype, device) -> torch.Tensor:
     if out is None:
-        out = torch.empty(shape, dtype=dtype, device=arena.device)
-    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != arena.device or not out.is_contiguous():
-        raise TypeError(f"{what}: `out` must be a contiguous {shape} {dtype} tensor on {arena.device}")
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise TypeError(f"{what}: `out` must be a contiguous {shape} {dtype} tensor on {device}")
+    return out
+
+
+def _polygon_workspace(what: str, n_rows: int, count: int, device=None, given=None):
+    """(boxes, inside, paths) of a batch: allocated on `device`, or `given` checked to be what augment_polygons allocated for it"""
+    spec = ((torch.float64, (int(n_rows), 4)), (torch.int32, (int(n_rows),)), (torch.int32, (int(count), 2)))
+    if given is None:
+        return tuple(torch.empty(shape, dtype=dt, device=device) for dt, shape in spec)
+    for t, (dt, shape) in zip(given, spec):
+        require_gpu(t, what)
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"{what} expects the contiguous {dt} {shape} workspace of augment_polygons")
+    return given
+
+
+def _data(t: torch.Tensor):
+    return t.data_ptr() if t.numel() else None
+
+
+def _call(export: str, *args):
+    check(getattr(_lib.lib(), export)(*args, stream_ptr()), export)
+
+
+def _polygons(export: str, vertices, vertex_offsets, label_offsets, batch, size, n_rows, paste=()):
+    ws = _polygon_workspace(export, n_rows, batch[3], vertices.device)
+    _call(export, _data(vertices), vertices.shape[0], vertex_offsets.data_ptr(), vertex_offsets.numel() - 1, label_offsets.data_ptr(), *batch, int(size), *paste,
+          *map(_data, ws), int(n_rows))
+    return ws
+
+
+def _targets(export: str, labels, label_offsets, batch, sides, n_rows, ws=(), paste=()):
+    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
+    offsets = torch.empty(batch[3] + 1, dtype=torch.int64, device=labels.device)
+    _call(export, _data(labels), label_offsets.data_ptr(), *batch, *map(int, sides), *paste, *map(_data, ws), _data(targets), int(n_rows), offsets.data_ptr())
+    return targets, offsets
+
+
+def _augment_batch(what: str, export: str, arena, images, n, items, count, sides, dtype, out):
+    """augment_batch (sides = (S,)) and augment_batch_hw (sides = (H, W)), each with its own export"""
+    require_gpu(arena, what)
+    batch = _augment_args(what, images, n, items, count, *sides)
+    _arena(what, arena, dtype)
+    out = _out(what, out, (int(count), 3, int(sides[0]), int(sides[-1])), dtype, arena.device)
     if count:
-        head = (arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), items.data_ptr(), int(count), out.data_ptr(), DTYPE_CODE[dtype])
-        if what == "augment_batch":
-            check(_lib.lib().y3_augment_batch(*head, int(height), stream_ptr()), "y3_augment_batch")
-        else:
-            check(_lib.lib().y3_augment_batch_hw(*head, int(height), int(width), stream_ptr()), "y3_augment_batch_hw")
+        _call(export, arena.data_ptr(), arena.numel(), *batch, out.data_ptr(), DTYPE_CODE[dtype], *map(int, sides))
     return out
 
 
@@ -1065,46 +1120,35 @@ def augment_batch(arena: torch.Tensor, images: torch.Tensor, n: int, items: torc
     """One augmented batch of a device-resident dataset in one launch (y3_augment_batch): `arena` / `images` as for dataset_batch, `items` the batch's
     y3_augment_item records as bytes (1360 each, what augment.pack_items forms) -> (count, 3, size, size) in `dtype`: mosaic, affine warp, mixup, HSV and the flips
     applied, CHW, RGB.  `out`: a contiguous, 16-byte aligned tensor of that shape and dtype to write into."""
-    return _augment_batch("augment_batch", arena, images, n, items, count, size, size, dtype, out)
+    return _augment_batch("augment_batch", "y3_augment_batch", arena, images, n, items, count, (size,), dtype, out)
 
 
 def augment_batch_hw(arena: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, height: int, width: int, dtype: torch.dtype = torch.uint8,
                      out: torch.Tensor | None = None) -> torch.Tensor:
     """augment_batch for items of `height` rows and `width` columns, the batch shape of a rect=True set (y3_augment_batch_hw; both multiples of 16) ->
     (count, 3, height, width) in `dtype`."""
-    return _augment_batch("augment_batch_hw", arena, images, n, items, count, height, width, dtype, out)
+    return _augment_batch("augment_batch_hw", "y3_augment_batch_hw", arena, images, n, items, count, (height, width), dtype, out)
 
 
-def _augment_targets(what: str, labels, label_offsets, images, n, items, count, height, width, n_rows):
-    """augment_targets / augment_targets_hw: the square export for the one, the (H, W) export for the other"""
+def _augment_targets(what: str, export: str, labels, label_offsets, images, n, items, count, sides, n_rows, ws=()):
+    """the targets wrappers without a paste, each with its own export: sides = (S,) or (H, W), `ws` the workspace of the polygon form"""
     require_gpu(labels, what)
     require_gpu(label_offsets, what)
-    for side in dict.fromkeys((height, width)):
-        _augment_args(what, images, n, items, count, side)
-    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
-        raise TypeError(f"{what} expects the contiguous fp32 (total, 5) label table")
-    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
-        raise TypeError(f"{what} expects {n + 1} contiguous int64 label offsets")
-    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
-    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
-    head = (labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count))
-    tail = (targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr())
-    if what == "augment_targets":
-        check(_lib.lib().y3_augment_targets(*head, int(height), *tail), "y3_augment_targets")
-    else:
-        check(_lib.lib().y3_augment_targets_hw(*head, int(height), int(width), *tail), "y3_augment_targets_hw")
-    return targets, offsets
+    batch = _augment_args(what, images, n, items, count, *sides)
+    _table(what, labels, 5, "(total, 5) label")
+    _offsets(what, label_offsets, n + 1, "label")
+    return _targets(export, labels, label_offsets, batch, sides, n_rows, ws and _polygon_workspace(what, n_rows, count, given=ws))
 
 
 def augment_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int, n_rows: int):
     """The targets of one augmented batch (y3_augment_targets): `n_rows` the label count of all tiles of the batch, an upper bound of the survivors ->
     (DEVICE fp32 (n_rows, 6) [item in batch, cls, x, y, w, h], DEVICE int64 (count + 1,) offsets); only the first offsets[count] rows are written."""
-    return _augment_targets("augment_targets", labels, label_offsets, images, n, items, count, size, size, n_rows)
+    return _augment_targets("augment_targets", "y3_augment_targets", labels, label_offsets, images, n, items, count, (size,), n_rows)
 
 
 def augment_targets_hw(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, height: int, width: int, n_rows: int):
     """augment_targets for items of `height` rows and `width` columns (y3_augment_targets_hw): the boxes are clipped and normalised per axis."""
-    return _augment_targets("augment_targets_hw", labels, label_offsets, images, n, items, count, height, width, n_rows)
+    return _augment_targets("augment_targets_hw", "y3_augment_targets_hw", labels, label_offsets, images, n, items, count, (height, width), n_rows)
 
 
 def augment_polygons(vertices: torch.Tensor, vertex_offsets: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int,
@@ -1114,48 +1158,20 @@ def augment_polygons(vertices: torch.Tensor, vertex_offsets: torch.Tensor, label
     DEVICE int32 (n_rows,) whether a point lay inside, DEVICE int32 (count, 2) the path word per item and mosaic: 1 = the polygon path).  Positions of letterbox items
     are not written."""
     what = "augment_polygons"
-    require_gpu(vertices, what)
-    require_gpu(vertex_offsets, what)
-    require_gpu(label_offsets, what)
-    _augment_args(what, images, n, items, count, size)
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 2 or not vertices.is_contiguous():
-        raise TypeError("augment_polygons expects the contiguous fp32 (V, 2) vertex table")
-    if vertex_offsets.dtype != torch.int64 or vertex_offsets.dim() != 1 or vertex_offsets.numel() < 1 or not vertex_offsets.is_contiguous():
-        raise TypeError("augment_polygons expects contiguous int64 vertex offsets, one per label row plus one")
-    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
-        raise TypeError(f"augment_polygons expects {n + 1} contiguous int64 label offsets")
-    dev = vertices.device
-    boxes = torch.empty(int(n_rows), 4, dtype=torch.float64, device=dev)
-    inside = torch.empty(int(n_rows), dtype=torch.int32, device=dev)
-    paths = torch.empty(int(count), 2, dtype=torch.int32, device=dev)
-    check(_lib.lib().y3_augment_polygons(vertices.data_ptr() if vertices.numel() else None, vertices.shape[0], vertex_offsets.data_ptr(), vertex_offsets.numel() - 1,
-                                         label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count), int(size), boxes.data_ptr() if n_rows else None,
-                                         inside.data_ptr() if n_rows else None, paths.data_ptr() if count else None, int(n_rows), stream_ptr()), "y3_augment_polygons")
-    return boxes, inside, paths
+    for t in (vertices, vertex_offsets, label_offsets):
+        require_gpu(t, what)
+    batch = _augment_args(what, images, n, items, count, size)
+    _table(what, vertices, 2, "(V, 2) vertex")
+    _offsets(what, vertex_offsets, None, "vertex")
+    _offsets(what, label_offsets, n + 1, "label")
+    return _polygons("y3_augment_polygons", vertices, vertex_offsets, label_offsets, batch, size, n_rows)
 
 
 def augment_targets_polygons(labels: torch.Tensor, label_offsets: torch.Tensor, images: torch.Tensor, n: int, items: torch.Tensor, count: int, size: int, n_rows: int,
                              boxes: torch.Tensor, inside: torch.Tensor, paths: torch.Tensor):
     """augment_targets for a set with polygon labels (y3_augment_targets_polygons): `boxes`, `inside`, `paths` as augment_polygons returned them for this batch; a mosaic
     whose path word is 1 takes the polygon boxes with area_thr 0.01, every other the four corners with 0.10."""
-    what = "augment_targets_polygons"
-    require_gpu(labels, what)
-    require_gpu(label_offsets, what)
-    _augment_args(what, images, n, items, count, size)
-    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous():
-        raise TypeError("augment_targets_polygons expects the contiguous fp32 (total, 5) label table")
-    if label_offsets.dtype != torch.int64 or label_offsets.dim() != 1 or label_offsets.numel() != n + 1 or not label_offsets.is_contiguous():
-        raise TypeError(f"augment_targets_polygons expects {n + 1} contiguous int64 label offsets")
-    for t, dt, shape in ((boxes, torch.float64, (int(n_rows), 4)), (inside, torch.int32, (int(n_rows),)), (paths, torch.int32, (int(count), 2))):
-        require_gpu(t, what)
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise TypeError(f"augment_targets_polygons expects the contiguous {dt} {shape} workspace of augment_polygons")
-    targets = torch.empty(int(n_rows), 6, dtype=torch.float32, device=labels.device)
-    offsets = torch.empty(int(count) + 1, dtype=torch.int64, device=labels.device)
-    check(_lib.lib().y3_augment_targets_polygons(labels.data_ptr() if labels.numel() else None, label_offsets.data_ptr(), images.data_ptr(), int(n), items.data_ptr(), int(count),
-                                                 int(size), boxes.data_ptr() if n_rows else None, inside.data_ptr() if n_rows else None, paths.data_ptr() if count else None,
-                                                 targets.data_ptr() if n_rows else None, int(n_rows), offsets.data_ptr(), stream_ptr()), "y3_augment_targets_polygons")
-    return targets, offsets
+    return _augment_targets("augment_targets_polygons", "y3_augment_targets_polygons", labels, label_offsets, images, n, items, count, (size,), n_rows, (boxes, inside, paths))
 
 
 _paste_ws: dict = {}   # device -> the int32 words of the copy-paste masks, grown on demand and cleared per batch
@@ -1173,29 +1189,19 @@ def augment_copy_paste(labels: torch.Tensor, label_offsets: torch.Tensor, vertic
     what = "augment_copy_paste"
     for t in (labels, label_offsets, vertices, vertex_offsets, arena, paste):
         require_gpu(t, what)
-    _augment_args(what, images, n, items, count, size)
-    if labels.dtype != torch.float32 or labels.dim() != 2 or labels.shape[1] != 5 or not labels.is_contiguous() or not labels.numel():
-        raise TypeError(f"{what} expects the contiguous, non-empty fp32 (total, 5) label table")
-    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 2 or not vertices.is_contiguous() or not vertices.numel():
-        raise TypeError(f"{what} expects the contiguous, non-empty fp32 (V, 2) vertex table")
-    for t, k, name in ((label_offsets, n + 1, "label"), (vertex_offsets, labels.shape[0] + 1, "vertex")):
-        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != k or not t.is_contiguous():
-            raise TypeError(f"{what} expects {k} contiguous int64 {name} offsets")
-    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
-        raise TypeError(f"{what} expects the contiguous uint8 arena of the set")
-    if dtype not in DTYPE_CODE:
-        raise TypeError(f"{what} writes uint8 / float16 / bfloat16 / float32, not {dtype}")
+    batch = _augment_args(what, images, n, items, count, size)
+    _table(what, labels, 5, "(total, 5) label", nonempty=True)
+    _table(what, vertices, 2, "(V, 2) vertex", nonempty=True)
+    _offsets(what, label_offsets, n + 1, "label")
+    _offsets(what, vertex_offsets, labels.shape[0] + 1, "vertex")
+    _arena(what, arena, dtype)
     n_paste, n_masks, count, size, n_rows = int(n_paste), int(n_masks), int(count), int(size), int(n_rows)
     if count < 1 or n_paste < 1 or not 1 <= n_masks <= 2 * count or n_rows < n_paste:
         raise ValueError(f"{what}: {n_paste} candidates in {n_masks} mosaics of {count} items, {n_rows} rows")
     if paste.dtype != torch.int32 or paste.dim() != 1 or not paste.is_contiguous() or paste.numel() != 4 * count + 1 + n_paste:
         raise TypeError(f"{what} expects the contiguous int32 paste table of the batch: {4 * count + 1 + n_paste} words")
     dev = labels.device
-    shape = (count, 3, size, size)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=dev)
-    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
-        raise TypeError(f"{what}: `out` must be a contiguous {shape} {dtype} tensor on {dev}")
+    out = _out(what, out, (count, 3, size, size), dtype, dev)
     words = n_masks * 2 * size * (2 * size // 32)
     ws = _paste_ws.get(dev)
     if ws is None or ws.numel() < words:
@@ -1203,24 +1209,15 @@ def augment_copy_paste(labels: torch.Tensor, label_offsets: torch.Tensor, vertic
     masks = ws[:words].zero_()
     sel_i = torch.empty(n_paste, 4, dtype=torch.int32, device=dev)
     sel_f = torch.empty(n_paste, 5, dtype=torch.float32, device=dev)
-    boxes = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
-    inside = torch.empty(n_rows, dtype=torch.int32, device=dev)
-    paths = torch.empty(count, 2, dtype=torch.int32, device=dev)
-    targets = torch.empty(n_rows, 6, dtype=torch.float32, device=dev)
-    offsets = torch.empty(count + 1, dtype=torch.int64, device=dev)
-    lib, st = _lib.lib(), stream_ptr()
-    verts = (vertices.data_ptr(), vertices.shape[0], vertex_offsets.data_ptr(), vertex_offsets.numel() - 1)
-    batch = (images.data_ptr(), int(n), items.data_ptr(), count, size, paste.data_ptr(), n_paste)
-    check(lib.y3_augment_copy_paste_select(labels.data_ptr(), label_offsets.data_ptr(), vertex_offsets.data_ptr(), vertices.shape[0], vertex_offsets.numel() - 1, *batch,
-                                           sel_i.data_ptr(), sel_f.data_ptr(), st), "y3_augment_copy_paste_select")
-    check(lib.y3_augment_copy_paste_raster(*verts, label_offsets.data_ptr(), *batch, sel_i.data_ptr(), masks.data_ptr(), n_masks, st), "y3_augment_copy_paste_raster")
-    check(lib.y3_augment_batch_paste(arena.data_ptr(), arena.numel(), images.data_ptr(), int(n), items.data_ptr(), count, out.data_ptr(), DTYPE_CODE[dtype], size,
-                                     paste.data_ptr(), masks.data_ptr(), n_masks, st), "y3_augment_batch_paste")
-    check(lib.y3_augment_polygons_paste(*verts, label_offsets.data_ptr(), *batch, sel_i.data_ptr(), sel_f.data_ptr(), boxes.data_ptr(), inside.data_ptr(), paths.data_ptr(),
-                                        n_rows, st), "y3_augment_polygons_paste")
-    check(lib.y3_augment_targets_paste(labels.data_ptr(), label_offsets.data_ptr(), *batch, sel_i.data_ptr(), sel_f.data_ptr(), boxes.data_ptr(), inside.data_ptr(),
-                                       paths.data_ptr(), targets.data_ptr(), n_rows, offsets.data_ptr(), st), "y3_augment_targets_paste")
-    return out, targets, offsets, (boxes, inside, paths), (sel_i, sel_f, masks.view(n_masks, 2 * size, 2 * size // 32))
+    n_vertices, n_label_rows = vertices.shape[0], vertex_offsets.numel() - 1
+    selection = (paste.data_ptr(), n_paste, sel_i.data_ptr(), sel_f.data_ptr())   # (paste, n_paste, sel_i, sel_f) as the three exports after the raster take them
+    _call("y3_augment_copy_paste_select", labels.data_ptr(), label_offsets.data_ptr(), vertex_offsets.data_ptr(), n_vertices, n_label_rows, *batch, size, *selection)
+    _call("y3_augment_copy_paste_raster", vertices.data_ptr(), n_vertices, vertex_offsets.data_ptr(), n_label_rows, label_offsets.data_ptr(), *batch, size,
+          paste.data_ptr(), n_paste, sel_i.data_ptr(), masks.data_ptr(), n_masks)
+    _call("y3_augment_batch_paste", arena.data_ptr(), arena.numel(), *batch, out.data_ptr(), DTYPE_CODE[dtype], size, paste.data_ptr(), masks.data_ptr(), n_masks)
+    polygons = _polygons("y3_augment_polygons_paste", vertices, vertex_offsets, label_offsets, batch, size, n_rows, selection)
+    targets, offsets = _targets("y3_augment_targets_paste", labels, label_offsets, batch, (size,), n_rows, polygons, selection)
+    return out, targets, offsets, polygons, (sel_i, sel_f, masks.view(n_masks, 2 * size, 2 * size // 32))
 
 
 _coco_ws: dict = {}
