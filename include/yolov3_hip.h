@@ -409,6 +409,26 @@ int y3_dataset_batch(const uint8_t* arena, int64_t arena_bytes, const y3_dataset
 int y3_dataset_targets(const float* labels, const int64_t* label_offsets, const y3_dataset_image* images, int64_t n_images, const int64_t* indices, int64_t first,
                        int32_t count, int32_t H, int32_t W, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
 
+/* The same set kept in pinned HOST memory, one batch of it staged into a small device ring (csrc/dataset_stage.hip).  The host knows the images of a batch before any
+ * pixel is touched, so dataset_stage copies just those, in ONE launch that reads the host arena over PCIe: the exports above and below then take (ring, dst_images)
+ * where they take (arena, images) of a resident set.  Nothing here allocates or synchronises.
+ * host_arena: HOST uint8, pinned and mapped (hipHostMalloc / hipHostRegister), 16-byte aligned, host_bytes a positive multiple of 16; its device-visible address is
+ *   taken from hipPointerGetAttributes, and a range that is not pinned, mapped host memory is refused before anything is launched.  src_images: DEVICE table of
+ *   n_images records whose `offset` is the image's first byte in host_arena, a multiple of 16.  dst_images: DEVICE table of n_images records, the ring's.
+ * jobs: DEVICE int64 (m, 3), 8-byte aligned: per job the image, the offset of its slot in the ring (a multiple of 16) and the chunks of all jobs up to and including
+ *   this one -- a job owns ceil(slot / y3_dataset_stage_chunk_bytes()) chunks, slot = 3 h w rounded up to 16; n_chunks is the last count, the launch's blocks.
+ * Per job: ring[slot offset ..] = the image's 3 h w bytes, then zeros up to the slot's end, and dst_images[image] = src_images[image] with `offset` the slot's; no
+ *   other record and no byte of the ring outside the slots is written.  Whatever the jobs and the records hold, no read leaves [host_arena, host_arena + host_bytes)
+ *   and no write leaves the ring or dst_images: a job that would -- an image outside [0, n_images), a source range or a slot that does not fit, a misaligned offset,
+ *   a chunk count above its predecessor's by another number than its slot's chunks -- is skipped by every block it owns, and its first block adds 1 to *status
+ *   (DEVICE int32, which the caller zeroes once and reads when it reads the batch).  The table lives on the device, so what no block sees is the caller's to get
+ *   right and is NOT reported: a job that owns no chunk (a running count equal to its predecessor's) is neither copied nor counted, and with n_chunks below the last
+ *   running count the blocks past it do not run and the last jobs stay partly copied; dataset.stage_jobs (Python) forms the counts and n_chunks from one array.
+ * Limits: m <= 8192 (m == 0 launches nothing), n_chunks < 2^31. */
+int64_t y3_dataset_stage_chunk_bytes(void);
+int y3_dataset_stage(const uint8_t* host_arena, int64_t host_bytes, const y3_dataset_image* src_images, int64_t n_images, const int64_t* jobs, int32_t m, int64_t n_chunks,
+                     uint8_t* ring, int64_t ring_bytes, y3_dataset_image* dst_images, int32_t* status, void* stream);
+
 /* The train-mode loader over the same arena and record table (csrc/augment.hip): the augment=True path of reference utils/dataloaders.py:659-735, 764-822
  * and utils/augmentations.py:57-73, 137-216, 270-283 -- mosaic, random_perspective (affine only), mixup, augment_hsv, the flips, collate_fn.  The host draws the random
  * numbers and sends one y3_augment_item per item of the batch (DEVICE, 8-byte aligned); nothing here allocates or synchronises.

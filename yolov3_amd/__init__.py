@@ -24,6 +24,8 @@ Public surface mirrors the reference's own Python signatures:
                                          the reference's random stream; polygon labels (segments=) warp as 1000 resampled points per polygon in one more launch)
     DeviceRectTrainDataset               (reference utils/dataloaders.py:547-570, 659-735; utils/augmentations.py:104-216: the augment=True, rect=True loader of train.py --rect --
                                          the set in aspect-ratio order, every batch letterboxed to its own (H, W), affine warp, HSV and flips in the same two launches)
+    store="host" on the three datasets   (the `--cache ram` cache where the reference keeps it: the images in pinned host memory, the images of the next batch staged into a
+                                         small HBM ring by one launch on a side stream while the current step trains; the same batches bit for bit, for sets larger than HBM)
     multi_scale_size / resize_batch / preprocess_batch / quad_collate   (reference train.py:380,394-399 and utils/dataloaders.py:833-858 collate_fn4: the uint8 batch divided by 255 and
                                          resized for --multi-scale in one launch; the --quad collate in one launch)
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)

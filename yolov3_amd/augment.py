@@ -56,8 +56,25 @@ Refused (ValueError) before anything is uploaded: hyp["perspective"] != 0, hyp["
 (DeviceRectTrainDataset is that loader), an image whose long side is not img_size (load_image's resize is not here), an img_size that is odd or no multiple of 16; on a
 rect set an image that letterbox(scaleup=True) would resize (r = min(H / h, W / w) != 1; the message names the image, its size and the batch shape), an img_size or
 stride that is no multiple of 16, and set_indices (the batch shapes belong to the order); KeyError for a missing hyp key.  Albumentations is a no-op, as in the
-reference when the package is absent.  Out of scope: warpPerspective, a resize inside letterbox, load_mosaic9, cutout, prefetching, returning the warped
-polygons.
+reference when the package is absent.  Out of scope: warpPerspective, a resize inside letterbox, load_mosaic9, cutout, returning the warped polygons.
+
+A set larger than HBM (store="host", both classes and their from_dataset; dataset.HostStore): the images stay in one pinned host tensor and the device holds a ring of
+two halves, each sized for the worst batch -- the min(n, t batch_size) largest images, t = 4 for mosaics, 8 when hyp["mixup"] > 0, 1 for a rect set and for mosaic=False --
+with its own copy of the record table.  The host knows the images of a batch once its items are drawn (at most 4 per item, 8 with mixup); dataset.plan_slots gives each
+unique image a slot in a half, the job table rides up behind the batch's records (and its copy-paste candidates) in the same pinned copy, and ONE launch of
+y3_dataset_stage (csrc/dataset_stage.hip) copies those images over PCIe and writes their records with the slots' offsets; the launches above then read (ring half, its
+table) where they read (arena, table).  No sampling kernel changes and the batches are bit-identical.  prefetch=1 (the default under store="host"): when __iter__
+hands out batch k, the items of batch k + 1 are drawn and their stage is launched on a side stream the set owns, so the copy runs under the caller's step on batch k
+whatever that step does; events make the stage wait for the last launches that read the half it overwrites (batch k - 1's) and batch k + 1's launches wait for the
+stage.  prefetch=0 draws and stages inside get_batch, on the current stream, exactly where the resident path draws.  get_batch(k) out of turn always works, staging on
+the current stream into the half that the batch staged ahead does not occupy.  A stated difference: with prefetch=1 the draws of batch k + 1 are made one batch earlier
+in the process's `random` / `np.random` streams, so a caller that draws between batches (multi_scale_size) sees another interleaving than with prefetch=0 -- the
+reference's own worker processes fix no such interleaving -- and the batches themselves are unaffected.  The host's draws for batch k + 1 (about 2 ms for 64 mosaics)
+stand between batch k and the launch of its step; profiles/dataset_stream_ab.txt has what that costs against a loop whose step ends in a host synchronise and one
+whose step does not.  Refused
+(ValueError) before anything is pinned or uploaded: an unknown store, prefetch not in (0, 1), prefetch=1 with store="device".  .host_bytes and .ring_bytes tell what the
+set takes on either side (0 for a resident set).  The stage's status word (jobs the kernel skipped because they did not fit: none for a plan of this module) is read
+right after the batch's offsets; RuntimeError if it is not zero.
 """
 from __future__ import annotations
 
@@ -301,7 +318,7 @@ class _DeviceAugmentDataset(DeviceDataset):
         return hyp
 
     @classmethod
-    def _cached(cls, dataset, batch_size, device, dtype, single_cls, copy_paste):
+    def _cached(cls, dataset, batch_size, device, dtype, single_cls, copy_paste, store="device", prefetch=None):
         """from_dataset's shared refusals -> (the cached images, the constructor arguments both classes read from the dataset)"""
         ims = list(dataset.ims)
         if any(im is None for im in ims):
@@ -309,7 +326,7 @@ class _DeviceAugmentDataset(DeviceDataset):
         if not getattr(dataset, "augment", False):
             raise ValueError(f"{cls.__name__}.from_dataset: the dataset does not augment (augment=False); use DeviceDataset")
         return ims, dict(img_size=dataset.img_size, batch_size=batch_size, stride=dataset.stride, shapes0=[tuple(hw0) for hw0 in dataset.im_hw0], paths=dataset.im_files,
-                         single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), copy_paste=copy_paste)
+                         single_cls=single_cls, device=device, dtype=dtype, segments=getattr(dataset, "segments", None), copy_paste=copy_paste, store=store, prefetch=prefetch)
 
     def _set_up(self, hyp, images, mosaic=False, poly_counts=None):
         """what draw_batch reads, and the pinned records of one batch with their device twin; the copy-paste candidates of a batch ride behind its records"""
@@ -317,21 +334,59 @@ class _DeviceAugmentDataset(DeviceDataset):
         self.hw = [tuple(int(v) for v in images[i].shape[:2]) for i in self.order]   # in the set's order, as the record table is
         nbytes = self.batch_size * ITEM.itemsize
         room = 0 if poly_counts is None else 4 * (4 * self.batch_size + 1 + 8 * self.batch_size * max(poly_counts))
+        self._room = nbytes + room
+        if self._store is not None:   # store="host": each half of the ring has its own pinned records and device twin, the stage's jobs behind them
+            self._store.reserve(self._room)
+            return
         self._stage = torch.empty(nbytes + room, dtype=torch.uint8).pin_memory()
         self._stage_rec = self._stage.numpy()[:nbytes].view(ITEM)
         self._items_dev = torch.empty(nbytes + room, dtype=torch.uint8, device=self.device)
 
-    def _upload_items(self, items, table=None):
-        """pack the records of the batch, the int32 `table` behind them, and make the one host -> device copy of the batch -> the table on the device, or None"""
-        pack_items(items, self._stage_rec[: len(items)])
+    def _pack(self, items, stage, items_dev):
+        """Pack the records of the batch, and behind them the int32 table of `_paste`, into the pinned `stage` -> (the bytes packed, None or (the table's place in
+        `items_dev`, its candidates, its mosaics with candidates)): what travels with a staged batch, so the launches pair the table with the counts it was made with."""
+        paste = self._paste(items)
         nbytes = end = len(items) * ITEM.itemsize
-        if table is not None:
-            end = nbytes + table.nbytes
-            if end > self._stage.numel():
-                raise ValueError(f"{type(self).__name__}: {table.size - 4 * len(items) - 1} copy-paste candidates in one batch exceed the staging buffer (items drawn for another set?)")
-            self._stage.numpy()[nbytes:end].view(np.int32)[:] = table
+        if paste is not None:
+            end = nbytes + paste[0].nbytes
+        if end > self._room:
+            raise ValueError(f"{type(self).__name__}: {0 if paste is None else paste[0].size - 4 * len(items) - 1} copy-paste candidates in one batch exceed the staging buffer (items drawn for another set?)")
+        pack_items(items, stage.numpy()[:nbytes].view(ITEM))
+        if paste is None:
+            return end, None
+        stage.numpy()[nbytes:end].view(np.int32)[:] = paste[0]
+        return end, (items_dev[nbytes:end].view(torch.int32), paste[1], paste[2])
+
+    def _upload_items(self, items):
+        """pack the records of the batch and the table behind them and make the one host -> device copy of the batch -> what _pack returns second"""
+        end, paste = self._pack(items, self._stage, self._items_dev)
         self._items_dev[:end].copy_(self._stage[:end], non_blocking=True)
-        return None if table is None else self._items_dev[nbytes:end].view(torch.int32)
+        return paste
+
+    def _paste(self, items):
+        """(the int32 table that rides behind the records of the batch, its candidates, its mosaics with candidates) or None: pack_paste for a DeviceTrainDataset batch that pastes"""
+        return None
+
+    @staticmethod
+    def _needs(items):
+        """the images the launches of the batch read: every tile of every mosaic, at most 4 per item, or 8 with mixup"""
+        return [j for it in items for mo in it.mosaics for j in mo.indices]
+
+    def _source(self, items):
+        """What the launches of the batch read -> (arena, record table, item records, what _pack returns second, the half of the ring or None).  A resident set:
+        its arena and table, after the batch's one host -> device copy.  store="host": a half of the ring with its own table -- the one staged ahead for these
+        `items`, else staged now on the current stream; the records of the batch went up in the same pinned copy as the stage's jobs."""
+        if self._store is None:
+            return self._arena, self._records, self._items_dev, self._upload_items(items), None
+        st = self._store
+        half, paste = st.acquire(items, self._needs(items), lambda stage, dev: self._pack(items, stage, dev))
+        return st.halves[half], st.records[half], st.dev[half], paste, half
+
+    def _stage_ahead(self, k: int) -> dict:
+        """draw the items of batch k now and launch their stage on the store's side stream -> the keywords get_batch(k) takes"""
+        items = self.draw_batch(k)
+        self._store.stage_ahead(items, self._needs(items), lambda stage, dev: self._pack(items, stage, dev))
+        return {"items": items}
 
     def draw_batch(self, k: int):
         """the items of batch k, drawn now from the global generators: a list of Item (a rect set draws every item for its batch's shape, without a mosaic)"""
@@ -342,8 +397,10 @@ class _DeviceAugmentDataset(DeviceDataset):
     def get_batch(self, k: int, out: torch.Tensor | None = None, items=None):
         """Batch k as the reference loader's 4-tuple; `items`: what draw_batch returned for it (default: drawn here)."""
         items = self.draw_batch(k) if items is None else items
-        im, targets, offsets = self._launch(k, items, out)   # the upload, then the launches of the class
+        im, targets, offsets = self._launch(k, items, out)   # the upload (store="host": the stage, unless it ran ahead), then the launches of the class
         nl = int(offsets.cpu()[len(items)])   # the survivors are counted on the device: the one device -> host read (it also frees the staging buffer for the next batch)
+        if self._store is not None:
+            self._store.check()   # the stage's status word, read where the batch is read
         return im, targets[:nl], tuple(self.paths[it.index] for it in items), tuple(None if it.mosaic else self.shapes[it.index] for it in items)
 
 
@@ -355,11 +412,14 @@ class DeviceTrainDataset(_DeviceAugmentDataset):
     (boxes, inside, path words) ops.augment_polygons wrote for it.
     copy_paste: False (the default) refuses a non-zero hyp["copy_paste"] as before -- the default is what it is because existing tests pin that refusal and its text;
     a later change may flip it.  True accepts it: on a set with polygons every load_mosaic draws and pastes as the reference's copy_paste does (`.pastes` holds the
-    selection tables and the masks of the last batch that pasted, else None); a set without polygons and a letterbox item never paste, as in the reference."""
+    selection tables and the masks of the last batch that pasted, else None); a set without polygons and a letterbox item never paste, as in the reference.
+    store / prefetch: "host" keeps the images in pinned host memory and stages each batch's into an HBM ring, by default one batch ahead on a side stream (the module docstring);
+    the default "device" is the resident set."""
 
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, mosaic=True, device="cuda", dtype=torch.uint8,
-                 rect=False, segments=None, copy_paste=False):
+                 rect=False, segments=None, copy_paste=False, store="device", prefetch=None):
         # every refusal comes before anything is uploaded
+        _dataset.check_store("DeviceTrainDataset", store, prefetch)
         hyp = self._read_hyp(hyp, copy_paste)
         polygons = None
         if segments is not None and any(len(sg) for sg in segments):
@@ -374,7 +434,7 @@ class DeviceTrainDataset(_DeviceAugmentDataset):
                 raise ValueError(f"DeviceTrainDataset: image {paths[i] if paths is not None else i} is {im.shape[0]}x{im.shape[1]}: its long side is not img_size = "
                                  f"{img_size} (load_image's cv2.resize is out of scope)")
         super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=False, shapes0=shapes0, paths=paths, single_cls=single_cls,
-                         device=device, dtype=dtype)
+                         device=device, dtype=dtype, store=store, prefetch=prefetch, _per_item=((8 if hyp["mixup"] > 0 else 4) if mosaic else 1))
         self._vertices = self._vertex_offsets = self.polygons = self.pastes = None   # a box-only set: the two launches per batch and nothing else
         if polygons is not None:
             self._vertices, self._vertex_offsets = _dataset._upload(polygons[0], self.device), _dataset._upload(polygons[1], self.device)
@@ -382,10 +442,10 @@ class DeviceTrainDataset(_DeviceAugmentDataset):
         self._set_up(hyp, images, mosaic, [len(sg) for sg in segments] if pasting else None)
 
     @classmethod
-    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False):
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False, store="device", prefetch=None):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=False: reads .ims, .im_hw0, .im_hw, .labels, .segments, .im_files, .hyp,
-        .img_size, .stride, .rect, .mosaic and .indices (the epoch's order).  copy_paste: as for the constructor."""
-        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste)
+        .img_size, .stride, .rect, .mosaic and .indices (the epoch's order).  copy_paste, store, prefetch: as for the constructor."""
+        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste, store, prefetch)
         ds = cls(ims, dataset.labels, dataset.hyp, mosaic=getattr(dataset, "mosaic", True), rect=bool(dataset.rect), **shared)
         indices = getattr(dataset, "indices", None)
         if indices is not None and list(indices) != list(range(ds.n)):
@@ -394,21 +454,29 @@ class DeviceTrainDataset(_DeviceAugmentDataset):
 
     def _launch(self, k, items, out):
         upper = int(sum(self._counts[j] for it in items for mo in it.mosaics for j in mo.indices))
-        batch = (self._records, self.n, self._items_dev, len(items), self.img_size)
-        if self._poly_counts is not None and any(mo.paste for it in items if it.mosaic for mo in it.mosaics):   # some mosaic pastes: the five launches of the copy-paste form
-            table, nk, masks = pack_paste(items)
-            paste = self._upload_items(items, table)
-            im, targets, offsets, self.polygons, self.pastes = ops.augment_copy_paste(self._labels, self._label_offsets, self._vertices, self._vertex_offsets, self._arena, *batch,
-                                                                                      upper + nk, paste, nk, masks, self.dtype, out)
-            return im, targets, offsets
-        self.pastes = None
-        self._upload_items(items)
-        im = ops.augment_batch(self._arena, *batch, self.dtype, out)
-        if self._vertices is None:
-            return (im, *ops.augment_targets(self._labels, self._label_offsets, *batch, upper))
-        # polygon labels: the boxes of the warped polygons first, then the targets that choose per mosaic between them and the four corners
-        self.polygons = ops.augment_polygons(self._vertices, self._vertex_offsets, self._label_offsets, *batch, upper)
-        return (im, *ops.augment_targets_polygons(self._labels, self._label_offsets, *batch, upper, *self.polygons))
+        arena, records, items_dev, paste, half = self._source(items)
+        batch = (records, self.n, items_dev, len(items), self.img_size)
+        try:
+            if paste is not None:   # some mosaic pastes: the five launches of the copy-paste form
+                table, nk, masks = paste
+                im, targets, offsets, self.polygons, self.pastes = ops.augment_copy_paste(self._labels, self._label_offsets, self._vertices, self._vertex_offsets, arena, *batch,
+                                                                                          upper + nk, table, nk, masks, self.dtype, out)
+                return im, targets, offsets
+            self.pastes = None
+            im = ops.augment_batch(arena, *batch, self.dtype, out)
+            if self._vertices is None:
+                return (im, *ops.augment_targets(self._labels, self._label_offsets, *batch, upper))
+            # polygon labels: the boxes of the warped polygons first, then the targets that choose per mosaic between them and the four corners
+            self.polygons = ops.augment_polygons(self._vertices, self._vertex_offsets, self._label_offsets, *batch, upper)
+            return (im, *ops.augment_targets_polygons(self._labels, self._label_offsets, *batch, upper, *self.polygons))
+        finally:
+            if half is not None:
+                self._store.release(half)
+
+    def _paste(self, items):
+        if self._poly_counts is not None and any(mo.paste for it in items if it.mosaic for mo in it.mosaics):
+            return pack_paste(items)
+        return None
 
 
 class DeviceRectTrainDataset(_DeviceAugmentDataset):
@@ -418,11 +486,13 @@ class DeviceRectTrainDataset(_DeviceAugmentDataset):
     letterbox tuple of every item.  hyp: the reference's dict (HYP_KEYS are read; `mosaic` and `mixup` are not used).  segments: accepted and not used, as the
     reference hands none to random_perspective on this branch (area_thr stays 0.10).  The order is the set's: set_indices raises.
     copy_paste: False (the default) refuses a non-zero hyp["copy_paste"] as before (existing tests pin it; a later change may flip it); True accepts the hyp and
-    ignores it: the reference's rect path never calls copy_paste."""
+    ignores it: the reference's rect path never calls copy_paste.
+    store / prefetch: as for DeviceTrainDataset; a rect item reads one image, so a ring half holds the batch_size largest."""
 
     def __init__(self, images, labels, hyp, img_size=640, batch_size=64, stride=32, shapes0=None, paths=None, single_cls=False, device="cuda", dtype=torch.uint8,
-                 segments=None, _adopt=None, copy_paste=False):
+                 segments=None, _adopt=None, copy_paste=False, store="device", prefetch=None):
         # every refusal comes before anything is uploaded
+        _dataset.check_store("DeviceRectTrainDataset", store, prefetch)
         hyp = self._read_hyp(hyp, copy_paste)
         for name, v in (("img_size", img_size), ("stride", stride)):
             if int(v) != v or int(v) < 16 or int(v) % 16:
@@ -430,7 +500,7 @@ class DeviceRectTrainDataset(_DeviceAugmentDataset):
         if all(isinstance(im, np.ndarray) and im.ndim == 3 for im in images) and (shapes0 is None or len(shapes0) == len(images)):   # (else the shared constructor refuses)
             self._refuse_resize(images, [im.shape[:2] for im in images] if shapes0 is None else shapes0, int(img_size), int(batch_size), int(stride), paths, _adopt)
         super().__init__(images, labels, img_size=img_size, batch_size=batch_size, stride=stride, pad=0.0, rect=True, shapes0=shapes0, paths=paths, single_cls=single_cls,
-                         device=device, dtype=dtype, _adopt=_adopt)
+                         device=device, dtype=dtype, _adopt=_adopt, store=store, prefetch=prefetch)
         self._set_up(hyp, images)
 
     @staticmethod
@@ -452,11 +522,11 @@ class DeviceRectTrainDataset(_DeviceAugmentDataset):
                                  "would resize it (r != 1), and cv2.resize is out of scope")
 
     @classmethod
-    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False):
+    def from_dataset(cls, dataset, batch_size, device="cuda", dtype=torch.uint8, single_cls=False, copy_paste=False, store="device", prefetch=None):
         """From a reference LoadImagesAndLabels built with cache="ram", augment=True, rect=True: reads .ims, .im_hw0, .im_hw, .labels, .im_files, .hyp, .img_size,
         .stride, .rect, .augment and, where present, .segments and .batch / .batch_shapes (the aspect-ratio order the dataset is already in is adopted).
-        copy_paste: as for the constructor (True accepts a non-zero hyp["copy_paste"] and ignores it)."""
-        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste)
+        copy_paste: as for the constructor (True accepts a non-zero hyp["copy_paste"] and ignores it); store, prefetch: as for the constructor."""
+        ims, shared = cls._cached(dataset, batch_size, device, dtype, single_cls, copy_paste, store, prefetch)
         if not dataset.rect:
             raise ValueError("DeviceRectTrainDataset.from_dataset: the dataset is not rectangular (rect=False); use DeviceTrainDataset")
         for i, (im, hw) in enumerate(zip(ims, dataset.im_hw)):
@@ -466,7 +536,11 @@ class DeviceRectTrainDataset(_DeviceAugmentDataset):
         return cls(ims, dataset.labels, dataset.hyp, _adopt=adopt, **shared)
 
     def _launch(self, k, items, out):
-        batch = (self._records, self.n, self._items_dev, len(items), *(int(v) for v in self.batch_shapes[k]))
-        self._upload_items(items)
-        im = ops.augment_batch_hw(self._arena, *batch, self.dtype, out)
-        return (im, *ops.augment_targets_hw(self._labels, self._label_offsets, *batch, int(sum(self._counts[it.index] for it in items))))
+        arena, records, items_dev, _, half = self._source(items)
+        batch = (records, self.n, items_dev, len(items), *(int(v) for v in self.batch_shapes[k]))
+        try:
+            im = ops.augment_batch_hw(arena, *batch, self.dtype, out)
+            return (im, *ops.augment_targets_hw(self._labels, self._label_offsets, *batch, int(sum(self._counts[it.index] for it in items))))
+        finally:
+            if half is not None:
+                self._store.release(half)

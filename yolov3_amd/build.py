@@ -33,6 +33,7 @@ SOURCES = [
     ("label_weights.hip", ["-ffp-contract=off"]),
     ("coco_eval.hip", ["-ffp-contract=off"]),
     ("dataset.hip", ["-ffp-contract=off"]),
+    ("dataset_stage.hip", ["-ffp-contract=off"]),
     ("augment.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),

@@ -1023,6 +1023,36 @@ def dataset_targets(labels: torch.Tensor, label_offsets: torch.Tensor, images: t
     return targets, offsets
 
 
+def dataset_stage_chunk_bytes() -> int:
+    """the bytes one block of y3_dataset_stage copies: a job of the stage owns ceil(slot / this) chunks"""
+    return int(_lib.lib().y3_dataset_stage_chunk_bytes())
+
+
+def dataset_stage(host_arena: torch.Tensor, src_images: torch.Tensor, n: int, jobs: torch.Tensor, m: int, n_chunks: int, ring: torch.Tensor, dst_images: torch.Tensor,
+                  status: torch.Tensor):
+    """The images of one batch from a pinned HOST arena into a device ring, in one launch on the current stream (y3_dataset_stage): `host_arena` the uint8 arena in
+    pinned host memory, `src_images` its record table on the device as bytes (32 n,), `jobs` DEVICE int64 (>= m, 3) [image, slot offset in `ring`, running chunk
+    count], `n_chunks` the last count.  Writes the m slots of `ring` (DEVICE uint8; the image, then zeros up to the next multiple of 16) and the m records of
+    `dst_images` (DEVICE uint8 (32 n,): the source record with the slot's offset); a job that does not fit is skipped and counted in `status` (DEVICE int32 (1,)).
+    Whether `host_arena` is pinned, mapped host memory is the library's own check: it raises Y3Error and launches nothing for a pageable tensor."""
+    what = "dataset_stage"
+    for t in (src_images, jobs, ring, dst_images, status):
+        require_gpu(t, what)
+    if host_arena.is_cuda or host_arena.dtype != torch.uint8 or host_arena.dim() != 1 or not host_arena.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous uint8 arena of the set in host memory")
+    for t in (src_images, dst_images):
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.numel() != 32 * n:
+            raise TypeError(f"{what} expects the contiguous record tables of the set: uint8 ({32 * n},)")
+    if jobs.dtype != torch.int64 or jobs.dim() != 2 or jobs.shape[1] != 3 or not jobs.is_contiguous() or m < 0 or jobs.shape[0] < m:
+        raise TypeError(f"{what} expects the contiguous int64 (m, 3) job table of the batch, m = {m}")
+    if ring.dtype != torch.uint8 or ring.dim() != 1 or not ring.is_contiguous():
+        raise TypeError(f"{what} expects a contiguous uint8 ring")
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise TypeError(f"{what} expects one int32 status word")
+    _call("y3_dataset_stage", host_arena.data_ptr(), host_arena.numel(), src_images.data_ptr(), int(n), _data(jobs), int(m), int(n_chunks), ring.data_ptr(), ring.numel(),
+          dst_images.data_ptr(), status.data_ptr())
+
+
 AUGMENT_ITEM_BYTES = 1360   # sizeof(y3_augment_item)
 
 
