@@ -528,6 +528,33 @@ int y3_augment_targets_paste(const float* labels, const int64_t* label_offsets, 
                              int32_t count, int32_t S, const int32_t* paste, int32_t n_paste, const int32_t* sel_i, const float* sel_f, const double* boxes,
                              const int32_t* inside, const int32_t* paths, float* targets, int64_t n_rows, int64_t* offsets, void* stream);
 
+/* The second-stage classifier hook of the detect loop (csrc/crops.hip): reference utils/general.py:827-859 apply_classifier (called at detect.py:202-203) for a whole
+ * batch, and the box of upstream save_one_box (Detections.crop).  Nothing here allocates or synchronises.
+ * rows / img_stride / row_stride / counts / bs / max_rows: the padded NMS result as y3_scale_boxes takes it, in the letterboxed space; rows are never written.
+ * classifier_boxes: boxes DEVICE fp32 (bs, max_rows, 4), the reference's `d[:, :4]` after `.long()`: b = xyxy2xywh(row), with square != 0 w = h = max(w, h), w and h
+ *   `* gain + pad` (a product, then a sum), xywh2xyxy, each coordinate truncated towards zero.  apply_classifier: gain 1.3, pad 30, square 1; save_one_box: 1.02, 10, 0.
+ *   Rows at and beyond counts[i] are written as zeros and not read (counts NULL: every row is read).  One thread per detection.  y3_scale_boxes then runs on the table
+ *   with row_stride 4: there is no second definition of that arithmetic.
+ * crop_resize: arena / arena_bytes / images as for y3_dataset_batch (of a record only offset, h, w are read); image i of the batch is record i, n_images >= bs.
+ *   boxes: the scaled, clipped table.  prefix: DEVICE int64 (bs), the exclusive prefix of the counts -- crop k of image i is tile prefix[i] + k of dst, DEVICE
+ *   (n_tiles, 3, S, S) of dst_dtype (Y3_F16 / Y3_BF16 / Y3_F32), contiguous; n_tiles is the host's sum of the counts.  Per tile: the four coordinates truncated,
+ *   h = y2 - y1, w = x2 - x1, cv2.resize(INTER_LINEAR) of the (h, w, 3) cutout to (S, S) in the 8-bit arithmetic of y3_letterbox_u8, every coordinate and coefficient
+ *   relative to the cutout; plane c holds source channel 2 - c as value / 255 (the fp32 IEEE quotient, rounded once to dst_dtype).  16-byte stores when S % 8 == 0
+ *   and dst is 16-byte aligned, element stores otherwise, the same values.  Whatever the tables hold, no read leaves an image's offset .. offset + 3 h w range or the
+ *   arena and no write leaves dst: a tile whose cutout is empty (h < 1 or w < 1), whose box lies outside its image, whose image's record does not lie inside the
+ *   arena or which the prefix and the counts do not place is written as zeros and adds 1 to *status (DEVICE int32, which the caller zeroes).  Limits: S in 1 .. 1024,
+ *   n_tiles <= bs * max_rows, n_tiles * ceil(S / 16) < 2^31 (n_tiles == 0 launches nothing).
+ * keep_matching: classes DEVICE int64 (n_tiles), the classifier's class per tile.  Writes out, DEVICE fp32 (bs, max_rows, 6) contiguous and distinct from rows: per
+ *   image the rows whose (long) cls equals the class of their tile, in order, then zeros up to max_rows; and out_counts, DEVICE int32 (bs).  A tile crop_resize counts
+ *   in *status never matches (the same test, on the same tables).  One block per image. */
+int y3_classifier_boxes(const float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, int32_t bs, int32_t max_rows, float gain, float pad,
+                        int32_t square, float* boxes, void* stream);
+int y3_crop_resize(const uint8_t* arena, int64_t arena_bytes, const y3_dataset_image* images, int64_t n_images, const float* boxes, const int32_t* counts,
+                   const int64_t* prefix, int32_t bs, int32_t max_rows, void* dst, int32_t dst_dtype, int64_t n_tiles, int32_t S, int32_t* status, void* stream);
+int y3_keep_matching(const float* rows, int64_t img_stride, int32_t row_stride, const int32_t* counts, const int64_t* prefix, int32_t bs, int32_t max_rows,
+                     const int64_t* classes, int64_t n_tiles, const float* boxes, const y3_dataset_image* images, int64_t n_images, int64_t arena_bytes, float* out,
+                     int32_t* out_counts, void* stream);
+
 /* ComputeLoss: reference utils/loss.py:98-244 (build_targets :183-244, __call__ :131-181, criteria :104-129,
  * FocalLoss :31-63 when fl_gamma > 0) with upstream bbox_iou(CIoU) and smooth_bce.
  * preds: HOST array of nl DEVICE pointers, level i is contiguous (bs, na, ny[i], nx[i], nc+5) of `dtype`;

@@ -31,7 +31,10 @@ Public surface mirrors the reference's own Python signatures:
     freeze_layers                        (reference train.py:217-223, --freeze: the training engine skips the backward work of frozen layers)
     save_checkpoint / smart_resume / strip_optimizer   (reference train.py:470-488, utils/torch_utils.py smart_resume, utils/general.py strip_optimizer)
     save_reference_checkpoint / export_reference / to_reference   (the way out: files the unmodified reference's attempt_load, strip_optimizer and smart_resume read)
-    DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py)
+    apply_classifier / apply_classifier_batched / classifier_crops / DeviceImages   (reference utils/general.py:827-859, detect.py:202-203: the second-stage classifier -- every
+                                         detection of a batch cut out of its native image, resized to 224 x 224, RGB CHW / 255, in one launch; the rows the classifier confirms
+                                         compacted in another)
+    DetectMultiBackend (.pt branch), attempt_load, AutoShape   (reference models/common.py, models/experimental.py; Detections.crop())
     Ensemble                             (reference models/experimental.py:74-86, `--weights a.pt b.pt`: every member decodes into its window of one prediction)
 Everything executes through libyolov3_hip.so (include/yolov3_hip.h); there is no CPU/PyTorch fallback.
 """
@@ -46,6 +49,7 @@ from .dataset import DeviceDataset, rect_batch_shapes  # noqa: F401
 from .augment import DeviceRectTrainDataset, DeviceTrainDataset, draw_item  # noqa: F401
 from .batching import multi_scale_size, preprocess_batch, quad_collate, resize_batch  # noqa: F401
 from .autoshape import AutoShape, Detections, letterbox_batch  # noqa: F401
+from .crops import DeviceImages, apply_classifier, apply_classifier_batched, classifier_crops  # noqa: F401
 from .coco_eval import CocoEval, CocoGroundTruth, CocoResult  # noqa: F401
 from .outputs import coco80_to_coco91_class, output_to_target, save_json_batched, save_one_json, save_one_txt, save_txt_batched  # noqa: F401
 from .compat import attempt_load, save_checkpoint, smart_resume, strip_optimizer  # noqa: F401

@@ -4,8 +4,9 @@ numpy / PIL images of any size go in; each is uploaded once as raw HWC uint8 and
 (csrc/val_edge.hip: cv2.resize INTER_LINEAR + 114-border + HWC->CHW in one pass, reference utils/augmentations.py:104-134),
 the uint8 batch feeds the model's first kernel directly (the /255 of models/common.py:868 happens inside the stem
 convolution), then batched NMS and batched scale_boxes (one launch each instead of the per-image loop of :871-872).
-``Detections`` has the reference's data attributes and its text half (``str()`` / ``print()`` / ``pandas()``); the rendering helpers (show/save/crop/render) are
-outside the hot path and not provided.
+``Detections`` has the reference's data attributes, its text half (``str()`` / ``print()`` / ``pandas()``) and ``crop()``, whose boxes come from one launch of
+y3_classifier_boxes and one of y3_scale_boxes (csrc/crops.hip, csrc/val_edge.hip) and one copy to the host; show / save / render draw with upstream's Annotator and a
+font, neither of which is here, and are not provided.
 """
 from __future__ import annotations
 
@@ -114,6 +115,63 @@ class Detections:
             a = [[[*x[:5], int(x[5]), self._name(int(x[5]))] for x in t.tolist()] for t in getattr(self, k)]
             setattr(new, k, [pd.DataFrame(x, columns=c) for x in a])
         return new
+
+    def crop(self, save=True, save_dir="runs/detect/exp", exist_ok=False):
+        """reference models/common.py:974-980 (`_run(crop=True)`, :916-928): per image, in reversed(pred) order, {"box", "conf", "cls", "label", "im"} with `im` the crop
+        of upstream save_one_box (gain 1.02, pad 10, not squared, clipped to the image; ims[i][y1:y2, x1:x2, ::-1]).  The boxes of all images are formed on the device
+        (crop_boxes) and read back in one copy.  save=True writes every crop to save_dir/crops/<class name>/<file> as save_one_box does (Pillow, quality=95,
+        subsampling=0, an existing name incremented); the un-annotated whole images the reference's `save` also writes next to them are not written."""
+        save_dir = increment_path(save_dir, exist_ok, mkdir=True) if save else None
+        live = [i for i, p in enumerate(self.pred) if p.shape[0]]
+        boxes = crop_boxes([self.pred[i] for i in live], [self.ims[i].shape[:2] for i in live]) if live else []
+        crops = []
+        for i, b in zip(live, boxes):
+            im, pred = self.ims[i], self.pred[i]
+            for j in reversed(range(pred.shape[0])):
+                *box, conf, cls = pred[j]
+                name = self._name(int(cls))
+                x1, y1, x2, y2 = b[j]
+                cut = im[y1:y2, x1:x2, ::-1]
+                if save:
+                    file = increment_path(save_dir / "crops" / name / self.files[i]).with_suffix(".jpg")
+                    file.parent.mkdir(parents=True, exist_ok=True)
+                    from PIL import Image
+
+                    Image.fromarray(np.ascontiguousarray(cut[..., ::-1])).save(str(file), quality=95, subsampling=0)
+                crops.append({"box": box, "conf": conf, "cls": cls, "label": f"{name} {conf:.2f}", "im": cut})
+        return crops
+
+
+def increment_path(path, exist_ok=False, sep="", mkdir=False):
+    """upstream increment_path with the reference's sep="" (utils/general.py:862): runs/exp -> runs/exp2, runs/exp3, ...; a file keeps its suffix"""
+    path = Path(path)
+    if path.exists() and not exist_ok:
+        path, suffix = (path.with_suffix(""), path.suffix) if path.is_file() else (path, "")
+        n = 2
+        while Path(f"{path}{sep}{n}{suffix}").exists():
+            n += 1
+        path = Path(f"{path}{sep}{n}{suffix}")
+    if mkdir:
+        path.mkdir(parents=True, exist_ok=True)
+    return path
+
+
+def crop_boxes(pred, shapes, gain=1.02, pad=10, square=False):
+    """The integer boxes of upstream save_one_box for a list of (n, 6) DEVICE predictions in native pixels and the (h, w) of their images -> per image an (n, 4) int
+    list [x1, y1, x2, y2]: y3_classifier_boxes, then y3_scale_boxes with gain 1 and pad 0 (its clip to the image), then ONE copy to the host."""
+    counts = [int(p.shape[0]) for p in pred]
+    for p in pred:
+        ops.require_gpu(p, "Detections.crop")
+    dev = pred[0].device
+    rows = torch.zeros(len(pred), max(counts), 6, dtype=torch.float32, device=dev)
+    for i, p in enumerate(pred):
+        rows[i, : counts[i]] = p
+    counts_t = torch.tensor(counts, dtype=torch.int32).to(dev, non_blocking=True)
+    boxes = ops.classifier_boxes(rows, counts_t, gain, pad, square)
+    params = torch.tensor([[1.0, 0.0, 0.0, float(w), float(h)] for h, w in shapes], dtype=torch.float32).to(dev, non_blocking=True)
+    ops.scale_boxes_raw(boxes, boxes.stride(0), 4, counts_t, len(pred), boxes.shape[1], params)
+    host = boxes.to(torch.int32).tolist()
+    return [host[i][: counts[i]] for i in range(len(pred))]
 
 
 def _xyxy2xywh(x):

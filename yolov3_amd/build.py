@@ -35,6 +35,7 @@ SOURCES = [
     ("dataset.hip", ["-ffp-contract=off"]),
     ("dataset_stage.hip", ["-ffp-contract=off"]),
     ("augment.hip", ["-ffp-contract=off"]),
+    ("crops.hip", ["-ffp-contract=off"]),
     ("loss.hip", ["-ffp-contract=off"]),
     ("train.hip", []),
     ("filter_bank.hip", []),

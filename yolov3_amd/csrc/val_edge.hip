@@ -8,6 +8,7 @@
 // fp32 arithmetic in the reference's operation order (built with -ffp-contract=off; IEEE division as torch's CPU kernels).
 #include "y3_bilinear.h"
 #include "y3_common.h"
+#include "y3_resize_u8.h"
 
 namespace {
 
@@ -51,17 +52,6 @@ struct LetterboxArgs {
     int h0, w0, cs, H1, W1, nh, nw, top, left, color;
     double scale_x, scale_y; // 1 / (nw / w0), 1 / (nh / h0) as cv2 computes them
 };
-Y3_DEV void lb_coef(int d, double scale, int size, bool clamp_frac, int& s, int& c0, int& c1) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    s = (int)floorf(f);
-    f -= (float)s;
-    if (clamp_frac) {   // x axis: outside columns read one pixel with full weight
-        if (s < 0) { f = 0.0f; s = 0; }
-        if (s >= size - 1) { f = 0.0f; s = size - 1; }
-    }
-    c0 = (int)(short)__float2int_rn((1.0f - f) * 2048.0f);
-    c1 = (int)(short)__float2int_rn(f * 2048.0f);
-}
 __global__ __launch_bounds__(256) void letterbox_u8_kernel(const LetterboxArgs p) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= p.W1 || y >= p.H1) return;
@@ -72,8 +62,8 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(const LetterboxArgs p
         return;
     }
     int sx, a0, a1, sy, b0, b1;
-    lb_coef(dx, p.scale_x, p.w0, true, sx, a0, a1);
-    lb_coef(dy, p.scale_y, p.h0, false, sy, b0, b1);
+    y3_resize_coef(dx, p.scale_x, p.w0, true, sx, a0, a1);   // (y3_resize_u8.h: the one definition of cv2's coefficients)
+    y3_resize_coef(dy, p.scale_y, p.h0, false, sy, b0, b1);
     const int sx1 = sx + 1 < p.w0 ? sx + 1 : sx;   // weight 0 whenever it would fall outside
     const int r0 = sy < 0 ? 0 : (sy > p.h0 - 1 ? p.h0 - 1 : sy), r1 = sy + 1 < 0 ? 0 : (sy + 1 > p.h0 - 1 ? p.h0 - 1 : sy + 1);
     const unsigned char* q0 = p.src + ((long long)r0 * p.w0) * p.cs;

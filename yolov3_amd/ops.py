@@ -1250,6 +1250,114 @@ def augment_copy_paste(labels: torch.Tensor, label_offsets: torch.Tensor, vertic
     return out, targets, offsets, polygons, (sel_i, sel_f, masks.view(n_masks, 2 * size, 2 * size // 32))
 
 
+# The classifier-crop wrappers (csrc/crops.hip), organised as the augment wrappers above: one validator per argument group, each refusal carrying `what`.
+CROP_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+CROP_MAX_SIZE = 1024
+
+
+def _detections(what: str, rows: torch.Tensor, counts: torch.Tensor):
+    """the padded NMS result: rows fp32 (bs, max_rows, >= 6) with unit stride along a row, counts DEVICE int32 (bs,) -> (rows, img_stride, row_stride, counts, bs, max_rows)
+    as the exports take them"""
+    require_gpu(rows, what)
+    require_gpu(counts, what)
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] < 6 or (rows.numel() and rows.stride(2) != 1):
+        raise TypeError(f"{what} expects the fp32 (bs, max_det, 6) rows of non_max_suppression_batched")
+    if counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() != rows.shape[0] or not counts.is_contiguous():
+        raise TypeError(f"{what} expects {rows.shape[0]} contiguous int32 counts, one per image")
+    return rows.data_ptr(), int(rows.stride(0)), int(rows.stride(1)), counts.data_ptr(), int(rows.shape[0]), int(rows.shape[1])
+
+
+def _box_table(what: str, boxes: torch.Tensor, bs: int, max_rows: int):
+    require_gpu(boxes, what)
+    if boxes.dtype != torch.float32 or tuple(boxes.shape) != (bs, max_rows, 4) or not boxes.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous fp32 ({bs}, {max_rows}, 4) box table of classifier_boxes")
+
+
+def _tiles(what: str, prefix: torch.Tensor, bs: int, max_rows: int, n_tiles: int):
+    require_gpu(prefix, what)
+    if prefix.dtype != torch.int64 or prefix.dim() != 1 or prefix.numel() != bs or not prefix.is_contiguous():
+        raise TypeError(f"{what} expects {bs} contiguous int64 prefix entries, one per image")
+    if not 0 <= n_tiles <= bs * max_rows:
+        raise ValueError(f"{what}: {n_tiles} crops of {bs} images with at most {max_rows} detections each")
+
+
+def _image_set(what: str, arena: torch.Tensor, images: torch.Tensor, bs: int):
+    """the arena and the record table of the batch's source images (crops.DeviceImages): one record per image of the batch"""
+    require_gpu(arena, what)
+    require_gpu(images, what)
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous() or arena.numel() < 4 or arena.numel() % 4:
+        raise TypeError(f"{what} expects the contiguous uint8 arena of the images, a positive multiple of 4 bytes")
+    if images.dtype != torch.uint8 or images.dim() != 1 or not images.is_contiguous() or images.numel() % 32:
+        raise TypeError(f"{what} expects the contiguous record table of the images: uint8, 32 bytes each")
+    if images.numel() != 32 * bs:
+        raise ValueError(f"{what}: {images.numel() // 32} images for the detections of {bs}")
+    return images.data_ptr(), int(bs)
+
+
+def classifier_boxes(rows: torch.Tensor, counts: torch.Tensor, gain: float = 1.3, pad: float = 30.0, square: bool = True) -> torch.Tensor:
+    """The padded, squared, truncated boxes of apply_classifier in one launch (y3_classifier_boxes): `rows` / `counts` the DEVICE output of non_max_suppression_batched
+    in the letterboxed space -> DEVICE fp32 (bs, max_det, 4), zeros at and beyond an image's count.  `rows` is not written.  square=False, gain=1.02, pad=10: the box
+    of upstream save_one_box."""
+    what = "classifier_boxes"
+    det = _detections(what, rows, counts)
+    boxes = torch.empty(det[4], det[5], 4, dtype=torch.float32, device=rows.device)
+    if boxes.numel():
+        _call("y3_classifier_boxes", *det, float(gain), float(pad), 1 if square else 0, boxes.data_ptr())
+    return boxes
+
+
+def crop_resize(arena: torch.Tensor, images: torch.Tensor, boxes: torch.Tensor, counts: torch.Tensor, prefix: torch.Tensor, n_tiles: int, size: int = 224,
+                dtype: torch.dtype = torch.float32, status: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """The crops of a batch in one launch (y3_crop_resize): `arena` / `images` the source images and their records (32 bs,), `boxes` the scaled, clipped table of
+    classifier_boxes + scale_boxes, `prefix` DEVICE int64 (bs,) the exclusive prefix of `counts`, `n_tiles` their sum as the host knows it ->
+    (DEVICE (n_tiles, 3, size, size) in `dtype`: RGB, CHW, divided by 255; status DEVICE int32 (1,): the crops written as zeros)."""
+    what = "crop_resize"
+    bs, max_rows = int(boxes.shape[0]), int(boxes.shape[1]) if boxes.dim() == 3 else 0
+    _box_table(what, boxes, bs, max_rows)
+    require_gpu(counts, what)
+    if counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() != bs or not counts.is_contiguous():
+        raise TypeError(f"{what} expects {bs} contiguous int32 counts, one per image")
+    n_tiles, size = int(n_tiles), int(size)
+    _tiles(what, prefix, bs, max_rows, n_tiles)
+    if not 1 <= size <= CROP_MAX_SIZE:
+        raise ValueError(f"{what}: size = {size}; crops are 1 .. {CROP_MAX_SIZE} pixels on a side")
+    if dtype not in CROP_DTYPES:
+        raise TypeError(f"{what} writes float16 / bfloat16 / float32, not {dtype}")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=boxes.device)
+    elif not status.is_cuda or status.dtype != torch.int32 or status.numel() != 1:
+        raise TypeError(f"{what} expects one int32 status word on the device")
+    out = _out(what, out, (n_tiles, 3, size, size), dtype, boxes.device)
+    if n_tiles:
+        batch = _image_set(what, arena, images, bs)
+        _call("y3_crop_resize", arena.data_ptr(), arena.numel(), *batch, boxes.data_ptr(), counts.data_ptr(), prefix.data_ptr(), bs, max_rows, out.data_ptr(), DTYPE_CODE[dtype],
+              n_tiles, size, status.data_ptr())
+    return out, status
+
+
+def keep_matching(rows: torch.Tensor, counts: torch.Tensor, prefix: torch.Tensor, classes: torch.Tensor, boxes: torch.Tensor, arena: torch.Tensor, images: torch.Tensor):
+    """The filter of apply_classifier in one launch (y3_keep_matching): `classes` DEVICE int64 (n_tiles,), the classifier's class per crop ->
+    (DEVICE fp32 (bs, max_det, 6): per image the rows whose (long) cls equals the class of their crop, in order, then zeros; DEVICE int32 (bs,) the new counts).
+    A crop the status word of crop_resize counted never matches."""
+    what = "keep_matching"
+    det = _detections(what, rows, counts)
+    bs, max_rows = det[4], det[5]
+    _box_table(what, boxes, bs, max_rows)
+    require_gpu(classes, what)
+    if classes.dtype != torch.int64 or classes.dim() != 1 or not classes.is_contiguous():
+        raise TypeError(f"{what} expects the contiguous int64 classes of the crops")
+    _tiles(what, prefix, bs, max_rows, int(classes.numel()))
+    out = torch.empty(bs, max_rows, 6, dtype=torch.float32, device=rows.device)
+    out_counts = torch.empty(bs, dtype=torch.int32, device=rows.device)
+    if bs and max_rows:
+        batch = _image_set(what, arena, images, bs)
+        _call("y3_keep_matching", *det[:4], prefix.data_ptr(), bs, max_rows, _data(classes), int(classes.numel()), boxes.data_ptr(), *batch, arena.numel(), out.data_ptr(),
+              out_counts.data_ptr())
+    else:
+        out_counts.zero_()
+    return out, out_counts
+
+
 _coco_ws: dict = {}
 
 
